@@ -17,6 +17,11 @@ torch.distributed (RCCL) carries the barrier and one all_reduce of {max elapsed,
 
 Prints ONE JSON line on rank 0 (DESIGN.md section "Measurement").  PyTorch is used for device memory, the HIP
 stream, events and torch.distributed only; the codec is liblc3gpu.so (hand-written HIP) called through its C ABI.
+
+A plain run sets up, warms up, times exactly --steps steps and prints the line (`value`, `ms_per_step`).  `--full` adds everything
+else the line can carry: the parity gate against the CPU oracle, per-kernel HIP-event times and the roofline, the other caller
+arrangements, the sustained leg, the other shapes of the batch, the host-resident leg and the CPU baseline.  `--dump-outputs DIR`
+writes what the last timed step computed (frame bytes, decoded PCM) as float32 .npy files, so that two builds can be compared.
 `--engine emu` (tests only) swaps the GPU engine for the CPU wave emulator of the device code and RCCL for gloo, so
 that the launcher and the sharding / reduction path run in a GPU-less container (tests/test_dist_gloo.py).
 """
@@ -40,6 +45,8 @@ HBM_PEAK_GBS = 8000.0             # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 CLOCK_MHZ = 2400.0                # max shader clock (MI355X_MICROARCH.md, chip-level parameters)
 N_SIMD = 1024                     # 256 CUs x 4 SIMDs
 KERNEL_EVENTS_EVERY = 10          # the library's per-kernel HIP events are recorded on every tenth step of the timed region (16 records a step: ~2 % of it)
+DUMP_BYTES = 48 << 20             # --dump-outputs: float32 bytes written at most; larger outputs are dumped for a seeded sample of the streams
+DUMP_SEED = 0x4C43335F
 
 
 def parse_args(argv=None):
@@ -82,6 +89,12 @@ def parse_args(argv=None):
                          "host-resident leg")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: parity gate, per-kernel times and roofline, other arrangements, sustained leg, other shapes, "
+                         "host-resident leg and CPU baseline (the --no-* and --also / --sustain-seconds options above select among these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's frame bytes (frame_bytes.npy) and decoded PCM (pcm_out.npy, round trip) "
+                         "as float32, rank 0's streams; above %d MB in all, a fixed seeded sample of the streams" % (DUMP_BYTES >> 20))
     ap.add_argument("--engine", choices=("gpu", "emu"), default="gpu", help=argparse.SUPPRESS)
     a = ap.parse_args(argv)
     if a.also is None:
@@ -578,13 +591,13 @@ class GpuEngine:
             return self.bufs[(self.k - 1) % 3]
         return self.d_bytes
 
-    def last_bytes(self, k):
-        """the sampled streams' frame bytes of the most recent step"""
-        return self.last_bytes_all()[self.torch.from_numpy(self.sample(k)).cuda()].cpu().numpy()
+    def outputs(self, streams):
+        """(frame bytes, decoded PCM or None) of the most recent step for the given stream indices, as host arrays"""
+        idx = self.torch.from_numpy(streams).cuda()
+        return (self.last_bytes_all()[idx].cpu().numpy(), self.d_out[idx].cpu().numpy() if self.d_out is not None else None)
 
     def results(self, k):
-        idx = self.torch.from_numpy(self.sample(k)).cuda()
-        return (self.last_bytes(k), self.d_out[idx].cpu().numpy() if self.d_out is not None else None)
+        return self.outputs(self.sample(k))
 
     def timing_start(self, every=1):
         encs, decs = self._handles()
@@ -699,6 +712,9 @@ class EmuEngine:
 
     def reset(self):
         pass
+
+    def outputs(self, streams):
+        return self.bytes[streams], (self.out[streams] if self.out is not None else None)
 
     def results(self, k):
         return self.bytes[:k], (self.out[:k] if self.out is not None else None)
@@ -866,6 +882,21 @@ def host_resident_bench(torch, pkg, pcm_host, S, T, reps=3):
                     "D2H copy of channel ranges of 32 768 frames on three internal HIP streams (copy-in, kernels, copy-out side by side); best of %d repetitions; NOT `value` (inputs there are resident in HBM)" % reps}
 
 
+def dump_outputs(eng, out_dir, S, T, mode):
+    """--dump-outputs: the last step's frame bytes and (round trip) decoded PCM as float32 .npy files (exact: bytes and int16 samples), every
+    stream when that fits in DUMP_BYTES, else the same seeded sample of streams on every run"""
+    import numpy as np
+
+    per_stream = 4 * T * (NBYTES + (NF if mode == "roundtrip" else 0))
+    k = max(1, min(S, DUMP_BYTES // per_stream))
+    streams = np.arange(S) if k == S else np.sort(np.random.default_rng(DUMP_SEED).choice(S, k, replace=False))
+    got_b, got_p = eng.outputs(streams)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "frame_bytes.npy"), got_b.astype(np.float32))
+    if got_p is not None:
+        np.save(os.path.join(out_dir, "pcm_out.npy"), got_p.astype(np.float32))
+
+
 # ---------------------------------------------------------------------------------------------------------------
 def run_rank(args):
     import numpy as np
@@ -992,14 +1023,17 @@ def run_rank(args):
         return par, mism
 
     parity, mismatches = None, 0
-    if not args.no_parity:
+    if args.full and not args.no_parity:
         parity, mismatches = gate(main_arr)
 
-    # timed region: exactly K steps; per-kernel durations from HIP events the C ABI records on the launch streams on every tenth
+    # timed region: exactly K steps.  --full: per-kernel durations from HIP events the C ABI records on the launch streams on every tenth
     # step (an event after every kernel of every step costs the streams ~0.03 ms per step), and one event after every step for the
     # per-step minimum / median
     eng.set_arrangement(main_arr)
-    elapsed, kernel_ms, step_ms = eng.timed_steps(args.steps, args.warmup, dist=dist, kernel_events=KERNEL_EVENTS_EVERY, marks=True)
+    elapsed, kernel_ms, step_ms = eng.timed_steps(args.steps, args.warmup, dist=dist, kernel_events=KERNEL_EVENTS_EVERY if args.full else 0,
+                                                  marks=args.full)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, args.dump_outputs, S, T, mode)
 
     # max time over ranks, counters summed over ranks (the only collective of the job)
     red_dev = "cpu" if (dist is not None and dist.get_backend() == "gloo") else eng.device
@@ -1007,7 +1041,7 @@ def run_rank(args):
                                                                   mismatches=mismatches, force=rccl_single)
     # the other arrangement (same K steps, its own parity gate) and the sustained leg of the main one: single rank only
     other, others, sustained = None, [], None
-    if world == 1 and not emu:
+    if world == 1 and not emu and args.full:
         if can_pipeline and not args.no_overlap_probe:
             for arr2 in [a for a in ("single", "pipelined", "staggered") + tuple(args.also) if a != main_arr]:
                 par2, mism2 = gate(arr2) if not args.no_parity else (None, 0)
@@ -1022,7 +1056,8 @@ def run_rank(args):
             eng.set_arrangement(main_arr)
             sustained = eng.sustained(args.sustain_seconds)
     other_modes, host_leg = None, None
-    if world == 1 and not emu and mode == "roundtrip" and not args.no_other_modes and eng.d_full is not None and S * T == 65536 and S == 16384:
+    if (args.full and world == 1 and not emu and mode == "roundtrip" and not args.no_other_modes and eng.d_full is not None and S * T == 65536
+            and S == 16384):
         # SURVEY 8d Config 2's own two modes (65 536 x 1 from fresh state, 4 096 x 16 streaming), the live-server tick (65 536 x 1, state
         # carried) and the T sweep between them, on the same resident PCM; the headline shape (16 384 x 4) is `value` above
         eng.sync()
@@ -1047,9 +1082,9 @@ def run_rank(args):
 
     if rank == 0:
         cpu = None
-        if not args.no_cpu_baseline and world == 1 and not emu:
+        if args.full and not args.no_cpu_baseline and world == 1 and not emu:
             cpu = cpu_baseline(mode)
-        elif world > 1:
+        elif args.full and world > 1:
             # the contract times the CPU path on rank 0 at N = 1 only (N ranks share the host's cores with their own parity gates): the N = 1
             # line of the same command is where the figure is
             cpu = {"value": None, "unit": "frames/s", "cores": None, "kind": "port",

@@ -95,14 +95,52 @@ def test_synth_shards_are_consistent():
     assert a.dtype == np.int16 and np.abs(a).max() > 1000
 
 
-def _run_bench(*extra):
+def _run_bench(*extra, full=True):
     import json
     import subprocess
 
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--engine", "emu", "--steps", "1", "--warmup", "0",
-                        *extra], capture_output=True, text=True, timeout=600)
+                        *(["--full"] if full else []), *extra], capture_output=True, text=True, timeout=600)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     return p.returncode, (json.loads(lines[-1]) if lines else None)
+
+
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """without --full the line carries the timed steps only (no parity gate); --dump-outputs writes the last step's frame bytes and
+    PCM as float32, the same on every run, equal to the oracle's on the bench generator's PCM (the emulator starts every step afresh)"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import oracle_lib as O
+
+    synth = importlib.import_module("lc3-codec_amd.synth")
+    got = []
+    for d in (tmp_path / "a", tmp_path / "b"):
+        rc, line = _run_bench("--steps", "2", "--dump-outputs", str(d), full=False)
+        assert rc == 0 and line is not None and line["steps"] == 2 and line["parity"] is None
+        assert abs(line["value"] - 2 * 8 / (line["ms_per_step"] * 2e-3)) < 1e-6 * line["value"]
+        got.append((np.load(d / "frame_bytes.npy"), np.load(d / "pcm_out.npy")))
+    (b, p), (b2, p2) = got
+    assert b.dtype == np.float32 and p.dtype == np.float32 and np.array_equal(b, b2) and np.array_equal(p, p2)
+    ref_b = O.encode_batch(synth.make_pcm(4, 2, 480, 48000), 150)
+    assert np.array_equal(b, ref_b) and np.array_equal(p, O.decode_batch(ref_b, 480))
+
+
+def test_bench_dump_of_a_large_batch_is_a_fixed_sample(tmp_path):
+    """the headline batch (16 384 streams x 4 frames) is larger than the dump budget: a seeded sample of streams, the same every time"""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class Eng:
+        def outputs(self, streams):
+            return (np.broadcast_to(streams[:, None, None], (len(streams), 4, 150)),
+                    np.broadcast_to(-streams[:, None, None], (len(streams), 4, 480)))
+
+    for d in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(Eng(), str(d), 16384, 4, "roundtrip")
+    a, b = np.load(tmp_path / "a" / "frame_bytes.npy"), np.load(tmp_path / "b" / "frame_bytes.npy")
+    total = sum(os.path.getsize(f) for f in (tmp_path / "a").iterdir())
+    assert total <= 64 << 20 and 1000 < a.shape[0] < 16384 and np.array_equal(a, b)
+    s = a[:, 0, 0]
+    assert np.all(np.diff(s) > 0) and np.array_equal(np.load(tmp_path / "a" / "pcm_out.npy")[:, 0, 0], -s)
 
 
 def test_bench_launcher_starts_two_ranks():

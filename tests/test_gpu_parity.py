@@ -1625,15 +1625,15 @@ def test_8khz_encode_switch_and_mixed_handle_with_switches():
 
 
 # ---------------------------------------------------------------- the production launcher on the GPU
-def _bench_line(extra, env_extra, timeout=900):
+def _bench_line(extra, env_extra, timeout=900, full=True):
     import json
     import os
     import subprocess
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--no-cpu-baseline", *extra], capture_output=True, text=True,
-                       timeout=timeout, env=dict(os.environ, **env_extra))
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--no-cpu-baseline", *(["--full"] if full else []), *extra],
+                       capture_output=True, text=True, timeout=timeout, env=dict(os.environ, **env_extra))
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     return p, (json.loads(lines[-1]) if lines else None)
 
@@ -1705,6 +1705,25 @@ def test_default_arrangement_is_the_pipeline_object_and_a_mismatch_fails_the_run
                           {"LC3_BENCH_TEST_CORRUPT_GATE": "1"})
     assert line is not None and line["parity_mismatches_all_ranks"] > 0 and not line["parity"]["bitstream_exact"]
     assert p.returncode == 3, p.returncode
+
+
+def test_plain_bench_run_dumps_the_last_timed_step(tmp_path):
+    """bench.py without --full: the timed steps and the line only (no gate, no per-kernel events, no further legs); --dump-outputs
+    writes the last timed step's frame bytes and PCM, which match the oracle run over the same frames from fresh state (warmup + steps
+    steps of T frames, state carried)"""
+    W, K, S, T = 1, 3, 1024, 4
+    p, line = _bench_line(["--steps", str(K), "--warmup", str(W), "--streams", str(S), "--dump-outputs", str(tmp_path)], {}, full=False)
+    assert p.returncode == 0 and line is not None, p.stderr[-2000:]
+    assert line["steps"] == K and line["config"]["arrangement"] == "pipeline" and line["dtype"] == "f32"
+    assert abs(line["value"] - S * T / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+    assert line["parity"] is None and line["kernel_ms"] is None and line["other_arrangements"] == [] and line["sustained"] is None
+    got_b, got_p = np.load(tmp_path / "frame_bytes.npy"), np.load(tmp_path / "pcm_out.npy")
+    assert got_b.dtype == np.float32 and got_b.shape == (S, T, 150) and got_p.dtype == np.float32 and got_p.shape == (S, T, 480)
+    n, R = (W + K) * T, line["config"]["resident_frames_per_stream"]
+    assert n <= R  # (the steps code consecutive frames: no wrap-around)
+    ref_b = O.encode_batch(np.ascontiguousarray(synth.make_pcm(S, R, 480, 48000)[:, :n]), 150, threads=8)
+    assert np.array_equal(got_b, ref_b[:, n - T:])
+    assert np.array_equal(got_p, O.decode_batch(ref_b, 480, threads=8)[:, n - T:])
 
 
 def test_every_arrangement_produces_the_single_stream_output():

@@ -4,7 +4,7 @@ OUT=gpurun_out
 mkdir -p $OUT
 run() {  # tag, env...
     tag=$1; shift
-    env "$@" python3 bench.py --no-cpu-baseline --steps 40 --warmup 5 --sustain-seconds 0 > $OUT/exp_arr_$tag.json 2> $OUT/exp_arr_$tag.err
+    env "$@" python3 bench.py --full --no-cpu-baseline --steps 40 --warmup 5 --sustain-seconds 0 > $OUT/exp_arr_$tag.json 2> $OUT/exp_arr_$tag.err
     python3 - "$tag" $OUT/exp_arr_$tag.json <<'PY'
 import json, sys
 try:

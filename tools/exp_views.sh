@@ -11,7 +11,7 @@ j = json.loads(sys.stdin.read()); print('  %-46s %6.2f M  %s  exact %s' % (j['co
   LC3GPU_LIB=$lib python3 tools/mixed_batch.py 2>/dev/null | tail -1 | python3 -c "
 import json, sys
 j = json.loads(sys.stdin.read()); print('  mixed batch %6.2f M  %.3f ms/step  parity %s' % (j['frames_per_s'] / 1e6, j['ms_per_step'], j['parity_all_streams_first_step']))"
-  LC3GPU_LIB=$lib python3 bench.py --no-parity --no-cpu-baseline --sustain-seconds 0 --steps 32 --warmup 4 2>/dev/null | python3 -c "
+  LC3GPU_LIB=$lib python3 bench.py --full --no-parity --no-cpu-baseline --sustain-seconds 0 --steps 32 --warmup 4 2>/dev/null | python3 -c "
 import json, sys
 j = json.loads([l for l in sys.stdin if l.startswith('{')][-1]); o = j['other_arrangement']
 print('  headline: pipelined %6.2f M  single %6.2f M  front alone %.3f' % (j['value'] / 1e6, o['value'] / 1e6, o['kernel_ms']['lc3_enc_front_kernel']))"

@@ -9,7 +9,7 @@ OUT=gpurun_out
 mkdir -p $OUT
 rm -f $OUT/${TAG}_repeat_lines.jsonl
 for i in $(seq 1 $N); do
-    python3 bench.py --no-cpu-baseline --no-overlap-probe --no-other-modes --sustain-seconds 0 >> $OUT/${TAG}_repeat_lines.jsonl 2>> $OUT/${TAG}_repeat.err
+    python3 bench.py --full --no-cpu-baseline --no-overlap-probe --no-other-modes --sustain-seconds 0 >> $OUT/${TAG}_repeat_lines.jsonl 2>> $OUT/${TAG}_repeat.err
 done
 python3 - "$OUT/${TAG}_repeat_lines.jsonl" > $OUT/${TAG}_repeat_bench.json <<'PY'
 import json, sys
