@@ -118,6 +118,24 @@ int lc3gpu_encode_range(lc3gpu_encoder *enc, int first_channel, int n_channels, 
 int lc3gpu_encode_layout(lc3gpu_encoder *enc, int layout, const int16_t *d_pcm, uint8_t *d_out, int nbytes, int n_frames,
                          void *hip_stream);
 
+/* Batch encode with a frame size per frame: d_nbytes[c][t] is what the reference's buf_out.len() is for frame t of channel c
+ * (lc3_encoder.rs:65, it may change per call), so every channel may change its bitrate in every frame of one launch.  DEVICE pointers,
+ * planar, every channel of the handle:
+ *   d_pcm     int16[num_channels][n_frames][nf]          as lc3gpu_encode (4-byte aligned)
+ *   d_nbytes  uint16[num_channels][n_frames]
+ *   d_out     uint8[num_channels][n_frames][slot_bytes]  frame (c, t) is written to the first d_nbytes[c][t] bytes of its slot; the rest
+ *                                                        of the slot is left untouched
+ * slot_bytes 20 ... 400, else LC3GPU_ELENGTH.  Null pointers, misaligned PCM and mixed handles: LC3GPU_EINVAL.  A bound handle takes the
+ * call on its bound stream only.  The sizes are device data, so they are checked on the device: an entry outside [20, slot_bytes] is
+ * clamped into that range, the frame is encoded (and the channel's state advanced) at the clamped size, and the clamp is counted
+ * (lc3gpu_encoder_size_clamps).  The carried state is that of the uniform calls: sized and uniform calls may alternate on a handle, and a
+ * sized call whose sizes all equal n gives the bytes of lc3gpu_encode at nbytes = n.  The call always runs unsplit (LC3GPU_SPLIT is
+ * ignored) with the one-lane-per-frame packer (LC3GPU_PACK_PC is ignored).  Asynchronous on hip_stream. */
+int lc3gpu_encode_vbr(lc3gpu_encoder *enc, const int16_t *d_pcm, uint8_t *d_out, const uint16_t *d_nbytes, int slot_bytes,
+                      int n_frames, void *hip_stream);
+/* sticky count of the frame sizes lc3gpu_encode_vbr has clamped into [20, slot_bytes] on this handle (waits for the handle's work in flight) */
+int lc3gpu_encoder_size_clamps(lc3gpu_encoder *enc, uint64_t *out);
+
 /* Mixed-configuration encoder: n_streams streams, each with its own rate, frame duration and frame size; 8 kHz streams are
  * refused (LC3GPU_EUNSUPPORTED, as lc3gpu_encoder_create).  lc3gpu_encode_mixed encodes n_frames frames of every stream
  * with one launch per kernel.  Ragged DEVICE buffers, streams in descriptor order, each stream planar:
@@ -157,6 +175,19 @@ int lc3gpu_decode(lc3gpu_decoder *dec, const uint8_t *d_in, const uint8_t *d_bad
                   int n_frames, void *hip_stream);
 int lc3gpu_decode_range(lc3gpu_decoder *dec, int first_channel, int n_channels, const uint8_t *d_in,
                         const uint8_t *d_bad_frame, int16_t *d_pcm, int nbytes, int n_frames, void *hip_stream);
+/* Batch decode with a frame size per frame: d_nbytes[c][t] is what the reference's buf_in.len() is for frame t of channel c
+ * (lc3_decoder.rs:85).  DEVICE pointers, planar, every channel of the handle:
+ *   d_in      uint8[num_channels][n_frames][slot_bytes]  frame (c, t) is the first d_nbytes[c][t] bytes of its slot
+ *   d_nbytes  uint16[num_channels][n_frames]
+ *   d_bad_frame, d_pcm                                   as lc3gpu_decode
+ * slot_bytes 1 ... 400, else LC3GPU_ELENGTH.  Null d_in / d_nbytes / d_pcm, misaligned PCM and mixed handles: LC3GPU_EINVAL.  An entry of
+ * 0 is an empty buf_in: the frame is concealed (the reference does the same, with nbits = 0 in the post-filter); an entry above
+ * slot_bytes is treated as 0.  A frame flagged in d_bad_frame is concealed with its own size as nbits.  Concealed frames count in
+ * lc3gpu_decoder_plc_events.  The carried state is that of the uniform calls (they may alternate on a handle), and a sized call whose
+ * entries all equal n gives the PCM of lc3gpu_decode at nbytes = n.  The call always runs unsplit (LC3GPU_SPLIT is ignored) with the
+ * one-lane-per-frame parser (LC3GPU_PARSE_PC is ignored); LC3GPU_RECON selects the reconstruction form as for lc3gpu_decode. */
+int lc3gpu_decode_vbr(lc3gpu_decoder *dec, const uint8_t *d_in, const uint16_t *d_nbytes, const uint8_t *d_bad_frame, int16_t *d_pcm,
+                      int slot_bytes, int n_frames, void *hip_stream);
 /* same as lc3gpu_decode with the buffers (and the flag array) in `layout` (LC3GPU_LAYOUT_*) */
 int lc3gpu_decode_layout(lc3gpu_decoder *dec, int layout, const uint8_t *d_in, const uint8_t *d_bad_frame, int16_t *d_pcm,
                          int nbytes, int n_frames, void *hip_stream);

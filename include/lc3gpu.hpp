@@ -62,6 +62,18 @@ public:
         int rc = lc3gpu_encode_mixed(h_, d_pcm, d_out, n_frames, hip_stream);
         if (rc) throw Error(rc, "encode_mixed");
     }
+    // a frame size per frame (DEVICE buffers): d_nbytes[channel][frame] is that frame's buf_out.len(), written to the first d_nbytes bytes
+    // of its slot of slot_bytes; sizes outside [20, slot_bytes] are clamped and counted (size_clamps)
+    void encode_vbr(const int16_t *d_pcm, uint8_t *d_out, const uint16_t *d_nbytes, int slot_bytes, int n_frames, void *hip_stream = nullptr) {
+        int rc = lc3gpu_encode_vbr(h_, d_pcm, d_out, d_nbytes, slot_bytes, n_frames, hip_stream);
+        if (rc) throw Error(rc, "encode_vbr");
+    }
+    uint64_t size_clamps() {
+        uint64_t v = 0;
+        int rc = lc3gpu_encoder_size_clamps(h_, &v);
+        if (rc) throw Error(rc, "size_clamps");
+        return v;
+    }
     uint64_t pair_timeouts() {
         uint64_t v = 0;
         int rc = lc3gpu_encoder_pair_timeouts(h_, &v);
@@ -114,6 +126,13 @@ public:
         int rc = lc3gpu_decoder_plc_events(h_, &v);
         if (rc) throw Error(rc, "plc_events");
         return v;
+    }
+    // a frame size per frame (DEVICE buffers): d_nbytes[channel][frame] is that frame's buf_in.len(), its bytes the first d_nbytes of its
+    // slot of slot_bytes; 0 or above slot_bytes: concealed
+    void decode_vbr(const uint8_t *d_in, const uint16_t *d_nbytes, int16_t *d_pcm, int slot_bytes, int n_frames, void *hip_stream = nullptr,
+                    const uint8_t *d_bad_frame = nullptr) {
+        int rc = lc3gpu_decode_vbr(h_, d_in, d_nbytes, d_bad_frame, d_pcm, slot_bytes, n_frames, hip_stream);
+        if (rc) throw Error(rc, "decode_vbr");
     }
     uint64_t pair_timeouts() {
         uint64_t v = 0;

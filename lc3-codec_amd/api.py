@@ -247,6 +247,9 @@ def load_library():
     L.lc3gpu_encode_frame_debug.argtypes = [vp, vp, i, vp, i, vp]
     L.lc3gpu_encode.argtypes = [vp, vp, vp, i, i, vp]
     L.lc3gpu_encode_range.argtypes = [vp, i, i, vp, vp, i, i, vp]
+    L.lc3gpu_encode_vbr.argtypes = [vp, vp, vp, vp, i, i, vp]
+    L.lc3gpu_encoder_size_clamps.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
+    L.lc3gpu_decode_vbr.argtypes = [vp, vp, vp, vp, vp, i, i, vp]
     L.lc3gpu_encoder_state_size.restype = ctypes.c_size_t
     L.lc3gpu_encoder_state_size.argtypes = [vp]
     L.lc3gpu_encoder_state_save.argtypes = [vp, vp, ctypes.c_size_t]
@@ -325,7 +328,7 @@ ABI_SYMBOLS = [
     "lc3gpu_host_free", "lc3gpu_pipeline_create", "lc3gpu_pipeline_create_mixed", "lc3gpu_pipeline_submit_mixed", "lc3gpu_pipeline_encode_mixed",
     "lc3gpu_pipeline_decode_mixed", "lc3gpu_pipeline_destroy", "lc3gpu_pipeline_reset", "lc3gpu_pipeline_submit",
     "lc3gpu_pipeline_encode", "lc3gpu_pipeline_decode", "lc3gpu_pipeline_wait", "lc3gpu_pipeline_join", "lc3gpu_pipeline_follow", "lc3gpu_pipeline_mark",
-    "lc3gpu_pipeline_groups", "lc3gpu_pipeline_group", "lc3gpu_pipeline_last_hip_error",
+    "lc3gpu_pipeline_groups", "lc3gpu_pipeline_group", "lc3gpu_pipeline_last_hip_error", "lc3gpu_encode_vbr", "lc3gpu_encoder_size_clamps", "lc3gpu_decode_vbr",
 ]
 
 # LC3GPU_SPEC_*: opt-in corrections of the reference's deviations from the LC3 specification (default 0 = reference behaviour)
@@ -510,6 +513,22 @@ class Lc3Encoder:
         if rc:
             raise Lc3EncoderError(rc, "encode")
 
+    def encode_vbr(self, d_pcm, d_out, d_nbytes, slot_bytes, n_frames, stream=None):
+        """batch with a frame size per frame: DEVICE int16[S][T][nf], DEVICE uint16 d_nbytes[S][T] (each frame's buf_out.len()) ->
+        DEVICE uint8[S][T][slot_bytes], frame (s, t) in the first d_nbytes[s][t] bytes of its slot; sizes outside [20, slot_bytes] are
+        clamped and counted (size_clamps).  Asynchronous on `stream`"""
+        rc = self._L.lc3gpu_encode_vbr(self._h, _ptr(d_pcm), _ptr(d_out), _ptr(d_nbytes), int(slot_bytes), int(n_frames), _ptr(stream))
+        if rc:
+            raise Lc3EncoderError(rc, "encode_vbr")
+
+    def size_clamps(self):
+        """frame sizes encode_vbr has clamped into [20, slot_bytes] on this handle (sticky; waits for the handle's work in flight)"""
+        v = ctypes.c_uint64()
+        rc = self._L.lc3gpu_encoder_size_clamps(self._h, ctypes.byref(v))
+        if rc:
+            raise Lc3EncoderError(rc, "size_clamps")
+        return int(v.value)
+
     def stage_event(self, stage, event):
         """every batch call from now on records `event` (the caller's; None clears) behind the kernels of `stage` (ENC_STAGE_*)"""
         rc = self._L.lc3gpu_encoder_stage_event(self._h, int(stage), _event_handle(event))
@@ -664,6 +683,15 @@ class Lc3Decoder:
                                              _ptr(d_bad_frame), _ptr(d_pcm), int(nbytes), int(n_frames), _ptr(stream))
         if rc:
             raise Lc3DecoderError(rc, "decode")
+
+    def decode_vbr(self, d_in, d_nbytes, d_pcm, slot_bytes, n_frames, stream=None, d_bad_frame=None):
+        """batch with a frame size per frame: DEVICE uint8[S][T][slot_bytes] (frame (s, t) = the first d_nbytes[s][t] bytes of its slot),
+        DEVICE uint16 d_nbytes[S][T] (each frame's buf_in.len(); 0 or above slot_bytes: concealed) -> DEVICE int16[S][T][nf].
+        Asynchronous on `stream`"""
+        rc = self._L.lc3gpu_decode_vbr(self._h, _ptr(d_in), _ptr(d_nbytes), _ptr(d_bad_frame), _ptr(d_pcm), int(slot_bytes), int(n_frames),
+                                       _ptr(stream))
+        if rc:
+            raise Lc3DecoderError(rc, "decode_vbr")
 
     def stage_event(self, stage, event):
         """every batch call from now on records `event` (the caller's; None clears) behind the kernels of `stage` (DEC_STAGE_PARSE)"""

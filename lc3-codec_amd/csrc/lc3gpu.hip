@@ -535,6 +535,8 @@ LC3_TU_STATIC __device__ unsigned long long lc3_prof_acc[64];  // 0..31 stage su
 #include "lc3_dev_dec.h"
 #include "lc3_dev_dec_recon.h"
 #include "lc3_dev_enc.h"
+#include "lc3_dev_enc_vbr.h"
+#include "lc3_dev_dec_vbr.h"
 #include "lc3_host_plan.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -882,6 +884,130 @@ __global__ __launch_bounds__(256) void lc3_pack_mixed_kernel(lc3_groups G, const
     const lc3_group &g = G.g[lc3_find_group(G, blockIdx.x, 1)];
     lc3_pack_body(blockIdx.x - g.wg_frame, g.ne, planes + (size_t)g.frame_base * (size_t)EP_WORDS, out, g.nbytes, g.n_streams * T, T,
                   g.first_stream, io);
+}
+#endif
+
+// ---- a frame size per frame (lc3gpu_encode_vbr; lc3_dev_enc_vbr.h) ----------------------------------------------------------------------
+// Kernels of their own, so that the uniform ones compile exactly as before: the size of frame (s, t) is nb[s * T + t] clamped into
+// [20, slot], the bytes of frame f go to out + f * slot.  Planar buffers, every channel of the handle.  Main unit only: the headline view and
+// the run-time view (every other configuration).
+#if LC3_IN_HOST_TU
+template <class CV>
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, lc3_front_waves<CV>::value) void lc3_enc_front_vbr_kernel(
+    lc3_cfg_slot<CV> cfg, lc3_enc_state *states, int n_streams, const int16_t *pcm, float *mid, int32_t *planes, const uint16_t *nb, int slot,
+    unsigned long long *clamps, int n_frames, int fresh, int spec_flags) {
+    const int lane = threadIdx.x & 63, wave = LC3_WAVE_ID();
+    lc3_enc_lds &L = lc3_enc_wg[wave];
+    const int wg_s0 = (int)blockIdx.x * LC3_WG_WAVES, s_raw = wg_s0 + wave;
+    const int valid = s_raw < n_streams;
+    const int s = valid ? s_raw : n_streams - 1;
+    typename CV::bind_t c0 = CV::bind(lc3_cfg_table[cfg.id]);
+    const int nf = c0.nf, z = c0.z;
+    lc3_enc_state *gst = states + (size_t)s;
+    const lc3_io io = {0, nullptr};
+#ifndef LC3_TABLES_IN_GLOBAL
+    lc3_front_tables_stage_image(c0.stage_image);
+    lc3_fft_tables_stage_image(c0.stage_image);  // ends with the workgroup barrier
+#endif
+    if (lane == 0) L.spec_flags = spec_flags;
+    if (fresh) lc3_enc_state_init(L, lane, gst, valid);
+    else lc3_enc_state_load(L, lane, gst);
+    for (int t = 0; t < n_frames; t++) {
+        const size_t f = (size_t)s * (size_t)n_frames + (size_t)t;
+        int32_t *plane = valid ? LC3_PLANE_COL(planes, f, EP_WORDS) : nullptr;
+        float *mcol = valid ? mid + f * (size_t)MP_WORDS : nullptr;
+        int stride, clamped;
+        const int16_t *frame = lc3_io_pcm(io, pcm, nf, 0, s, t, n_frames, &stride);
+        const int16_t *hist = t > 0 ? frame - (size_t)(nf - z) : (fresh ? nullptr : gst->hist);
+        const int nbytes = lc3_vbr_enc_size(nb, f, slot, &clamped);
+        if (valid && clamped && lane == 0) atomicAdd(clamps, 1ull);
+        // (the phase is the same for every wave of the workgroup: the gathered LTPF blocks stay workgroup-uniform)
+        const int phase = lc3_vbr_front_phase(c0, nb, slot, wg_s0, n_streams, t, n_frames, LC3_WG_WAVES);
+        lc3_encode_front_wave(cfg, L, lane, frame, hist, gst, mcol, plane, LC3_PLANE_STRIDE, nbytes, nullptr, 1, 1, phase,
+                              lc3_front_outline<CV>::value);
+    }
+    if (valid) {
+        int stride = 1;
+        const int16_t *last = n_frames > 0 ? lc3_io_pcm(io, pcm, nf, 0, s, n_frames - 1, n_frames, &stride) : nullptr;
+        lc3_enc_state_store(c0, L, lane, gst, last, stride);
+    }
+}
+template <class CV>
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, LC3_BACK_WAVES) void lc3_enc_back_vbr_kernel(lc3_cfg_slot<CV> cfg, lc3_enc_state *states,
+                                                                                int n_streams, const float *mid, int32_t *planes,
+                                                                                const uint16_t *nb, int slot, int n_frames, int spec_flags) {
+    const int lane = threadIdx.x & 63, wave = LC3_WAVE_ID();
+    lc3_enc_lds &L = lc3_enc_wg[wave];
+    const int s_raw = (int)blockIdx.x * LC3_WG_WAVES + wave;
+    const int valid = s_raw < n_streams;
+    const int s = valid ? s_raw : n_streams - 1;
+    lc3_enc_state *gst = states + (size_t)s;
+#if LC3_SPEC_IN_LDS
+    {
+        const uint32_t *lk = (const uint32_t *)LC3T_AC_SPEC_LOOKUP, *bt = (const uint32_t *)&LC3T_AC_SPEC_BITS[0][0];
+        uint32_t *dl = (uint32_t *)lc3_spec_tab.lookup, *db = (uint32_t *)lc3_spec_tab.bits;
+        for (int i = threadIdx.x; i < 1024; i += 64 * LC3_WG_WAVES) dl[i] = lk[i];
+        for (int i = threadIdx.x; i < 64 * 17 / 2; i += 64 * LC3_WG_WAVES) db[i] = bt[i];
+        __syncthreads();  // (the back half's last workgroup barrier: nothing after it depends on a frame size)
+    }
+#endif
+    if (lane == 0) L.spec_flags = spec_flags;
+    lc3_enc_state_load(L, lane, gst);
+    typename CV::bind_t c0 = CV::bind(lc3_cfg_table[cfg.id]);
+    const size_t fbase = (size_t)s * (size_t)n_frames;
+    lc3_encode_back_stream_vbr(cfg, L, lane, mid, planes, fbase, n_frames, nb + fbase, slot, valid, nullptr);
+    if (valid) lc3_enc_state_store(c0, L, lane, gst, nullptr);
+}
+// The packer with a size per lane: staging slots of `slot` bytes, each frame copied out with its own size (the rest of its slot untouched).
+// Dynamic LDS: LC3_PACK_LDS_FIXED + blockDim.x * slot (rounded up to 4) + 4 (sink); static: the block's sizes.
+__global__ __launch_bounds__(256) void lc3_pack_vbr_kernel(int ne, const int32_t *planes, uint8_t *out, const uint16_t *nb, int slot,
+                                                           int n_frames) {
+    LC3_LANE_KERNEL_BEGIN();
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    __shared__ int s_nb[256];
+    uint8_t *s_lookup = smem;
+    uint32_t *s_cf = (uint32_t *)(smem + 4096);
+    uint32_t *s_tns = (uint32_t *)(smem + 4096 + 64 * 17 * 4);
+    uint8_t *s_bytes = smem + LC3_PACK_LDS_FIXED;
+    const int tid = threadIdx.x, fpb = blockDim.x;
+    const size_t f0 = (size_t)blockIdx.x * (size_t)fpb;
+    const size_t remaining = (size_t)n_frames - f0;
+    const int nfr = remaining < (size_t)fpb ? (int)remaining : fpb;
+    const int total = nfr * slot;
+    {
+        const uint32_t *lk32 = (const uint32_t *)LC3T_AC_SPEC_LOOKUP;
+        uint32_t *d32 = (uint32_t *)s_lookup;
+        for (int i = tid; i < 1024; i += fpb) d32[i] = lk32[i];
+        for (int i = tid; i < 64 * 17; i += fpb) {
+            const int p = i / 17, j = i - 17 * p;
+            s_cf[i] = (uint32_t)(int)LC3T_AC_SPEC_CUMFREQ[p][j] | ((uint32_t)(int)LC3T_AC_SPEC_FREQ[p][j] << 16);
+        }
+        for (int i = tid; i < LC3_TNS_MODEL_WORDS; i += fpb) s_tns[i] = lc3_tns_model_word(i);
+        uint32_t *b32 = (uint32_t *)s_bytes;  // frames start zero-filled
+        for (int i = tid; i < (total + 3) / 4; i += fpb) b32[i] = 0;
+    }
+    const size_t f = f0 + (size_t)tid;
+    s_nb[tid] = f < (size_t)n_frames ? lc3_vbr_enc_size(nb, f, slot) : 0;
+    __syncthreads();
+    if (f < (size_t)n_frames) {
+        lc3_pack_ctx c;
+        c.buf = s_bytes + tid * slot;
+        c.sink = s_bytes + (((size_t)fpb * (size_t)slot + 3) & ~(size_t)3);
+        c.nbytes = s_nb[tid];
+        c.lookup = s_lookup;
+        c.cf = s_cf;
+        c.tns = s_tns;
+        c.plane = LC3_PLANE_COL(planes, f, EP_WORDS);
+        c.stride = LC3_PLANE_STRIDE;
+        lc3_pack_frame(c, ne);
+    }
+    __syncthreads();
+    // the block's slots are one contiguous run of the output: byte i is byte i % slot of frame i / slot, written when inside that frame
+    uint8_t *dst = out + f0 * (size_t)slot;
+    for (int i = tid; i < total; i += fpb) {
+        const int j = (int)((unsigned)i / (unsigned)slot);
+        if (i - j * slot < s_nb[j]) dst[i] = s_bytes[i];
+    }
 }
 #endif
 
@@ -1449,6 +1575,131 @@ __global__ __launch_bounds__(64 * LC3_WG_WAVES, 4) void lc3_decode_mixed_late_ke
 // ---------------------------------------------------------------------------------------------
 // per translation unit: the unit's kernels, its copy of the tables
 // ---------------------------------------------------------------------------------------------
+// ---- decoder with a frame size per frame (lc3gpu_decode_vbr; lc3_dev_dec_vbr.h) --------------------------------------------------------
+// Kernels of their own, as for the encoder: frame f's bytes are the first lc3_vbr_dec_size(nb, f, slot) bytes of in + f * slot (planar,
+// every channel of the handle); an empty frame is concealed without being parsed, as a flagged one is.  The one-lane parser with any of
+// the three reconstruction forms (late: 0 = in the parser, 1 = in the synthesis, 2 = the wave-per-frame kernels).
+#if LC3_IN_HOST_TU
+template <class CV>
+__global__ __launch_bounds__(256) void lc3_parse_vbr_kernel(lc3_cfg_slot<CV> cfg, const uint8_t *in, const uint8_t *bad, const uint16_t *nb,
+                                                            int slot, int32_t *planes, int n_frames, int late) {
+    LC3_LANE_KERNEL_BEGIN();
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    typename CV::bind_t c0 = CV::bind(lc3_cfg_table[cfg.id]);
+    const int ne = c0.ne, fs_ind = c0.fs_ind, n_ms_10 = c0.n_ms_10;
+    const int tid = threadIdx.x, fpb = blockDim.x;
+    uint8_t *s_lookup = smem;
+    uint32_t *s_cf = (uint32_t *)(smem + 4096);
+    uint32_t *s_mpvq = (uint32_t *)(smem + 4096 + 64 * LC3_DCF_ROW_WORDS * 4);
+    uint32_t *s_tns = (uint32_t *)(smem + 4096 + 64 * LC3_DCF_ROW_WORDS * 4 + 16 * 11 * 4);
+    uint16_t *s_ifs = (uint16_t *)(smem + 4096 + 64 * LC3_DCF_ROW_WORDS * 4 + 16 * 11 * 4 + 4 * 152);
+    float *s_scf = (float *)(smem + LC3_PARSE_LDS_FIXED);
+    uint8_t *s_bytes = smem + LC3_PARSE_LDS_FIXED + 16 * 4 * fpb;
+    const size_t f0 = (size_t)blockIdx.x * (size_t)fpb;
+    {
+        for (int i = tid; i < 16 * 11; i += fpb) s_mpvq[i] = LC3T_MPVQ_OFFSETS[i / 11][i % 11];
+        for (int i = tid; i < LC3_TNS_MODEL_WORDS; i += fpb) s_tns[i] = lc3_tns_model_word(i);
+        for (int i = tid; i <= c0.nb; i += fpb) s_ifs[i] = lc3_band_index(c0)[i];
+        const uint32_t *lk32 = (const uint32_t *)LC3T_AC_SPEC_LOOKUP;
+        uint32_t *d32 = (uint32_t *)s_lookup;
+        for (int i = tid; i < 1024; i += fpb) d32[i] = lk32[i];
+        for (int i = tid; i < 64 * LC3_DCF_ROW_WORDS; i += fpb) s_cf[i] = lc3_dcf_word(i);
+        // the block's slots are one contiguous run of the input (the bytes beyond a frame's size come along unused)
+        const size_t remaining = (size_t)n_frames - f0;
+        const int nfr = remaining < (size_t)fpb ? (int)remaining : fpb;
+        const int total = nfr * slot;
+        const uint8_t *src = in + f0 * (size_t)slot;
+        if ((((uintptr_t)src) & 3u) == 0) {
+            const uint32_t *s32 = (const uint32_t *)src;
+            uint32_t *b32 = (uint32_t *)s_bytes;
+            for (int i = tid; i < total / 4; i += fpb) b32[i] = s32[i];
+            for (int i = (total & ~3) + tid; i < total; i += fpb) s_bytes[i] = src[i];
+        } else {
+            for (int i = tid; i < total; i += fpb) s_bytes[i] = src[i];
+        }
+    }
+    __syncthreads();
+    const size_t f = f0 + (size_t)tid;
+    if (f < (size_t)n_frames) {
+        const int len = lc3_vbr_dec_size(nb, f, slot);
+        lc3_parse_ctx c;
+        c.dbg = nullptr;
+        c.bytes = s_bytes + tid * slot;
+        c.len = len;
+        c.lookup = s_lookup;
+        c.cf = s_cf;
+        c.tns = s_tns;
+        c.plane = LC3_PLANE_COL(planes, f, LC3_PLANE_WORDS);
+        c.stride = LC3_PLANE_STRIDE;
+        c.head = 0;
+        c.tail = 0;
+        const int lost = (bad && bad[f]) || len == 0;  // an empty buf_in is concealed (lc3_decoder.rs:138-141)
+        int rc;
+        if (late == 2) rc = lost ? -100 : lc3_parse_frame<0>(c, ne, fs_ind, n_ms_10);
+        else rc = lost ? -100 : lc3_parse_frame<1>(c, ne, fs_ind, n_ms_10);
+        int ok = rc == 0;
+        if (ok && late == 2) {
+            lc3_recon_ctx r;
+            r.scf = nullptr;
+            r.sstride = 0;
+            r.mpvq = s_mpvq;
+            r.ifs = nullptr;
+            lc3_reconstruct_prepare_wave(c);
+            lc3_parse_pulses(c, r);
+        } else if (ok && late) {
+            ok = lc3_reconstruct_prepare_late(c);
+        } else if (ok) {
+            lc3_recon_ctx r;
+            r.scf = s_scf + tid;
+            r.sstride = fpb;
+            r.mpvq = s_mpvq;
+            r.ifs = s_ifs;
+            ok = lc3_reconstruct_frame(c, r, c0);
+        }
+        lc3_px_set(c, AD_OK, ok);
+    }
+}
+template <class CV>
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, LC3_RECON_WAVES) void lc3_recon_vbr_kernel(lc3_cfg_slot<CV> cfg, int32_t *planes,
+                                                                                           const uint16_t *nb, int slot, int n_frames) {
+    const int lane = threadIdx.x & 63, wave = LC3_WAVE_ID();
+    typename CV::bind_t c0 = CV::bind(lc3_cfg_table[cfg.id]);
+    lc3_recon_tables_stage(c0, lc3_recon_tab, (int)threadIdx.x, 64 * LC3_WG_WAVES);
+    __syncthreads();  // (the last workgroup barrier: the frame loop below is per wave)
+    for (size_t f = (size_t)blockIdx.x * LC3_WG_WAVES + (size_t)wave; f < (size_t)n_frames; f += (size_t)gridDim.x * LC3_WG_WAVES)
+        lc3_recon_frame_direct(c0, lc3_recon_tab, lc3_recon_wv[wave], lane, LC3_PLANE_COL(planes, f, LC3_PLANE_WORDS), lc3_vbr_dec_size(nb, f, slot));
+}
+template <class CV, int LATE>
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, LATE ? 4 : LC3_SYNTH_WAVES) void lc3_decode_vbr_kernel(lc3_cfg_slot<CV> cfg, lc3_dec_state *states,
+                                                                                                  int n_streams, const int32_t *planes,
+                                                                                                  int16_t *pcm, const uint16_t *nb, int slot,
+                                                                                                  int n_frames, int fresh) {
+    const int lane = threadIdx.x & 63, wave = LC3_WAVE_ID();
+    lc3_dec_lds &L = lc3_dec_wg[wave];
+    const int s_raw = (int)blockIdx.x * LC3_WG_WAVES + wave;
+    const int valid = s_raw < n_streams;
+    const int s = valid ? s_raw : n_streams - 1;
+    typename CV::bind_t c0 = CV::bind(lc3_cfg_table[cfg.id]);
+    const int nf = c0.nf;
+    lc3_dec_state *gst = states + (size_t)s;
+#ifndef LC3_TABLES_IN_GLOBAL
+    const lc3_fft_image_regs tab_regs = lc3_fft_tables_image_issue(c0.stage_image);
+#endif
+    lc3_i4 st_regs = {0, 0, 0, 0};
+    if (!fresh) st_regs = lc3_dec_state_issue(lane, gst);
+    const size_t fbase = (size_t)s * (size_t)n_frames;
+    lc3_decode_stream_wave_vbr(cfg, L, lane, nb + fbase, slot, planes, fbase, n_frames, gst, valid, pcm + fbase * (size_t)nf, (size_t)nf, 1, LATE,
+                               [&]() {
+#ifndef LC3_TABLES_IN_GLOBAL
+                                   lc3_fft_tables_image_commit(tab_regs);
+#endif
+                                   if (fresh) lc3_dec_state_init(L, lane, gst, valid);
+                                   else lc3_dec_state_commit(L, lane, st_regs);
+                               }, fresh);
+    if (valid) lc3_dec_state_store(c0, L, lane, gst);
+}
+#endif
+
 template <int I> struct lc3_view_by_index { typedef lc3_cfg_any type; };
 #define LC3_X(i, V) template <> struct lc3_view_by_index<i> { typedef V type; };
 LC3_FOR_EACH_VIEW_ALL(LC3_X)
@@ -2171,6 +2422,7 @@ struct lc3gpu_encoder : HandleCommon {
     int32_t *d_planes = nullptr;      // packer planes, EP_WORDS words per frame
     float *d_mid = nullptr;           // mid planes (front half -> vector quantiser -> back half), MP_WORDS words per frame
     size_t planes_frames = 0;
+    unsigned long long *d_vbr_clamps = nullptr;  // sized calls: frame sizes clamped into [20, slot] (sticky; allocated at first use)
 };
 
 struct lc3gpu_decoder : HandleCommon {
@@ -2561,6 +2813,7 @@ int lc3gpu_encoder_destroy(lc3gpu_encoder *e) {
         if (e->d_out1) (void)hipHostFree(e->d_out1);
         if (e->d_dbg) (void)hipFree(e->d_dbg);
         if (e->d_planes) (void)hipFree(e->d_planes);
+        if (e->d_vbr_clamps) (void)hipFree(e->d_vbr_clamps);
         if (e->d_mid) (void)hipFree(e->d_mid);
         e->release_common();
     }
@@ -2769,6 +3022,104 @@ int lc3gpu_encode_range(lc3gpu_encoder *e, int first_channel, int n_channels, co
     LC3_ON_DEVICE(e);
     return encode_launch(e, e->h, first_channel, n_channels, d_pcm, d_out, nbytes, n_frames, LC3GPU_LAYOUT_PLANAR, (hipStream_t)stream,
                          nullptr);
+}
+
+// A frame size per frame (lc3_dev_enc_vbr.h): the four encoder stages as lc3gpu_encode runs them, with the sized front half, back half and
+// packer; the vector quantiser and the symbol preparation do not look at the size.  Always one part (no LC3GPU_SPLIT), always the
+// one-lane-per-frame packer (no producer / consumer pair).
+#define LC3_LAUNCH_VBR(kern, h, grid, block, lds, stream, ...)                                                                   \
+    do {                                                                                                                        \
+        if ((h).view == 1) hipLaunchKernelGGL(kern<lc3_cfg_48k10>, grid, block, lds, stream, lc3_cfg_slot<lc3_cfg_48k10>{(h).slot}, __VA_ARGS__); \
+        else hipLaunchKernelGGL(kern<lc3_cfg_any>, grid, block, lds, stream, lc3_cfg_slot<lc3_cfg_any>{(h).slot}, __VA_ARGS__);                 \
+    } while (0)
+int lc3gpu_encode_vbr(lc3gpu_encoder *e, const int16_t *d_pcm, uint8_t *d_out, const uint16_t *d_nbytes, int slot_bytes, int n_frames,
+                      void *stream_) {
+    if (!e || e->mixed || !d_pcm || !d_out || !d_nbytes) return LC3GPU_EINVAL;
+    if (slot_bytes < LC3_VBR_MIN_BYTES || slot_bytes > LC3_MAX_NE || n_frames <= 0) return LC3GPU_ELENGTH;
+    if (((uintptr_t)d_pcm & 3u) != 0) return LC3GPU_EINVAL;
+    LC3_ON_DEVICE(e);
+    hipStream_t stream = (hipStream_t)stream_;
+    const HostCfg &h = e->h;
+    const int n = e->num_channels;
+    const size_t frames = (size_t)n * (size_t)n_frames;
+    int rc = e->order_begin(stream);
+    if (rc == LC3GPU_OK) rc = encoder_reserve_planes(e, frames, stream);
+    if (rc == LC3GPU_OK && !e->d_vbr_clamps) {
+        HIP_TRY(hipMalloc((void **)&e->d_vbr_clamps, sizeof(unsigned long long)));
+        HIP_TRY(hipMemsetAsync(e->d_vbr_clamps, 0, sizeof(unsigned long long), stream));  // (ordered before this call's kernels)
+    }
+    if (rc) return rc;
+    int fresh = 1;
+    for (int i = 0; i < n; i++) fresh &= e->fresh_mask[(size_t)i];
+    if (!fresh && (rc = encoder_materialise(e, 0, n, stream)) != 0) return rc;
+    auto launched = [] {
+        const hipError_t er = hipGetLastError();
+        if (er == hipSuccess) return LC3GPU_OK;
+        g_last_hip = (int)er;
+        return LC3GPU_EHIP;
+    };
+    const size_t t0 = e->timer.used;
+    e->timer.arm();
+    const dim3 wg_grid((unsigned)((n + LC3_WG_WAVES - 1) / LC3_WG_WAVES)), wg_block(64 * LC3_WG_WAVES);
+    e->timer.mark(stream, -1, 0);
+    LC3_LAUNCH_VBR(lc3_enc_front_vbr_kernel, h, wg_grid, wg_block, lc3_lds_pad(0), stream, e->d_states, n, d_pcm, e->d_mid, e->d_planes, d_nbytes,
+                   slot_bytes, e->d_vbr_clamps, n_frames, fresh, e->spec_flags);
+    rc = launched();
+    if (rc == LC3GPU_OK) {
+        e->timer.mark(stream, 0, 0);
+        rc = e->stage_record(LC3GPU_ENC_STAGE_FRONT, stream);
+    }
+    if (rc == LC3GPU_OK) {
+        hipLaunchKernelGGL(lc3_sns_vq_kernel, dim3((unsigned)((frames + 255) / 256)), dim3(256), 0, stream, h.c.nb, e->d_mid, e->d_planes,
+                           (int)frames, e->spec_flags);
+        rc = launched();
+    }
+    if (rc == LC3GPU_OK) {
+        e->timer.mark(stream, 1, 0);
+        rc = e->stage_record(LC3GPU_ENC_STAGE_VQ, stream);
+    }
+    if (rc == LC3GPU_OK) {
+        LC3_LAUNCH_VBR(lc3_enc_back_vbr_kernel, h, wg_grid, wg_block, lc3_lds_pad(1), stream, e->d_states, n, (const float *)e->d_mid, e->d_planes,
+                       d_nbytes, slot_bytes, n_frames, e->spec_flags | lc3_prep_symbols_flag(frames));
+        rc = launched();
+    }
+    if (rc == LC3GPU_OK) {
+        e->timer.mark(stream, 2, 0);
+        rc = e->stage_record(LC3GPU_ENC_STAGE_BACK, stream);
+    }
+    if (rc == LC3GPU_OK && lc3_prep_symbols_mode(frames) == 2) {
+        const size_t wgs = (frames + LC3_WG_WAVES - 1) / LC3_WG_WAVES;
+        LC3_LAUNCH_CFG(lc3_symbols_kernel, h, dim3((unsigned)(wgs < lc3_recon_grid() ? wgs : lc3_recon_grid())), dim3(64 * LC3_WG_WAVES), 0, stream,
+                       e->d_planes, (int)frames);
+        rc = launched();
+    }
+    if (rc == LC3GPU_OK) {
+        const unsigned fpb = lc3_frame_block_fit(LC3_PACK_LDS_FIXED + 256 * sizeof(int), (size_t)slot_bytes);
+        const size_t lds = LC3_PACK_LDS_FIXED + (((size_t)fpb * (size_t)slot_bytes + 3) & ~(size_t)3) + 4;  // + the packer's sink byte
+        hipLaunchKernelGGL(lc3_pack_vbr_kernel, dim3((unsigned)((frames + fpb - 1) / fpb)), dim3(fpb), lds, stream, h.c.ne,
+                           (const int32_t *)e->d_planes, d_out, d_nbytes, slot_bytes, (int)frames);
+        rc = launched();
+    }
+    if (rc == LC3GPU_OK) e->timer.mark(stream, 3, 0);
+    if (rc) {
+        e->timer.rollback(t0);
+        (void)e->order_end(stream);
+        return rc;
+    }
+    for (int i = 0; i < n; i++) e->fresh_mask[(size_t)i] = 0;
+    return e->order_end(stream);
+}
+int lc3gpu_encoder_size_clamps(lc3gpu_encoder *e, uint64_t *out) {
+    if (!e || !out) return LC3GPU_EINVAL;
+    LC3_ON_DEVICE(e);
+    *out = 0;
+    if (!e->d_vbr_clamps) return LC3GPU_OK;
+    int rc = e->quiesce();
+    if (rc) return rc;
+    unsigned long long v = 0;
+    HIP_TRY(hipMemcpy(&v, e->d_vbr_clamps, sizeof v, hipMemcpyDeviceToHost));
+    *out = (uint64_t)v;
+    return LC3GPU_OK;
 }
 
 // every stream of a mixed-configuration handle, ONE launch per kernel
@@ -3117,6 +3468,80 @@ int lc3gpu_decode_layout(lc3gpu_decoder *d, int layout, const uint8_t *d_in, con
 int lc3gpu_decode(lc3gpu_decoder *d, const uint8_t *d_in, const uint8_t *d_bad, int16_t *d_pcm, int nbytes, int n_frames,
                   void *stream) {
     return lc3gpu_decode_layout(d, LC3GPU_LAYOUT_PLANAR, d_in, d_bad, d_pcm, nbytes, n_frames, stream);
+}
+
+// A frame size per frame on the decoder: the parser (one lane per frame), the reconstruction form lc3_recon_mode picks for the launch, the
+// synthesis.  Always one part (no LC3GPU_SPLIT), always the one-lane parser (no producer / consumer pair).
+int lc3gpu_decode_vbr(lc3gpu_decoder *d, const uint8_t *d_in, const uint16_t *d_nbytes, const uint8_t *d_bad, int16_t *d_pcm, int slot_bytes,
+                      int n_frames, void *stream_) {
+    if (!d || d->mixed || !d_in || !d_nbytes || !d_pcm) return LC3GPU_EINVAL;
+    if (slot_bytes < 1 || slot_bytes > LC3_MAX_NE || n_frames <= 0) return LC3GPU_ELENGTH;
+    if (((uintptr_t)d_pcm & 3u) != 0) return LC3GPU_EINVAL;
+    LC3_ON_DEVICE(d);
+    hipStream_t stream = (hipStream_t)stream_;
+    const HostCfg &h = d->h;
+    const int n = d->num_channels;
+    const size_t frames = (size_t)n * (size_t)n_frames;
+    const int fresh = d->fresh_pending ? 1 : 0;  // (a launch over every channel carries a noted reset out itself)
+    int rc = d->order_begin(stream);
+    if (rc == LC3GPU_OK) rc = decoder_reserve_planes(d, frames, stream);
+    if (rc) return rc;
+    const int mode = lc3_recon_mode(frames, n_frames);
+    if (mode == LC3_RECON_WAVE && (rc = lc3_tns_lds_optin()) != LC3GPU_OK) return rc;
+    auto launched = [] {
+        const hipError_t er = hipGetLastError();
+        if (er == hipSuccess) return LC3GPU_OK;
+        g_last_hip = (int)er;
+        return LC3GPU_EHIP;
+    };
+    const size_t t0 = d->timer.used;
+    d->timer.arm();
+    d->timer.mark(stream, -1, 0);
+    const unsigned fpb = lc3_frame_block_fit(LC3_PARSE_LDS_FIXED, (size_t)(64 + slot_bytes));
+    const size_t lds = LC3_PARSE_LDS_FIXED + (size_t)fpb * (size_t)(64 + slot_bytes);
+    LC3_LAUNCH_VBR(lc3_parse_vbr_kernel, h, dim3((unsigned)((frames + fpb - 1) / fpb)), dim3(fpb), lds, stream, d_in, d_bad, d_nbytes, slot_bytes,
+                   d->d_planes, (int)frames, mode);
+    rc = launched();
+    if (rc == LC3GPU_OK) d->timer.mark(stream, 0, 0);
+    if (rc == LC3GPU_OK && mode == LC3_RECON_WAVE) {
+        const size_t wgs = (frames + LC3_WG_WAVES - 1) / LC3_WG_WAVES;
+        LC3_LAUNCH_VBR(lc3_recon_vbr_kernel, h, dim3((unsigned)(wgs < lc3_recon_grid() ? wgs : lc3_recon_grid())), dim3(64 * LC3_WG_WAVES), 0,
+                       stream, d->d_planes, d_nbytes, slot_bytes, (int)frames);
+        rc = launched();
+        if (rc == LC3GPU_OK) d->timer.mark(stream, 1, 0);
+        if (rc == LC3GPU_OK) {
+            LC3_LAUNCH_CFG(lc3_tns_kernel, h, dim3((unsigned)((frames + LC3_TNS_FPB - 1) / LC3_TNS_FPB)), dim3(LC3_TNS_FPB), LC3_TNS_LDS, stream,
+                           d->d_planes, (int)frames);
+            rc = launched();
+        }
+        if (rc == LC3GPU_OK) d->timer.mark(stream, 2, 0);
+    }
+    if (rc == LC3GPU_OK) rc = d->stage_record(LC3GPU_DEC_STAGE_PARSE, stream);
+    if (rc == LC3GPU_OK) {
+        const dim3 grid((unsigned)((n + LC3_WG_WAVES - 1) / LC3_WG_WAVES)), block(64 * LC3_WG_WAVES);
+        const int32_t *pl = d->d_planes;
+        if (mode == LC3_RECON_LATE) {
+            if (h.view == 1) hipLaunchKernelGGL((lc3_decode_vbr_kernel<lc3_cfg_48k10, 1>), grid, block, 0, stream, lc3_cfg_slot<lc3_cfg_48k10>{h.slot},
+                                                d->d_states, n, pl, d_pcm, d_nbytes, slot_bytes, n_frames, fresh);
+            else hipLaunchKernelGGL((lc3_decode_vbr_kernel<lc3_cfg_any, 1>), grid, block, 0, stream, lc3_cfg_slot<lc3_cfg_any>{h.slot}, d->d_states,
+                                    n, pl, d_pcm, d_nbytes, slot_bytes, n_frames, fresh);
+        } else {
+            if (h.view == 1) hipLaunchKernelGGL((lc3_decode_vbr_kernel<lc3_cfg_48k10, 0>), grid, block, lc3_lds_pad(2), stream,
+                                                lc3_cfg_slot<lc3_cfg_48k10>{h.slot}, d->d_states, n, pl, d_pcm, d_nbytes, slot_bytes, n_frames, fresh);
+            else hipLaunchKernelGGL((lc3_decode_vbr_kernel<lc3_cfg_any, 0>), grid, block, lc3_lds_pad(2), stream, lc3_cfg_slot<lc3_cfg_any>{h.slot},
+                                    d->d_states, n, pl, d_pcm, d_nbytes, slot_bytes, n_frames, fresh);
+        }
+        rc = launched();
+    }
+    if (rc == LC3GPU_OK) d->timer.mark(stream, 3, 0);
+    if (rc) {
+        d->timer.rollback(t0);
+        (void)d->order_end(stream);
+        if (fresh) (void)decoder_init_states(d);
+        return rc;
+    }
+    if (fresh) d->fresh_pending = false;
+    return d->order_end(stream);
 }
 
 int lc3gpu_decode_range(lc3gpu_decoder *d, int first_channel, int n_channels, const uint8_t *d_in, const uint8_t *d_bad,

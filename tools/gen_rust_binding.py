@@ -19,7 +19,7 @@ HEADER = os.path.join(ROOT, "include", "lc3gpu.h")
 OPAQUE = {"lc3gpu_encoder": "Lc3GpuEncoder", "lc3gpu_decoder": "Lc3GpuDecoder", "lc3gpu_pipeline": "Lc3GpuPipeline",
           "lc3gpu_stream_desc": "Lc3GpuStreamDesc"}
 SCALAR = {"int": "i32", "unsigned": "u32", "unsigned int": "u32", "float": "f32", "double": "f64", "size_t": "usize",
-          "int16_t": "i16", "uint8_t": "u8", "int32_t": "i32", "uint32_t": "u32", "int64_t": "i64", "uint64_t": "u64",
+          "int16_t": "i16", "uint16_t": "u16", "uint8_t": "u8", "int32_t": "i32", "uint32_t": "u32", "int64_t": "i64", "uint64_t": "u64",
           "unsigned long long": "u64", "char": "c_char", "void": "c_void"}
 
 
@@ -155,6 +155,18 @@ impl Lc3EncoderGpu {
     pub unsafe fn encode_device(&mut self, d_pcm: *const i16, d_out: *mut u8, nbytes: usize, n_frames: usize, hip_stream: *mut c_void) -> i32 {
         lc3gpu_encode(self.h, d_pcm, d_out, nbytes as i32, n_frames as i32, hip_stream)
     }
+    /// a frame size per frame: d_nbytes[channel][frame] is that frame's buf_out.len(); frame (c, t) goes to the first d_nbytes[c][t]
+    /// bytes of slot (c, t) of slot_bytes bytes (device pointers, include/lc3gpu.h)
+    pub unsafe fn encode_vbr_device(&mut self, d_pcm: *const i16, d_out: *mut u8, d_nbytes: *const u16, slot_bytes: usize, n_frames: usize,
+                                    hip_stream: *mut c_void) -> i32 {
+        lc3gpu_encode_vbr(self.h, d_pcm, d_out, d_nbytes, slot_bytes as i32, n_frames as i32, hip_stream)
+    }
+    /// frame sizes encode_vbr_device has clamped into [20, slot_bytes] (sticky)
+    pub fn size_clamps(&mut self) -> Result<u64, i32> {
+        let mut v: u64 = 0;
+        let rc = unsafe { lc3gpu_encoder_size_clamps(self.h, &mut v) };
+        if rc == 0 { Ok(v) } else { Err(rc) }
+    }
 }
 impl Drop for Lc3EncoderGpu {
     fn drop(&mut self) {
@@ -201,6 +213,12 @@ impl Lc3DecoderGpu {
         assert_eq!(data.len(), self.num_channels * n_frames * nbytes);
         let bad = bad_frame.map_or(core::ptr::null(), |b| b.as_ptr());
         unsafe { lc3gpu_decode_host(self.h, data.as_ptr(), bad, pcm.as_mut_ptr(), nbytes as i32, n_frames as i32) }
+    }
+    /// a frame size per frame: frame (c, t) is the first d_nbytes[c][t] bytes of slot (c, t) of slot_bytes bytes (its buf_in.len(); 0 or
+    /// above slot_bytes: concealed); device pointers, include/lc3gpu.h
+    pub unsafe fn decode_vbr_device(&mut self, d_in: *const u8, d_nbytes: *const u16, d_bad_frame: *const u8, d_pcm: *mut i16, slot_bytes: usize,
+                                    n_frames: usize, hip_stream: *mut c_void) -> i32 {
+        lc3gpu_decode_vbr(self.h, d_in, d_nbytes, d_bad_frame, d_pcm, slot_bytes as i32, n_frames as i32, hip_stream)
     }
     /// frames concealed so far (decoder/packet_loss_concealment.rs:63-85)
     pub fn plc_events(&mut self) -> u64 {
