@@ -188,6 +188,50 @@ int lc3gpu_decode_range(lc3gpu_decoder *dec, int first_channel, int n_channels, 
  * one-lane-per-frame parser (LC3GPU_PARSE_PC is ignored); LC3GPU_RECON selects the reconstruction form as for lc3gpu_decode. */
 int lc3gpu_decode_vbr(lc3gpu_decoder *dec, const uint8_t *d_in, const uint16_t *d_nbytes, const uint8_t *d_bad_frame, int16_t *d_pcm,
                       int slot_bytes, int n_frames, void *hip_stream);
+/* Frame inspection: the side information and the decode status of every frame of a batch, without a handle (the reference's
+ * side_info_reader::read, decoder/side_info_reader.rs:29, needs only the configuration; read_frame, decoder/lc3_decoder.rs:165-178, returns
+ * the error that decode swallows at :138).  DEVICE pointers, a flat list of n_frames frames:
+ *   d_in         uint8[n_frames][slot_bytes]  frame i is the first d_nbytes[i] bytes of slot i (every frame slot_bytes long when d_nbytes is
+ *                                             NULL): planar and interleaved batches and the slots of the _vbr calls alike
+ *   d_nbytes     uint16[n_frames] or NULL
+ *   d_bad_frame  uint8[n_frames] or NULL      as lc3gpu_decode
+ *   d_info       lc3gpu_frame_info[n_frames]  one 128-byte record per frame
+ * Any of the 12 configurations (8 kHz included).  slot_bytes 1 ... 400, else LC3GPU_ELENGTH; null d_in / d_info, a negative n_frames or an
+ * unknown configuration: LC3GPU_EINVAL; n_frames = 0 launches nothing.  Asynchronous on hip_stream, like the batch calls.
+ *
+ * The status of a frame, by precedence: FLAGGED (d_bad_frame[i] != 0: its bytes are not read), EMPTY (a d_nbytes entry of 0 or above
+ * slot_bytes), then the frame's own: OK, SIDE_INFO + k for SideInfoError k, ARITH + k for ArithmeticDecodeError k (enum order of the
+ * reference: 1 BufferReaderError, 2 BandwidthIdxOutOfRange, 3 LastNonZeroTupleGreaterThanYLen, 4 PlcTriggerSns1OutOfRange,
+ * 5 PlcTriggerSns2OutOfRange; 1 ArithmeticCodec, 2 TnsOrder, 3 TnsCoef, 4 SpectralData, 5 SpectralBoolData, 6 NegativeResidualNumBits,
+ * 7 ResidualData, 8 ResidualBoolDataOverflow -- 1, 7 and 8 cannot occur once the side information has parsed).
+ * The contract: status != 0 exactly when lc3gpu_decode / lc3gpu_decode_vbr conceal that frame, given the same bytes, sizes and flags.  The
+ * one exception is a parser wave pair that gave up on its partner, which lc3gpu_decoder_pair_timeouts reports. */
+#define LC3GPU_FRAME_OK 0
+#define LC3GPU_FRAME_FLAGGED 1
+#define LC3GPU_FRAME_EMPTY 2
+#define LC3GPU_FRAME_SIDE_INFO 16
+#define LC3GPU_FRAME_ARITH 32
+typedef struct lc3gpu_frame_info {
+    int32_t status; /* LC3GPU_FRAME_* */
+    int32_t nbytes; /* the size the decoder takes for this frame: slot_bytes or d_nbytes[i]; 0 for EMPTY */
+    /* side_info_reader::read (decoder/side_info.rs:20-31): valid when status is OK or LC3GPU_FRAME_ARITH + k, else 0 */
+    int32_t bandwidth, lastnz, lsb_mode, global_gain_index, num_tns_filters, rc_order_ari_input[2];
+    int32_t sns_ind_lf, sns_ind_hf, sns_ls_inda, sns_ls_indb;
+    uint32_t sns_idx_a, sns_idx_b;
+    int32_t sns_submode_lsb, sns_submode_msb, sns_g_ind;
+    int32_t pitch_present, ltpf_active, pitch_index, noise_factor;
+    /* arithmetic_codec::decode (decoder/arithmetic_codec.rs:99-107): valid when status is OK, else 0 */
+    int32_t rc_order[2], n_residual_bits, noise_filling_seed, is_zero_frame;
+    uint8_t rc_i[16];
+    int32_t reserved; /* 0 */
+} lc3gpu_frame_info;
+#ifdef __cplusplus
+static_assert(sizeof(lc3gpu_frame_info) == 128, "lc3gpu_frame_info is 128 bytes");
+#else
+_Static_assert(sizeof(lc3gpu_frame_info) == 128, "lc3gpu_frame_info is 128 bytes");
+#endif
+int lc3gpu_inspect(int frame_us, int fs_hz, const uint8_t *d_in, const uint16_t *d_nbytes, const uint8_t *d_bad_frame, int slot_bytes,
+                   int n_frames, lc3gpu_frame_info *d_info, void *hip_stream);
 /* same as lc3gpu_decode with the buffers (and the flag array) in `layout` (LC3GPU_LAYOUT_*) */
 int lc3gpu_decode_layout(lc3gpu_decoder *dec, int layout, const uint8_t *d_in, const uint8_t *d_bad_frame, int16_t *d_pcm,
                          int nbytes, int n_frames, void *hip_stream);

@@ -146,6 +146,13 @@ private:
     lc3gpu_decoder *h_ = nullptr;
 };
 
+// Frame inspection (lc3gpu_inspect): the side information and decode status of n_frames frames; DEVICE pointers, no handle needed
+inline void inspect(FrameDuration d, SamplingFrequency f, const uint8_t *d_in, lc3gpu_frame_info *d_info, int slot_bytes, int n_frames,
+                    const uint16_t *d_nbytes = nullptr, const uint8_t *d_bad_frame = nullptr, void *hip_stream = nullptr) {
+    int rc = lc3gpu_inspect((int)d, (int)f, d_in, d_nbytes, d_bad_frame, slot_bytes, n_frames, d_info, hip_stream);
+    if (rc) throw Error(rc, "inspect");
+}
+
 // ---- the reference's no_std / no-alloc API shape (lc3_encoder.rs:37-40,212-303, lc3_decoder.rs:56-60,247-310): the
 // number of channels is a compile-time constant instead of a constructor argument (`Lc3Encoder::<NUM_CH>::new(duration,
 // frequency, ..)`, `Lc3Encoder::<NUM_CH>::calc_working_buffer_lengths(duration, frequency)`; default 2 as in the

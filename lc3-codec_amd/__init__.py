@@ -12,6 +12,13 @@ from .api import (  # noqa: F401
     ENC_STAGE_BACK,
     ENC_STAGE_FRONT,
     ENC_STAGE_VQ,
+    FRAME_ARITH,
+    FRAME_EMPTY,
+    FRAME_FLAGGED,
+    FRAME_INFO_DTYPE,
+    FRAME_OK,
+    FRAME_SIDE_INFO,
+    FRAME_STATUS_NAMES,
     FrameDuration,
     Lc3Config,
     Lc3Decoder,
@@ -35,6 +42,8 @@ from .api import (  # noqa: F401
     build_tool,
     clock_probe,
     device_count,
+    frame_status_name,
+    inspect,
     library_path,
     load_library,
     selftest_math,

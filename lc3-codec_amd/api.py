@@ -250,6 +250,7 @@ def load_library():
     L.lc3gpu_encode_vbr.argtypes = [vp, vp, vp, vp, i, i, vp]
     L.lc3gpu_encoder_size_clamps.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     L.lc3gpu_decode_vbr.argtypes = [vp, vp, vp, vp, vp, i, i, vp]
+    L.lc3gpu_inspect.argtypes = [i, i, vp, vp, vp, i, i, vp, vp]
     L.lc3gpu_encoder_state_size.restype = ctypes.c_size_t
     L.lc3gpu_encoder_state_size.argtypes = [vp]
     L.lc3gpu_encoder_state_save.argtypes = [vp, vp, ctypes.c_size_t]
@@ -329,6 +330,7 @@ ABI_SYMBOLS = [
     "lc3gpu_pipeline_decode_mixed", "lc3gpu_pipeline_destroy", "lc3gpu_pipeline_reset", "lc3gpu_pipeline_submit",
     "lc3gpu_pipeline_encode", "lc3gpu_pipeline_decode", "lc3gpu_pipeline_wait", "lc3gpu_pipeline_join", "lc3gpu_pipeline_follow", "lc3gpu_pipeline_mark",
     "lc3gpu_pipeline_groups", "lc3gpu_pipeline_group", "lc3gpu_pipeline_last_hip_error", "lc3gpu_encode_vbr", "lc3gpu_encoder_size_clamps", "lc3gpu_decode_vbr",
+    "lc3gpu_inspect",
 ]
 
 # LC3GPU_SPEC_*: opt-in corrections of the reference's deviations from the LC3 specification (default 0 = reference behaviour)
@@ -337,6 +339,43 @@ SPEC_8KHZ_ENCODE, SPEC_TNS_SSWB_STOP, SPEC_BW_CUTOFF_DB, SPEC_SNS_LAST_GAIN, SPE
 LAYOUT_PLANAR, LAYOUT_INTERLEAVED = 0, 1
 # stage events (LC3GPU_ENC_STAGE_* / LC3GPU_DEC_STAGE_*)
 ENC_STAGE_FRONT, ENC_STAGE_VQ, ENC_STAGE_BACK, DEC_STAGE_PARSE = 0, 1, 2, 0
+
+
+# frame inspection (lc3gpu_inspect): the record of one frame (lc3gpu_frame_info, 128 bytes) and its status codes (LC3GPU_FRAME_*)
+FRAME_INFO_DTYPE = np.dtype([
+    ("status", "<i4"), ("nbytes", "<i4"),
+    ("bandwidth", "<i4"), ("lastnz", "<i4"), ("lsb_mode", "<i4"), ("global_gain_index", "<i4"), ("num_tns_filters", "<i4"),
+    ("rc_order_ari_input", "<i4", (2,)), ("sns_ind_lf", "<i4"), ("sns_ind_hf", "<i4"), ("sns_ls_inda", "<i4"), ("sns_ls_indb", "<i4"),
+    ("sns_idx_a", "<u4"), ("sns_idx_b", "<u4"), ("sns_submode_lsb", "<i4"), ("sns_submode_msb", "<i4"), ("sns_g_ind", "<i4"),
+    ("pitch_present", "<i4"), ("ltpf_active", "<i4"), ("pitch_index", "<i4"), ("noise_factor", "<i4"),
+    ("rc_order", "<i4", (2,)), ("n_residual_bits", "<i4"), ("noise_filling_seed", "<i4"), ("is_zero_frame", "<i4"),
+    ("rc_i", "u1", (16,)), ("reserved", "<i4"),
+])
+assert FRAME_INFO_DTYPE.itemsize == 128
+FRAME_OK, FRAME_FLAGGED, FRAME_EMPTY, FRAME_SIDE_INFO, FRAME_ARITH = 0, 1, 2, 16, 32
+# the reference's error of a frame (decoder/lc3_decoder.rs:36-42): Lc3DecoderError::SideInfo(SideInfoError::..) for FRAME_SIDE_INFO + k,
+# Lc3DecoderError::ArithmeticDecode(ArithmeticDecodeError::..) for FRAME_ARITH + k
+FRAME_STATUS_NAMES = {FRAME_OK: "Ok", FRAME_FLAGGED: "Flagged", FRAME_EMPTY: "Empty"}
+for _k, _n in enumerate(("BufferReaderError", "BandwidthIdxOutOfRange", "LastNonZeroTupleGreaterThanYLen", "PlcTriggerSns1OutOfRange",
+                         "PlcTriggerSns2OutOfRange"), 1):
+    FRAME_STATUS_NAMES[FRAME_SIDE_INFO + _k] = "SideInfo::" + _n
+for _k, _n in enumerate(("ArithmeticCodec", "TnsOrder", "TnsCoef", "SpectralData", "SpectralBoolData", "NegativeResidualNumBits", "ResidualBoolData",
+                         "ResidualBoolDataOverflow"), 1):
+    FRAME_STATUS_NAMES[FRAME_ARITH + _k] = "ArithmeticDecode::" + _n
+
+
+def frame_status_name(status):
+    return FRAME_STATUS_NAMES.get(int(status), "Unknown(%d)" % int(status))
+
+
+def inspect(frame_duration, sampling_frequency, d_in, d_info, slot_bytes, n_frames, d_nbytes=None, d_bad_frame=None, stream=None):
+    """lc3gpu_inspect: the side information and decode status of n_frames frames (include/lc3gpu.h).  DEVICE pointers (or tensors):
+    d_in uint8[n_frames][slot_bytes], d_info FRAME_INFO_DTYPE[n_frames] (128 bytes per frame), d_nbytes uint16[n_frames] or None,
+    d_bad_frame uint8[n_frames] or None.  Asynchronous on `stream`; needs no codec handle."""
+    rc = load_library().lc3gpu_inspect(int(frame_duration), int(sampling_frequency), _ptr(d_in), _ptr(d_nbytes), _ptr(d_bad_frame),
+                                       int(slot_bytes), int(n_frames), _ptr(d_info), _ptr(stream))
+    if rc:
+        raise Lc3GpuError(rc, "inspect")
 
 
 def _event_handle(event):

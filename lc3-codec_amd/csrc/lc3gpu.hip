@@ -537,6 +537,7 @@ LC3_TU_STATIC __device__ unsigned long long lc3_prof_acc[64];  // 0..31 stage su
 #include "lc3_dev_enc.h"
 #include "lc3_dev_enc_vbr.h"
 #include "lc3_dev_dec_vbr.h"
+#include "lc3_dev_dec_inspect.h"
 #include "lc3_host_plan.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -1697,6 +1698,66 @@ __global__ __launch_bounds__(64 * LC3_WG_WAVES, LATE ? 4 : LC3_SYNTH_WAVES) void
                                    else lc3_dec_state_commit(L, lane, st_regs);
                                }, fresh);
     if (valid) lc3_dec_state_store(c0, L, lane, gst);
+}
+// ---- frame inspection (lc3gpu_inspect; lc3_dev_dec_inspect.h) ---------------------------------------------------------------------------
+// One lane per frame over a flat list of slots, the run-time view only.  Dynamic LDS: the parser's lookup, spectral and TNS models, then
+// per frame its 128-byte record (lane-major), 14 words of lsb-mode flags (word-major) and its slot of bytes.  The records leave through
+// LDS: after a barrier the workgroup writes its frames' records as one contiguous run, 16 bytes per store.
+#define LC3_INSPECT_LDS_FIXED (4096 + 64 * LC3_DCF_ROW_WORDS * 4 + LC3_TNS_MODEL_WORDS * 4)
+static_assert(LC3_INSPECT_LDS_FIXED % 16 == 0, "the records are read back 16 bytes at a time");
+static __host__ __device__ inline size_t lc3_inspect_lds_per_frame(int slot) { return 4 * LC3_FI_WORDS + 4 * LC3_INSPECT_BITS_WORDS + (size_t)slot; }
+__global__ __launch_bounds__(256) void lc3_inspect_kernel(lc3_cfg_slot<lc3_cfg_any> cfg, const uint8_t *in, const uint16_t *nb, const uint8_t *bad,
+                                                          int slot, int n_frames, int32_t *info) {
+    LC3_LANE_KERNEL_BEGIN();
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const lc3_cfg &c0 = lc3_cfg_table[cfg.id];
+    const int ne = c0.ne, fs_ind = c0.fs_ind, n_ms_10 = c0.n_ms_10;
+    const int tid = threadIdx.x, fpb = blockDim.x;
+    uint8_t *s_lookup = smem;
+    uint32_t *s_cf = (uint32_t *)(smem + 4096);
+    uint32_t *s_tns = (uint32_t *)(smem + 4096 + 64 * LC3_DCF_ROW_WORDS * 4);
+    int32_t *s_rec = (int32_t *)(smem + LC3_INSPECT_LDS_FIXED);
+    uint32_t *s_bits = (uint32_t *)(smem + LC3_INSPECT_LDS_FIXED + 4 * LC3_FI_WORDS * fpb);
+    uint8_t *s_bytes = smem + LC3_INSPECT_LDS_FIXED + (4 * LC3_FI_WORDS + 4 * LC3_INSPECT_BITS_WORDS) * fpb;
+    const size_t f0 = (size_t)blockIdx.x * (size_t)fpb;
+    const size_t remaining = (size_t)n_frames - f0;
+    const int nfr = remaining < (size_t)fpb ? (int)remaining : fpb;
+    {
+        for (int i = tid; i < LC3_TNS_MODEL_WORDS; i += fpb) s_tns[i] = lc3_tns_model_word(i);
+        const uint32_t *lk32 = (const uint32_t *)LC3T_AC_SPEC_LOOKUP;
+        uint32_t *d32 = (uint32_t *)s_lookup;
+        for (int i = tid; i < 1024; i += fpb) d32[i] = lk32[i];
+        for (int i = tid; i < 64 * LC3_DCF_ROW_WORDS; i += fpb) s_cf[i] = lc3_dcf_word(i);
+        const int total = nfr * slot;
+        const uint8_t *src = in + f0 * (size_t)slot;
+        if ((((uintptr_t)src) & 3u) == 0) {
+            const uint32_t *s32 = (const uint32_t *)src;
+            uint32_t *b32 = (uint32_t *)s_bytes;
+            for (int i = tid; i < total / 4; i += fpb) b32[i] = s32[i];
+            for (int i = (total & ~3) + tid; i < total; i += fpb) s_bytes[i] = src[i];
+        } else {
+            for (int i = tid; i < total; i += fpb) s_bytes[i] = src[i];
+        }
+    }
+    __syncthreads();
+    if (tid < nfr) {
+        const size_t f = f0 + (size_t)tid;
+        lc3_parse_ctx c;
+        c.dbg = nullptr;
+        c.bytes = s_bytes + tid * slot;
+        c.lookup = s_lookup;
+        c.cf = s_cf;
+        c.tns = s_tns;
+        const int size = nb ? lc3_vbr_dec_size(nb, f, slot) : slot;
+        lc3_inspect_record(c, bad && bad[f], size, s_rec + tid * LC3_FI_WORDS, s_bits + tid, fpb, ne, fs_ind, n_ms_10);
+    }
+    __syncthreads();
+    int32_t *dst = info + f0 * (size_t)LC3_FI_WORDS;
+    if ((((uintptr_t)dst) & 15u) == 0) {
+        for (int i = tid; i < nfr * (LC3_FI_WORDS / 4); i += fpb) ((lc3_i4 *)dst)[i] = ((const lc3_i4 *)s_rec)[i];
+    } else {
+        for (int i = tid; i < nfr * LC3_FI_WORDS; i += fpb) dst[i] = s_rec[i];
+    }
 }
 #endif
 
@@ -3542,6 +3603,26 @@ int lc3gpu_decode_vbr(lc3gpu_decoder *d, const uint8_t *d_in, const uint16_t *d_
     }
     if (fresh) d->fresh_pending = false;
     return d->order_end(stream);
+}
+
+int lc3gpu_inspect(int frame_us, int fs_hz, const uint8_t *d_in, const uint16_t *d_nbytes, const uint8_t *d_bad, int slot_bytes, int n_frames,
+                   lc3gpu_frame_info *d_info, void *stream) {
+    if (!d_in || !d_info || n_frames < 0) return LC3GPU_EINVAL;
+    if (slot_bytes < 1 || slot_bytes > LC3_MAX_NE) return LC3GPU_ELENGTH;
+    lc3_cfg c;
+    int rc = make_config(c, frame_us, fs_hz);
+    if (rc) return rc;
+    if (n_frames == 0) return LC3GPU_OK;
+    if (lc3gpu_device_count() <= 0) return LC3GPU_ENODEVICE;
+    HostCfg h;
+    rc = cfg_acquire(h, frame_us, fs_hz);  // the configuration slot and the tables, as handle creation registers them
+    if (rc) return rc;
+    const unsigned fpb = lc3_frame_block_fit(LC3_INSPECT_LDS_FIXED, lc3_inspect_lds_per_frame(slot_bytes));
+    const size_t lds = LC3_INSPECT_LDS_FIXED + (size_t)fpb * lc3_inspect_lds_per_frame(slot_bytes);
+    hipLaunchKernelGGL(lc3_inspect_kernel, dim3((unsigned)(((size_t)n_frames + fpb - 1) / fpb)), dim3(fpb), lds, (hipStream_t)stream,
+                       lc3_cfg_slot<lc3_cfg_any>{h.slot}, d_in, d_nbytes, d_bad, slot_bytes, n_frames, (int32_t *)d_info);
+    HIP_TRY(hipGetLastError());
+    return LC3GPU_OK;
 }
 
 int lc3gpu_decode_range(lc3gpu_decoder *d, int first_channel, int n_channels, const uint8_t *d_in, const uint8_t *d_bad,

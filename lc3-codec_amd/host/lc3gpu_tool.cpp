@@ -6,6 +6,7 @@
 //   lc3gpu-tool frame-timing [fs_hz=48000] [frame_us=10000] [bytes=150] [repeats=200]
 //   lc3gpu-tool buffer-lengths <channels 1|2> <fs_hz> <frame_us>
 //   lc3gpu-tool throughput [channels=16384] [frames_per_submit=4] [submits=200] [bytes=150]
+//   lc3gpu-tool inspect <in.lc3> <fs_hz> <frame_us> <bytes_per_channel> [channels=1]
 // The positional arguments are the reference drivers' function parameters (examples/encode.rs:36-44,
 // examples/decode.rs:36-44); the sampling frequency is NOT taken from the WAV header there either.
 #include <cstdio>
@@ -153,6 +154,78 @@ static int frame_timing(int fs_hz, int frame_us, int nbytes, int repeats) {
     }
 }
 
+// The reference's examples/read_sideinfo.rs over the headerless .lc3 framing of `decode` (frames in time order, the channels of a frame one
+// after the other, bytes_per_channel each): every whole frame through lc3gpu_inspect, one JSON object per line with its channel, frame
+// index, status name and every field of its record.
+static const char *frame_status_name(int s) {
+    static const char *side[] = {"BufferReaderError", "BandwidthIdxOutOfRange", "LastNonZeroTupleGreaterThanYLen", "PlcTriggerSns1OutOfRange",
+                                 "PlcTriggerSns2OutOfRange"};
+    static const char *arith[] = {"ArithmeticCodec", "TnsOrder", "TnsCoef", "SpectralData", "SpectralBoolData", "NegativeResidualNumBits",
+                                  "ResidualBoolData", "ResidualBoolDataOverflow"};
+    static char buf[64];
+    if (s == LC3GPU_FRAME_OK) return "Ok";
+    if (s == LC3GPU_FRAME_FLAGGED) return "Flagged";
+    if (s == LC3GPU_FRAME_EMPTY) return "Empty";
+    if (s > LC3GPU_FRAME_SIDE_INFO && s <= LC3GPU_FRAME_SIDE_INFO + 5) {
+        std::snprintf(buf, sizeof(buf), "SideInfo::%s", side[s - LC3GPU_FRAME_SIDE_INFO - 1]);
+        return buf;
+    }
+    if (s > LC3GPU_FRAME_ARITH && s <= LC3GPU_FRAME_ARITH + 8) {
+        std::snprintf(buf, sizeof(buf), "ArithmeticDecode::%s", arith[s - LC3GPU_FRAME_ARITH - 1]);
+        return buf;
+    }
+    std::snprintf(buf, sizeof(buf), "Unknown(%d)", s);
+    return buf;
+}
+
+static int inspect_file(const char *path, int fs_hz, int frame_us, int nbytes, int channels) {
+    if (nbytes < 1 || nbytes > 400 || channels < 1) { std::fprintf(stderr, "bytes_per_channel 1 ... 400, channels >= 1\n"); return 2; }
+    FILE *f = std::fopen(path, "rb");
+    if (!f) { std::fprintf(stderr, "cannot open %s\n", path); return 3; }
+    std::vector<uint8_t> in;
+    uint8_t chunk[65536];
+    for (size_t n; (n = std::fread(chunk, 1, sizeof(chunk), f)) > 0;) in.insert(in.end(), chunk, chunk + n);
+    std::fclose(f);
+    const size_t n_frames = in.size() / (size_t)nbytes;  // every whole frame (a trailing partial one is not a frame)
+    std::vector<lc3gpu_frame_info> info(n_frames);
+    uint8_t *d_in = nullptr;
+    lc3gpu_frame_info *d_info = nullptr;
+    int rc = 0;
+    try {
+        if (n_frames > 0) {
+            if (hipMalloc((void **)&d_in, in.size()) != hipSuccess || hipMalloc((void **)&d_info, n_frames * sizeof(lc3gpu_frame_info)) != hipSuccess ||
+                hipMemcpy(d_in, in.data(), n_frames * (size_t)nbytes, hipMemcpyHostToDevice) != hipSuccess)
+                throw lc3gpu::Error(LC3GPU_EHIP, "device buffers");
+            lc3gpu::inspect((lc3gpu::FrameDuration)frame_us, (lc3gpu::SamplingFrequency)fs_hz, d_in, d_info, nbytes, (int)n_frames);
+            if (hipMemcpy(info.data(), d_info, n_frames * sizeof(lc3gpu_frame_info), hipMemcpyDeviceToHost) != hipSuccess)
+                throw lc3gpu::Error(LC3GPU_EHIP, "read back");
+        }
+    } catch (const lc3gpu::Error &e) {
+        std::fprintf(stderr, "inspect failed: %s\n", e.what());
+        rc = 1;
+    }
+    (void)hipFree(d_in);
+    (void)hipFree(d_info);
+    if (rc) return rc;
+    for (size_t i = 0; i < n_frames; i++) {
+        const lc3gpu_frame_info &r = info[i];
+        std::printf("{\"channel\": %zu, \"frame\": %zu, \"status\": \"%s\", \"nbytes\": %d, \"bandwidth\": %d, \"lastnz\": %d, \"lsb_mode\": %d, "
+                    "\"global_gain_index\": %d, \"num_tns_filters\": %d, \"rc_order_ari_input\": [%d, %d], \"sns_ind_lf\": %d, \"sns_ind_hf\": %d, "
+                    "\"sns_ls_inda\": %d, \"sns_ls_indb\": %d, \"sns_idx_a\": %u, \"sns_idx_b\": %u, \"sns_submode_lsb\": %d, "
+                    "\"sns_submode_msb\": %d, \"sns_g_ind\": %d, \"pitch_present\": %d, \"ltpf_active\": %d, \"pitch_index\": %d, "
+                    "\"noise_factor\": %d, \"rc_order\": [%d, %d], \"n_residual_bits\": %d, \"noise_filling_seed\": %d, \"is_zero_frame\": %d, "
+                    "\"rc_i\": [",
+                    i % (size_t)channels, i / (size_t)channels, frame_status_name(r.status), r.nbytes, r.bandwidth, r.lastnz, r.lsb_mode,
+                    r.global_gain_index, r.num_tns_filters, r.rc_order_ari_input[0], r.rc_order_ari_input[1], r.sns_ind_lf, r.sns_ind_hf,
+                    r.sns_ls_inda, r.sns_ls_indb, r.sns_idx_a, r.sns_idx_b, r.sns_submode_lsb, r.sns_submode_msb, r.sns_g_ind, r.pitch_present,
+                    r.ltpf_active, r.pitch_index, r.noise_factor, r.rc_order[0], r.rc_order[1], r.n_residual_bits, r.noise_filling_seed,
+                    r.is_zero_frame);
+        for (int k = 0; k < 16; k++) std::printf(k ? ", %d" : "%d", r.rc_i[k]);
+        std::printf("], \"reserved\": %d}\n", r.reserved);
+    }
+    return 0;
+}
+
 static int usage() {
     std::fprintf(stderr,
                  "usage: lc3gpu-tool encode <in.wav> <out.lc3> <fs_hz> <channels> <frame_us> <bytes_per_channel> [--frames-per-launch N]\n"
@@ -161,7 +234,8 @@ static int usage() {
                  "       lc3gpu-tool wavinfo <file.wav>\n"
                  "       lc3gpu-tool frame-timing [fs_hz] [frame_us] [bytes] [repeats]\n"
                  "       lc3gpu-tool buffer-lengths <channels 1|2> <fs_hz> <frame_us>\n"
-                 "       lc3gpu-tool throughput [channels] [frames_per_submit] [submits] [bytes]\n");
+                 "       lc3gpu-tool throughput [channels] [frames_per_submit] [submits] [bytes]\n"
+                 "       lc3gpu-tool inspect <in.lc3> <fs_hz> <frame_us> <bytes_per_channel> [channels]\n");
     return 2;
 }
 
@@ -185,6 +259,10 @@ int main(int argc, char **argv) {
     if (cmd == "frame-timing")
         return frame_timing(argc > 2 ? std::atoi(argv[2]) : 48000, argc > 3 ? std::atoi(argv[3]) : 10000,
                             argc > 4 ? std::atoi(argv[4]) : 150, argc > 5 ? std::max(1, std::atoi(argv[5])) : 200);
+    if (cmd == "inspect") {
+        if (argc < 6) return usage();
+        return inspect_file(argv[2], std::atoi(argv[3]), std::atoi(argv[4]), std::atoi(argv[5]), argc > 6 ? std::atoi(argv[6]) : 1);
+    }
     if (cmd == "buffer-lengths") {  // calc_working_buffer_lengths of the static-channel API shape; no device needed
         if (argc < 5) return usage();
         const int ch = std::atoi(argv[2]);

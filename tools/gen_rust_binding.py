@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "lc3gpu.h")
 
 OPAQUE = {"lc3gpu_encoder": "Lc3GpuEncoder", "lc3gpu_decoder": "Lc3GpuDecoder", "lc3gpu_pipeline": "Lc3GpuPipeline",
-          "lc3gpu_stream_desc": "Lc3GpuStreamDesc"}
+          "lc3gpu_stream_desc": "Lc3GpuStreamDesc", "lc3gpu_frame_info": "Lc3GpuFrameInfo"}
 SCALAR = {"int": "i32", "unsigned": "u32", "unsigned int": "u32", "float": "f32", "double": "f64", "size_t": "usize",
           "int16_t": "i16", "uint16_t": "u16", "uint8_t": "u8", "int32_t": "i32", "uint32_t": "u32", "int64_t": "i64", "uint64_t": "u64",
           "unsigned long long": "u64", "char": "c_char", "void": "c_void"}
@@ -82,6 +82,23 @@ def constants():
     for m in re.finditer(r"^#define\s+(LC3GPU_\w+)\s+(-?\d+)\s*$", text, flags=re.M):
         if m.group(1) != "LC3GPU_H_":
             out.append((m.group(1), int(m.group(2))))
+    return out
+
+
+def frame_info_fields():
+    """(name, rust type) of every field of lc3gpu_frame_info, in the header's order"""
+    text = strip_comments(open(HEADER).read())
+    body = re.search(r"typedef struct lc3gpu_frame_info \{(.*?)\} lc3gpu_frame_info;", text, flags=re.S).group(1)
+    out = []
+    for decl in body.split(";"):
+        decl = " ".join(decl.split())
+        if not decl:
+            continue
+        ctype, names = decl.split(" ", 1)
+        for name in names.split(","):
+            m = re.match(r"^\s*(\w+)\s*(?:\[(\d+)\])?\s*$", name)
+            t = SCALAR[ctype]
+            out.append((m.group(1), "[%s; %s]" % (t, m.group(2)) if m.group(2) else t))
     return out
 
 
@@ -235,6 +252,17 @@ impl Drop for Lc3DecoderGpu {
     }
 }
 
+/// lc3gpu_inspect (include/lc3gpu.h): the side information and decode status of `n_frames` frames, no handle needed.  A status of
+/// LC3GPU_FRAME_SIDE_INFO + k is `Lc3DecoderError::SideInfo`, LC3GPU_FRAME_ARITH + k `Lc3DecoderError::ArithmeticDecode` (INTEGRATION.md).
+///
+/// # Safety
+/// device allocations: `d_in` of n_frames * slot_bytes bytes, `d_info` of n_frames records, `d_nbytes` / `d_bad_frame` of n_frames
+/// entries or null; they must stay valid until the work on `hip_stream` is done.
+pub unsafe fn inspect_device(d: FrameDuration, f: SamplingFrequency, d_in: *const u8, d_nbytes: *const u16, d_bad_frame: *const u8, slot_bytes: usize,
+                             n_frames: usize, d_info: *mut Lc3GpuFrameInfo, hip_stream: *mut c_void) -> i32 {
+    lc3gpu_inspect(frame_us(d), fs_hz(f), d_in, d_nbytes, d_bad_frame, slot_bytes as i32, n_frames as i32, d_info, hip_stream)
+}
+
 /// Encode + decode of many channels in the arrangement that measured fastest (include/lc3gpu.h, "pipeline"): device buffers, asynchronous.
 pub struct Lc3PipelineGpu {
     h: *mut Lc3GpuPipeline,
@@ -278,11 +306,16 @@ def generate():
         "",
     ]
     for c, r in sorted(OPAQUE.items()):
-        if c == "lc3gpu_stream_desc":
+        if c in ("lc3gpu_stream_desc", "lc3gpu_frame_info"):
             continue
         lines += ["#[repr(C)]", "pub struct %s {" % r, "    _private: [u8; 0],", "}"]
     lines += ["/// one stream of a mixed-configuration handle (lc3gpu_stream_desc)", "#[repr(C)]", "#[derive(Clone, Copy, Debug)]",
-              "pub struct Lc3GpuStreamDesc {", "    pub fs_hz: i32,", "    pub frame_us: i32,", "    pub nbytes: i32,", "}", ""]
+              "pub struct Lc3GpuStreamDesc {", "    pub fs_hz: i32,", "    pub frame_us: i32,", "    pub nbytes: i32,", "}"]
+    lines += ["/// one frame's record of lc3gpu_inspect (lc3gpu_frame_info, 128 bytes): status LC3GPU_FRAME_*, the side information",
+              "/// (decoder/side_info.rs:20-31) and the arithmetic data (decoder/arithmetic_codec.rs:99-107)", "#[repr(C)]",
+              "#[derive(Clone, Copy, Debug, Default)]", "pub struct Lc3GpuFrameInfo {"]
+    lines += ["    pub %s: %s," % f for f in frame_info_fields()]
+    lines += ["}", "const _: () = assert!(core::mem::size_of::<Lc3GpuFrameInfo>() == 128);", ""]
     for name, val in constants():
         lines.append("pub const %s: i32 = %d;" % (name, val))
     lines += ["", "#[link(name = \"lc3gpu\")]", "extern \"C\" {"]
