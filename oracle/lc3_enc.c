@@ -410,13 +410,11 @@ void lc3o_enc_sns_quant_spec(const float *scf, float *scfq, lc3o_sns_result *res
     }
 }
 
-/* SpectralNoiseShaping::run :203-282 */
-lc3o_sns_result lc3o_enc_sns(const lc3o_config *c, float *x, const float *e_b, int attack) {
+/* SpectralNoiseShaping::run :203-240 -- the 16 unquantised scale factors */
+void lc3o_enc_sns_scf(const lc3o_config *c, const float *e_b, int attack, float *scf) {
     static const int G_TILT[5] = {14, 18, 22, 26, 30};
     float W[6];
-    float padded[64], eb[64], ds[16], scf[16], scfq[16], interp[64];
-    const uint16_t *ifs = band_index(c);
-    lc3o_sns_result res;
+    float padded[64], eb[64], ds[16];
     int b, k, n, diff = 64 - c->nb;
     float exponent, total, noise_floor, avg;
 
@@ -483,8 +481,17 @@ lc3o_sns_result lc3o_enc_sns(const lc3o_config *c, float *x, const float *e_b, i
         att = c->n_ms_10 ? 0.5f : 0.3f;
         for (n = 0; n < 16; n++) scf[n] = att * (scf[n] - avg);
     } else {
-        memcpy(scf, ds, sizeof(scf));
+        memcpy(scf, ds, sizeof(ds));
     }
+}
+
+/* SpectralNoiseShaping::run :203-282 */
+lc3o_sns_result lc3o_enc_sns(const lc3o_config *c, float *x, const float *e_b, int attack) {
+    float scf[16], scfq[16], interp[64];
+    const uint16_t *ifs = band_index(c);
+    lc3o_sns_result res;
+    int b, k, n, diff = 64 - c->nb;
+    lc3o_enc_sns_scf(c, e_b, attack, scf);
     lc3o_enc_sns_quant_spec(scf, scfq, &res, c->spec_flags);
     /* apply_scale_factor_interpolation :163-183 */
     interp[0] = scfq[0];

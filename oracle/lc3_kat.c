@@ -212,3 +212,117 @@ void lc3o_kat_math(int which, const float *x, int n, float *out) {
         }
     }
 }
+
+/* ---------------------------------------------------------------- whole-frame stage dumps (tests/test_ref64_oracle.py)
+ * Each runs one frame exactly as lc3o_encode_frame / lc3o_decode_frame do and also returns every float stage's output, in the
+ * layout of the device's own dumps (lc3gpu_encode_frame_debug / lc3gpu_decode_frame_debug, include/lc3gpu.h), so that one
+ * checker serves the oracle and the device. */
+void *lc3o_encoder_new_spec(int fs_hz, int frame_us, int spec_flags) {
+    lc3o_encoder *e = (lc3o_encoder *)malloc(sizeof(*e));
+    if (e && lc3o_encoder_init_spec(e, fs_hz, frame_us, spec_flags)) { free(e); return 0; }
+    return e;
+}
+/* dbg float[1600]: MDCT [0,nf), after SNS [480,..), after TNS [960,..); scalars at 1440: +0 bandwidth index, +1 attack flag,
+ * +6 / +7 TNS orders, +21 near-Nyquist flag; band energies at 1472.  scf[16]: the unquantised scale factors; rc_q[16] */
+void lc3o_kat_encode_stages(void *enc, const int16_t *x_s, uint8_t *out, int nbytes, float *dbg, float *scf, float *rc_q) {
+    lc3o_encoder *e = (lc3o_encoder *)enc;
+    const lc3o_config *c = &e->cfg;
+    int nbits = nbytes * 8, near_nyquist, attack, n_res, noise_factor, k;
+    lc3o_bw_result bw;
+    lc3o_sns_result sns;
+    lc3o_tns_result tns;
+    lc3o_ltpf_result pf;
+    lc3o_quant_result spec;
+    for (k = 0; k < 1600; k++) dbg[k] = 0.0f;
+    e->frame_index += 1;
+    near_nyquist = lc3o_enc_mdct_run(e, x_s, e->mdct_out, e->energy_bands);
+    memcpy(dbg, e->mdct_out, sizeof(float) * (size_t)c->nf);
+    memcpy(dbg + 1472, e->energy_bands, sizeof(float) * (size_t)c->nb);
+    bw = lc3o_enc_bandwidth(c, e->energy_bands);
+    attack = lc3o_enc_attack(c, &e->att, x_s, nbytes);
+    lc3o_enc_sns_scf(c, e->energy_bands, attack, scf);
+    sns = lc3o_enc_sns(c, e->mdct_out, e->energy_bands, attack);
+    memcpy(dbg + 480, e->mdct_out, sizeof(float) * (size_t)c->nf);
+    tns = lc3o_enc_tns(c, e->mdct_out, bw.bandwidth_ind, nbits, near_nyquist);
+    memcpy(dbg + 960, e->mdct_out, sizeof(float) * (size_t)c->nf);
+    memcpy(rc_q, tns.rc_q, sizeof(float) * 16);
+    dbg[1440] = (float)bw.bandwidth_ind; dbg[1441] = (float)attack;
+    dbg[1446] = (float)tns.rc_order[0]; dbg[1447] = (float)tns.rc_order[1]; dbg[1461] = (float)near_nyquist;
+    pf = lc3o_enc_ltpf(c, &e->ltpf, x_s, near_nyquist, nbits);
+    spec = lc3o_enc_quant(c, &e->quant, e->mdct_out, e->x_q, nbits, bw.nbits_bandwidth, tns.nbits_tns, pf.nbits_ltpf);
+    n_res = lc3o_enc_residual(spec.nbits_spec, spec.nbits_trunc, c->ne, spec.gg, e->mdct_out, e->x_q, e->res_bits);
+    noise_factor = lc3o_enc_noise_factor(c, e->mdct_out, e->x_q, bw.bandwidth_ind, spec.gg);
+    lc3o_enc_bitstream(c, bw, &sns, &tns, pf, &spec, e->res_bits, n_res, noise_factor, e->x_q, out, nbytes);
+}
+/* dbg float[2560] in the LC3GPU_DBG_* layout (INT 0, SPEC 400, IMDCT 800, LTPF 1280, GAIN 1760, TNS 2160); si[20] as
+ * lc3o_kat_side_info, iad[22] as lc3o_kat_arith, res_bits[480].  Returns 1 when the frame was concealed (nothing but IMDCT / LTPF
+ * is then meaningful). */
+int lc3o_kat_decode_stages(void *dec, const uint8_t *in, int nbytes, int16_t *pcm_out, float *dbg, int64_t si_flat[20], int iad[22],
+                           uint8_t *res_bits) {
+    lc3o_decoder *d = (lc3o_decoder *)dec;
+    const lc3o_config *c = &d->cfg;
+    int nbits = nbytes * 8, k, ok;
+    int32_t x[LC3O_MAX_NE];
+    lc3o_reader rd = {0, 0};
+    lc3o_side_info si;
+    lc3o_arith_data ad;
+    lc3o_ltpf_info info;
+    for (k = 0; k < 2560; k++) dbg[k] = 0.0f;
+    memset(x, 0, sizeof(x));
+    memset(&si, 0, sizeof(si));
+    memset(&ad, 0, sizeof(ad));
+    d->frame_index += 1;
+    ok = lc3o_dec_side_info(in, nbytes, &rd, c->fs_ind, c->ne, &si) == 0;
+    if (ok) ok = lc3o_dec_arith(in, nbytes, &rd, c->fs_ind, c->ne, &si, c->n_ms_10, x, &ad) == 0;
+    if (ok) {
+        for (k = 0; k < c->ne; k++) d->spec_lines[k] = (float)x[k];
+        for (k = 0; k < c->ne; k++) dbg[k] = (float)x[k];
+        lc3o_dec_residual(si.lsb_mode, ad.residual_bits, ad.n_residual_bits, d->spec_lines, c->ne);
+        lc3o_dec_noise_filling(ad.is_zero_frame, ad.noise_filling_seed, si.bandwidth, c->n_ms_10, si.noise_factor, x,
+                               d->spec_lines, c->ne);
+        lc3o_dec_global_gain(ad.frame_num_bits, c->fs_ind, si.global_gain_index, d->spec_lines, c->ne);
+        memcpy(dbg + 1760, d->spec_lines, sizeof(float) * (size_t)c->ne);
+        lc3o_dec_tns(c->n_ms_10, si.bandwidth, si.num_tns_filters, ad.rc_order, ad.rc_i, d->spec_lines);
+        memcpy(dbg + 2160, d->spec_lines, sizeof(float) * (size_t)c->ne);
+        lc3o_dec_sns(c, &si.sns_vq, d->spec_lines);
+        memcpy(dbg + 400, d->spec_lines, sizeof(float) * (size_t)c->ne);
+        lc3o_dec_plc_save(d, d->spec_lines);
+        info = si.ltpf;
+        d->last_frame_was_plc = 0;
+    } else {
+        info = lc3o_dec_plc_load(d, d->spec_lines);
+        d->last_frame_was_plc = 1;
+        memcpy(dbg + 400, d->spec_lines, sizeof(float) * (size_t)c->ne);
+    }
+    lc3o_dec_imdct(d, d->spec_lines, d->freq_samples);
+    memcpy(dbg + 800, d->freq_samples, sizeof(float) * (size_t)c->nf);
+    lc3o_dec_ltpf(c, &d->ltpf, &info, nbits, d->freq_samples);
+    memcpy(dbg + 1280, d->freq_samples, sizeof(float) * (size_t)c->nf);
+    lc3o_dec_output(d->freq_samples, pcm_out, c->nf);
+    si_out(&si, si_flat);
+    iad[0] = ad.rc_order[0]; iad[1] = ad.rc_order[1];
+    for (k = 0; k < 16; k++) iad[2 + k] = ad.rc_i[k];
+    iad[18] = ad.n_residual_bits; iad[19] = ad.noise_filling_seed; iad[20] = ad.is_zero_frame; iad[21] = ad.frame_num_bits;
+    memcpy(res_bits, ad.residual_bits, 480);
+    return !ok;
+}
+/* the quantised integer vector y of the SNS VQ (decoder/spectral_noise_shaping.rs:21-63): integer input of ref64's scfq */
+void lc3o_kat_sns_y(const int64_t si_flat[20], int32_t y[16]) {
+    lc3o_side_info si;
+    int32_t z[16];
+    int shape_j, n;
+    si_in(&si, si_flat);
+    shape_j = (si.sns_vq.submode_msb << 1) + si.sns_vq.submode_lsb;
+    memset(z, 0, sizeof(z));
+    for (n = 0; n < 16; n++) y[n] = 0;
+    switch (shape_j) {
+    case 0:
+        lc3o_mpvq_deenum(10, 10, si.sns_vq.ls_inda, si.sns_vq.idx_a, y);
+        lc3o_mpvq_deenum(6, 1, si.sns_vq.ls_indb, si.sns_vq.idx_b, z);
+        for (n = 0; n < 6; n++) y[10 + n] = z[n];
+        break;
+    case 1: lc3o_mpvq_deenum(10, 10, si.sns_vq.ls_inda, si.sns_vq.idx_a, y); break;
+    case 2: lc3o_mpvq_deenum(16, 8, si.sns_vq.ls_inda, si.sns_vq.idx_a, y); break;
+    default: lc3o_mpvq_deenum(16, 6, si.sns_vq.ls_inda, si.sns_vq.idx_a, y); break;
+    }
+}

@@ -119,6 +119,7 @@ int lc3o_enc_mdct_run(lc3o_encoder *e, const int16_t *x_s, float *out, float *en
 lc3o_bw_result lc3o_enc_bandwidth(const lc3o_config *c, const float *e_b);
 int lc3o_enc_attack(const lc3o_config *c, lc3o_attack_state *st, const int16_t *x_s, int nbytes);
 lc3o_sns_result lc3o_enc_sns(const lc3o_config *c, float *x, const float *e_b, int attack);
+void lc3o_enc_sns_scf(const lc3o_config *c, const float *e_b, int attack, float *scf);
 void lc3o_enc_sns_quant(const float *scf, float *scfq, lc3o_sns_result *r);
 void lc3o_enc_sns_quant_spec(const float *scf, float *scfq, lc3o_sns_result *r, int spec_flags);
 lc3o_tns_result lc3o_enc_tns(const lc3o_config *c, float *x, int p_bw, int nbits, int near_nyquist);
