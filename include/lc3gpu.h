@@ -6,7 +6,8 @@
  * A handle owns N independent codec channels ("streams") on one HIP device; each stream is one
  * reference EncoderChannel / DecoderChannel with its own carried state.  The batch calls process
  * `n_streams x n_frames` frames per launch: one CDNA4 wavefront per stream, frames of a stream in
- * time order.  The *_frame calls are the n_streams = 1, n_frames = 1 case with host buffers and
+ * time order -- all channels, a contiguous range, or a list of channels in any order (lc3gpu_*_list, with
+ * per-channel resets and state blobs: lc3gpu_*_reset_channels, lc3gpu_*_state_{save,load}_channels).  The *_frame calls are the n_streams = 1, n_frames = 1 case with host buffers and
  * have the reference's argument meaning (slice lengths select the frame size / bitrate).
  *
  * Plain C types only (pointers + sizes); no torch / C++ types cross this boundary.
@@ -114,6 +115,28 @@ int lc3gpu_encode(lc3gpu_encoder *enc, const int16_t *d_pcm, uint8_t *d_out, int
 /* same, restricted to channels [first_channel, first_channel + n_channels); buffers hold only those channels */
 int lc3gpu_encode_range(lc3gpu_encoder *enc, int first_channel, int n_channels, const int16_t *d_pcm,
                         uint8_t *d_out, int nbytes, int n_frames, void *hip_stream);
+/* Batch over a LIST of the handle's channels: the reference's caller decides per call which channel gets a frame (examples/encode.rs:97-115,
+ * one encode_frame per channel it chooses), so a tick of a many-stream server -- only some streams have a frame, in any order -- is ONE call.
+ *   channels  HOST int32[n_list]: entry i names the channel whose frames are item i of the buffers; any order, no channel twice.  The array
+ *             may be reused as soon as the call returns (the handle copies it to pinned memory of its own and from there to the device in
+ *             stream order: no host synchronisation)
+ *   d_pcm     DEVICE int16[n_list][n_frames][nf] (4-byte aligned), d_out DEVICE uint8[n_list][n_frames][nbytes]: planar, compact in list order
+ * Checked on the host before anything is queued: an index outside [0, num_channels) or a channel named twice: LC3GPU_ECHANNEL; null pointers,
+ * a negative n_list, misaligned PCM, a mixed handle: LC3GPU_EINVAL; nbytes / n_frames as lc3gpu_encode (LC3GPU_ELENGTH).  A call that returns
+ * an error has launched nothing and changed no channel; n_list = 0 launches nothing and returns LC3GPU_OK.  A bound handle takes the call on its
+ * bound stream only; LC3GPU_EPAIR as for the other batch calls.  Every listed channel advances by n_frames frames exactly as under
+ * lc3gpu_encode; every channel not listed is left byte for byte as it was.  List, uniform, range, sized and *_frame calls may alternate on
+ * a handle; a list 0 .. num_channels-1 gives the bytes of lc3gpu_encode, a contiguous ascending run those of lc3gpu_encode_range.  Channels
+ * reset by lc3gpu_encoder_reset_channels start from the constructed state inside the same launch as the carried ones.  Asynchronous on
+ * hip_stream, ordered after the handle's earlier work.
+ * NOT provided (out of scope): lists on mixed handles, with the interleaved layout, with a frame size per frame (lc3gpu_*_vbr), on the
+ * host-resident calls (lc3gpu_*_host) and in the pipeline object. */
+int lc3gpu_encode_list(lc3gpu_encoder *enc, const int32_t *channels, int n_list, const int16_t *d_pcm, uint8_t *d_out, int nbytes,
+                       int n_frames, void *hip_stream);
+/* The named channels (HOST int32[n]) are back in the freshly constructed state from their next call on -- the reference builds a new
+ * EncoderChannel; channels not named are untouched.  Like lc3gpu_encoder_reset it waits for nothing and launches nothing.  LC3GPU_ECHANNEL
+ * for an index out of range, LC3GPU_EINVAL for null / negative; a channel named twice is harmless. */
+int lc3gpu_encoder_reset_channels(lc3gpu_encoder *enc, const int32_t *channels, int n);
 /* same as lc3gpu_encode with the buffers in `layout` (LC3GPU_LAYOUT_*); interleaved PCM needs 2-byte alignment only */
 int lc3gpu_encode_layout(lc3gpu_encoder *enc, int layout, const int16_t *d_pcm, uint8_t *d_out, int nbytes, int n_frames,
                          void *hip_stream);
@@ -155,6 +178,12 @@ int lc3gpu_encode_mixed(lc3gpu_encoder *enc, const int16_t *d_pcm, uint8_t *d_ou
 size_t lc3gpu_encoder_state_size(const lc3gpu_encoder *enc);
 int lc3gpu_encoder_state_save(lc3gpu_encoder *enc, void *host_dst, size_t nbytes);
 int lc3gpu_encoder_state_load(lc3gpu_encoder *enc, const void *host_src, size_t nbytes);
+/* the same for the channels named in a HOST list: blob i (state_size bytes, the format above) belongs to channels[i]; nbytes must be
+ * n * state_size (LC3GPU_ELENGTH).  A slice of a whole-handle save loads through here and the other way round: a stream moves to another
+ * handle.  The header check applies per blob, before any channel is written.  LC3GPU_ECHANNEL for an index out of range; they synchronise
+ * the device as the whole-handle calls do. */
+int lc3gpu_encoder_state_save_channels(lc3gpu_encoder *enc, const int32_t *channels, int n, void *host_dst, size_t nbytes);
+int lc3gpu_encoder_state_load_channels(lc3gpu_encoder *enc, const int32_t *channels, int n, const void *host_src, size_t nbytes);
 
 /* ---- decoder ------------------------------------------------------------------------------------ */
 /* Lc3Decoder::new (lc3_decoder.rs:181-215) */
@@ -175,6 +204,13 @@ int lc3gpu_decode(lc3gpu_decoder *dec, const uint8_t *d_in, const uint8_t *d_bad
                   int n_frames, void *hip_stream);
 int lc3gpu_decode_range(lc3gpu_decoder *dec, int first_channel, int n_channels, const uint8_t *d_in,
                         const uint8_t *d_bad_frame, int16_t *d_pcm, int nbytes, int n_frames, void *hip_stream);
+/* Batch decode over a LIST of channels: the contract of lc3gpu_encode_list (which see: host list, compact planar device buffers, host-side
+ * checks, out-of-scope list) with d_in uint8[n_list][n_frames][nbytes], d_bad_frame uint8[n_list][n_frames] or NULL, d_pcm
+ * int16[n_list][n_frames][nf]; nbytes / n_frames as lc3gpu_decode.  Channels not listed keep their state and their PLC count. */
+int lc3gpu_decode_list(lc3gpu_decoder *dec, const int32_t *channels, int n_list, const uint8_t *d_in, const uint8_t *d_bad_frame,
+                       int16_t *d_pcm, int nbytes, int n_frames, void *hip_stream);
+/* as lc3gpu_encoder_reset_channels (the reference builds a new DecoderChannel); the channels' PLC counts go to zero with their reset */
+int lc3gpu_decoder_reset_channels(lc3gpu_decoder *dec, const int32_t *channels, int n);
 /* Batch decode with a frame size per frame: d_nbytes[c][t] is what the reference's buf_in.len() is for frame t of channel c
  * (lc3_decoder.rs:85).  DEVICE pointers, planar, every channel of the handle:
  *   d_in      uint8[num_channels][n_frames][slot_bytes]  frame (c, t) is the first d_nbytes[c][t] bytes of its slot
@@ -245,6 +281,8 @@ int lc3gpu_decode_mixed(lc3gpu_decoder *dec, const uint8_t *d_in, const uint8_t 
 size_t lc3gpu_decoder_state_size(const lc3gpu_decoder *dec);
 int lc3gpu_decoder_state_save(lc3gpu_decoder *dec, void *host_dst, size_t nbytes);
 int lc3gpu_decoder_state_load(lc3gpu_decoder *dec, const void *host_src, size_t nbytes);
+int lc3gpu_decoder_state_save_channels(lc3gpu_decoder *dec, const int32_t *channels, int n, void *host_dst, size_t nbytes);
+int lc3gpu_decoder_state_load_channels(lc3gpu_decoder *dec, const int32_t *channels, int n, const void *host_src, size_t nbytes);
 /* total number of frames concealed so far over all channels (synchronises the device) */
 int lc3gpu_decoder_plc_events(lc3gpu_decoder *dec, uint64_t *out);
 /* Full batches run the bit packer and the bitstream parser as producer / consumer pairs of wavefronts.  A half that waits 2^24 polls for

@@ -68,6 +68,31 @@ public:
         int rc = lc3gpu_encode_vbr(h_, d_pcm, d_out, d_nbytes, slot_bytes, n_frames, hip_stream);
         if (rc) throw Error(rc, "encode_vbr");
     }
+    // a list of channels (HOST indices, any order, none twice): DEVICE buffers compact in list order; the other channels are left as they were
+    void encode_list(const std::vector<int32_t> &channels, const int16_t *d_pcm, uint8_t *d_out, int nbytes, int n_frames, void *hip_stream = nullptr) {
+        int rc = lc3gpu_encode_list(h_, channels.data(), (int)channels.size(), d_pcm, d_out, nbytes, n_frames, hip_stream);
+        if (rc) throw Error(rc, "encode_list");
+    }
+    // back to the freshly constructed state from the next call on: every channel, or the named ones (a new EncoderChannel); no wait
+    void reset() {
+        int rc = lc3gpu_encoder_reset(h_);
+        if (rc) throw Error(rc, "reset");
+    }
+    void reset(const std::vector<int32_t> &channels) {
+        int rc = lc3gpu_encoder_reset_channels(h_, channels.data(), (int)channels.size());
+        if (rc) throw Error(rc, "reset");
+    }
+    // state blobs of the named channels (blob i belongs to channels[i]; the format of lc3gpu_encoder_state_save)
+    std::vector<uint8_t> state_save(const std::vector<int32_t> &channels) {
+        std::vector<uint8_t> buf(lc3gpu_encoder_state_size(h_) * channels.size());
+        int rc = lc3gpu_encoder_state_save_channels(h_, channels.data(), (int)channels.size(), buf.data(), buf.size());
+        if (rc) throw Error(rc, "state_save");
+        return buf;
+    }
+    void state_load(const std::vector<uint8_t> &buf, const std::vector<int32_t> &channels) {
+        int rc = lc3gpu_encoder_state_load_channels(h_, channels.data(), (int)channels.size(), buf.data(), buf.size());
+        if (rc) throw Error(rc, "state_load");
+    }
     uint64_t size_clamps() {
         uint64_t v = 0;
         int rc = lc3gpu_encoder_size_clamps(h_, &v);
@@ -120,6 +145,31 @@ public:
     void decode_mixed(const uint8_t *d_in, int16_t *d_pcm, int n_frames, void *hip_stream = nullptr, const uint8_t *d_bad_frame = nullptr) {
         int rc = lc3gpu_decode_mixed(h_, d_in, d_bad_frame, d_pcm, n_frames, hip_stream);
         if (rc) throw Error(rc, "decode_mixed");
+    }
+    // a list of channels (HOST indices, any order, none twice): DEVICE buffers compact in list order; the other channels keep state and PLC count
+    void decode_list(const std::vector<int32_t> &channels, const uint8_t *d_in, int16_t *d_pcm, int nbytes, int n_frames, void *hip_stream = nullptr,
+                     const uint8_t *d_bad_frame = nullptr) {
+        int rc = lc3gpu_decode_list(h_, channels.data(), (int)channels.size(), d_in, d_bad_frame, d_pcm, nbytes, n_frames, hip_stream);
+        if (rc) throw Error(rc, "decode_list");
+    }
+    // every channel, or the named ones (a new DecoderChannel; their PLC counts go to zero); no wait
+    void reset() {
+        int rc = lc3gpu_decoder_reset(h_);
+        if (rc) throw Error(rc, "reset");
+    }
+    void reset(const std::vector<int32_t> &channels) {
+        int rc = lc3gpu_decoder_reset_channels(h_, channels.data(), (int)channels.size());
+        if (rc) throw Error(rc, "reset");
+    }
+    std::vector<uint8_t> state_save(const std::vector<int32_t> &channels) {
+        std::vector<uint8_t> buf(lc3gpu_decoder_state_size(h_) * channels.size());
+        int rc = lc3gpu_decoder_state_save_channels(h_, channels.data(), (int)channels.size(), buf.data(), buf.size());
+        if (rc) throw Error(rc, "state_save");
+        return buf;
+    }
+    void state_load(const std::vector<uint8_t> &buf, const std::vector<int32_t> &channels) {
+        int rc = lc3gpu_decoder_state_load_channels(h_, channels.data(), (int)channels.size(), buf.data(), buf.size());
+        if (rc) throw Error(rc, "state_load");
     }
     uint64_t plc_events() {
         uint64_t v = 0;

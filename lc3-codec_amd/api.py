@@ -248,6 +248,14 @@ def load_library():
     L.lc3gpu_encode.argtypes = [vp, vp, vp, i, i, vp]
     L.lc3gpu_encode_range.argtypes = [vp, i, i, vp, vp, i, i, vp]
     L.lc3gpu_encode_vbr.argtypes = [vp, vp, vp, vp, i, i, vp]
+    L.lc3gpu_encode_list.argtypes = [vp, vp, i, vp, vp, i, i, vp]
+    L.lc3gpu_decode_list.argtypes = [vp, vp, i, vp, vp, vp, i, i, vp]
+    L.lc3gpu_encoder_reset_channels.argtypes = [vp, vp, i]
+    L.lc3gpu_decoder_reset_channels.argtypes = [vp, vp, i]
+    L.lc3gpu_encoder_state_save_channels.argtypes = [vp, vp, i, vp, ctypes.c_size_t]
+    L.lc3gpu_encoder_state_load_channels.argtypes = [vp, vp, i, vp, ctypes.c_size_t]
+    L.lc3gpu_decoder_state_save_channels.argtypes = [vp, vp, i, vp, ctypes.c_size_t]
+    L.lc3gpu_decoder_state_load_channels.argtypes = [vp, vp, i, vp, ctypes.c_size_t]
     L.lc3gpu_encoder_size_clamps.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     L.lc3gpu_decode_vbr.argtypes = [vp, vp, vp, vp, vp, i, i, vp]
     L.lc3gpu_inspect.argtypes = [i, i, vp, vp, vp, i, i, vp, vp]
@@ -330,7 +338,9 @@ ABI_SYMBOLS = [
     "lc3gpu_pipeline_decode_mixed", "lc3gpu_pipeline_destroy", "lc3gpu_pipeline_reset", "lc3gpu_pipeline_submit",
     "lc3gpu_pipeline_encode", "lc3gpu_pipeline_decode", "lc3gpu_pipeline_wait", "lc3gpu_pipeline_join", "lc3gpu_pipeline_follow", "lc3gpu_pipeline_mark",
     "lc3gpu_pipeline_groups", "lc3gpu_pipeline_group", "lc3gpu_pipeline_last_hip_error", "lc3gpu_encode_vbr", "lc3gpu_encoder_size_clamps", "lc3gpu_decode_vbr",
-    "lc3gpu_inspect",
+    "lc3gpu_inspect", "lc3gpu_encode_list", "lc3gpu_decode_list", "lc3gpu_encoder_reset_channels", "lc3gpu_decoder_reset_channels",
+    "lc3gpu_encoder_state_save_channels", "lc3gpu_encoder_state_load_channels", "lc3gpu_decoder_state_save_channels",
+    "lc3gpu_decoder_state_load_channels",
 ]
 
 # LC3GPU_SPEC_*: opt-in corrections of the reference's deviations from the LC3 specification (default 0 = reference behaviour)
@@ -460,6 +470,14 @@ def _ptr(x):
     return ctypes.c_void_p(int(x))
 
 
+def _channel_list(channels):
+    """any integer sequence or numpy array -> contiguous HOST int32 array (the channel list of the *_list / *_channels calls)"""
+    a = np.asarray(channels)
+    if a.size and a.dtype.kind not in "iu":
+        raise TypeError("channel indices must be integers")
+    return np.ascontiguousarray(a.reshape(-1), dtype=np.int32)
+
+
 class Lc3Config:
     """common/config.rs:18-100"""
 
@@ -584,8 +602,22 @@ class Lc3Encoder:
             raise Lc3EncoderError(rc, "timing")
         return float(out[0]), float(out[1]), float(out[2]), float(out[3]), int(out[4])
 
-    def reset(self):
-        rc = self._L.lc3gpu_encoder_reset(self._h)
+    def encode_list(self, channels, d_pcm, d_out, nbytes, n_frames, stream=None):
+        """batch over a list of channels (HOST integers, any order, none twice): DEVICE int16[len(channels)][T][nf] -> DEVICE
+        uint8[len(channels)][T][nbytes], item i the frames of channel channels[i]; the other channels are left as they were.  Asynchronous
+        on `stream`; the list may be reused when the call returns (lc3gpu_encode_list)"""
+        ch = _channel_list(channels)
+        rc = self._L.lc3gpu_encode_list(self._h, _ptr(ch), int(ch.size), _ptr(d_pcm), _ptr(d_out), int(nbytes), int(n_frames), _ptr(stream))
+        if rc:
+            raise Lc3EncoderError(rc, "encode_list")
+
+    def reset(self, channels=None):
+        """every channel (channels=None) or the named ones back to the freshly constructed state from their next call on; no wait"""
+        if channels is None:
+            rc = self._L.lc3gpu_encoder_reset(self._h)
+        else:
+            ch = _channel_list(channels)
+            rc = self._L.lc3gpu_encoder_reset_channels(self._h, _ptr(ch), int(ch.size))
         if rc:
             raise Lc3EncoderError(rc, "reset")
 
@@ -615,7 +647,15 @@ class Lc3Encoder:
             raise Lc3EncoderError(rc, "pair_timeouts")
         return int(v.value)
 
-    def state_save(self):
+    def state_save(self, channels=None):
+        """the state blobs of every channel, or of the named ones (blob i belongs to channels[i])"""
+        if channels is not None:
+            ch = _channel_list(channels)
+            buf = np.zeros(self._L.lc3gpu_encoder_state_size(self._h) * ch.size, np.uint8)
+            rc = self._L.lc3gpu_encoder_state_save_channels(self._h, _ptr(ch), int(ch.size), _ptr(buf), buf.size)
+            if rc:
+                raise Lc3EncoderError(rc, "state_save")
+            return buf
         n = self._L.lc3gpu_encoder_state_size(self._h) * self.num_channels
         buf = np.zeros(n, np.uint8)
         rc = self._L.lc3gpu_encoder_state_save(self._h, _ptr(buf), buf.size)
@@ -623,8 +663,16 @@ class Lc3Encoder:
             raise Lc3EncoderError(rc, "state_save")
         return buf
 
-    def state_load(self, buf):
+    def state_load(self, buf, channels=None):
         buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        if channels is not None:
+            ch = _channel_list(channels)
+            if buf.size != self._L.lc3gpu_encoder_state_size(self._h) * ch.size:
+                raise ValueError("state blob size does not match the channel list (state_size * len(channels))")
+            rc = self._L.lc3gpu_encoder_state_load_channels(self._h, _ptr(ch), int(ch.size), _ptr(buf), buf.size)
+            if rc:
+                raise Lc3EncoderError(rc, "state_load")
+            return
         if buf.size != self._L.lc3gpu_encoder_state_size(self._h) * self.num_channels:
             raise ValueError("state blob size does not match this handle (state_size * num_channels)")
         rc = self._L.lc3gpu_encoder_state_load(self._h, _ptr(buf), buf.size)
@@ -778,8 +826,23 @@ class Lc3Decoder:
             raise Lc3DecoderError(rc, "timing")
         return float(out[0]), float(out[1]), float(out[2]), float(out[3]), int(out[4])
 
-    def reset(self):
-        rc = self._L.lc3gpu_decoder_reset(self._h)
+    def decode_list(self, channels, d_in, d_pcm, nbytes, n_frames, stream=None, d_bad_frame=None):
+        """batch over a list of channels (HOST integers, any order, none twice): DEVICE uint8[len(channels)][T][nbytes] (and optional flags
+        uint8[len(channels)][T]) -> DEVICE int16[len(channels)][T][nf], item i the frames of channel channels[i]; the other channels keep
+        their state and PLC count.  Asynchronous on `stream` (lc3gpu_decode_list)"""
+        ch = _channel_list(channels)
+        rc = self._L.lc3gpu_decode_list(self._h, _ptr(ch), int(ch.size), _ptr(d_in), _ptr(d_bad_frame), _ptr(d_pcm), int(nbytes), int(n_frames),
+                                        _ptr(stream))
+        if rc:
+            raise Lc3DecoderError(rc, "decode_list")
+
+    def reset(self, channels=None):
+        """every channel (channels=None) or the named ones back to the freshly constructed state (PLC count 0) from their next call on; no wait"""
+        if channels is None:
+            rc = self._L.lc3gpu_decoder_reset(self._h)
+        else:
+            ch = _channel_list(channels)
+            rc = self._L.lc3gpu_decoder_reset_channels(self._h, _ptr(ch), int(ch.size))
         if rc:
             raise Lc3DecoderError(rc, "reset")
 
@@ -814,7 +877,15 @@ class Lc3Decoder:
             raise Lc3DecoderError(rc, "pair_timeouts")
         return int(v.value)
 
-    def state_save(self):
+    def state_save(self, channels=None):
+        """the state blobs of every channel, or of the named ones (blob i belongs to channels[i])"""
+        if channels is not None:
+            ch = _channel_list(channels)
+            buf = np.zeros(self._L.lc3gpu_decoder_state_size(self._h) * ch.size, np.uint8)
+            rc = self._L.lc3gpu_decoder_state_save_channels(self._h, _ptr(ch), int(ch.size), _ptr(buf), buf.size)
+            if rc:
+                raise Lc3DecoderError(rc, "state_save")
+            return buf
         n = self._L.lc3gpu_decoder_state_size(self._h) * self.num_channels
         buf = np.zeros(n, np.uint8)
         rc = self._L.lc3gpu_decoder_state_save(self._h, _ptr(buf), buf.size)
@@ -822,8 +893,16 @@ class Lc3Decoder:
             raise Lc3DecoderError(rc, "state_save")
         return buf
 
-    def state_load(self, buf):
+    def state_load(self, buf, channels=None):
         buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        if channels is not None:
+            ch = _channel_list(channels)
+            if buf.size != self._L.lc3gpu_decoder_state_size(self._h) * ch.size:
+                raise ValueError("state blob size does not match the channel list (state_size * len(channels))")
+            rc = self._L.lc3gpu_decoder_state_load_channels(self._h, _ptr(ch), int(ch.size), _ptr(buf), buf.size)
+            if rc:
+                raise Lc3DecoderError(rc, "state_load")
+            return
         if buf.size != self._L.lc3gpu_decoder_state_size(self._h) * self.num_channels:
             raise ValueError("state blob size does not match this handle (state_size * num_channels)")
         rc = self._L.lc3gpu_decoder_state_load(self._h, _ptr(buf), buf.size)

@@ -538,6 +538,7 @@ LC3_TU_STATIC __device__ unsigned long long lc3_prof_acc[64];  // 0..31 stage su
 #include "lc3_dev_enc_vbr.h"
 #include "lc3_dev_dec_vbr.h"
 #include "lc3_dev_dec_inspect.h"
+#include "lc3_dev_list.h"
 #include "lc3_host_plan.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -1009,6 +1010,54 @@ __global__ __launch_bounds__(256) void lc3_pack_vbr_kernel(int ne, const int32_t
         const int j = (int)((unsigned)i / (unsigned)slot);
         if (i - j * slot < s_nb[j]) dst[i] = s_bytes[i];
     }
+}
+#endif
+
+// ---- a list of channels (lc3gpu_encode_list; lc3_dev_list.h) -----------------------------------------------------------------------------
+// Kernels of their own, as the sized ones: the launch's stream s is item s of the caller's compact planar buffers and of the planes, its
+// state is states[channel of entry s] and it starts fresh when entry s says so.  The vector quantiser, the symbol preparation and both
+// packers run unchanged on the compact planes.  Main unit only: the headline view and the run-time view.
+#if LC3_IN_HOST_TU
+template <class CV>
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, lc3_front_waves<CV>::value) void lc3_enc_front_list_kernel(
+    lc3_cfg_slot<CV> cfg, lc3_enc_state *states, const int32_t *channel_of, int n_streams, const int16_t *pcm, float *mid, int32_t *planes,
+    int nbytes, int n_frames, int spec_flags) {
+    const int lane = threadIdx.x & 63, wave = LC3_WAVE_ID();
+    lc3_enc_lds &L = lc3_enc_wg[wave];
+    const int s_raw = (int)blockIdx.x * LC3_WG_WAVES + wave;
+    const int valid = s_raw < n_streams;
+    const int s = valid ? s_raw : n_streams - 1;  // see lc3_enc_front_body
+    typename CV::bind_t c0 = CV::bind(lc3_cfg_table[cfg.id]);
+    const int entry = lc3_list_entry(channel_of, s);
+    lc3_enc_state *gst = states + (size_t)lc3_list_channel(entry);
+#ifndef LC3_TABLES_IN_GLOBAL
+    lc3_front_tables_stage_image(c0.stage_image);
+    lc3_fft_tables_stage_image(c0.stage_image);  // ends with the workgroup barrier
+#endif
+    const size_t fbase = (size_t)s * (size_t)n_frames;
+    lc3_list_front_stream(cfg, L, lane, gst, lc3_list_fresh(entry), valid, pcm + fbase * (size_t)c0.nf, mid, planes, fbase, nbytes, n_frames,
+                          spec_flags, lc3_front_outline<CV>::value);
+}
+template <class CV>
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, LC3_BACK_WAVES) void lc3_enc_back_list_kernel(lc3_cfg_slot<CV> cfg, lc3_enc_state *states,
+                                                                                 const int32_t *channel_of, int n_streams, const float *mid,
+                                                                                 int32_t *planes, int nbytes, int n_frames, int spec_flags) {
+    const int lane = threadIdx.x & 63, wave = LC3_WAVE_ID();
+    lc3_enc_lds &L = lc3_enc_wg[wave];
+    const int s_raw = (int)blockIdx.x * LC3_WG_WAVES + wave;
+    const int valid = s_raw < n_streams;
+    const int s = valid ? s_raw : n_streams - 1;
+    lc3_enc_state *gst = states + (size_t)lc3_list_channel(lc3_list_entry(channel_of, s));
+#if LC3_SPEC_IN_LDS
+    {   // spectral-model tables -> LDS, once per workgroup
+        const uint32_t *lk = (const uint32_t *)LC3T_AC_SPEC_LOOKUP, *bt = (const uint32_t *)&LC3T_AC_SPEC_BITS[0][0];
+        uint32_t *dl = (uint32_t *)lc3_spec_tab.lookup, *db = (uint32_t *)lc3_spec_tab.bits;
+        for (int i = threadIdx.x; i < 1024; i += 64 * LC3_WG_WAVES) dl[i] = lk[i];
+        for (int i = threadIdx.x; i < 64 * 17 / 2; i += 64 * LC3_WG_WAVES) db[i] = bt[i];
+        __syncthreads();
+    }
+#endif
+    lc3_list_back_stream(cfg, L, lane, gst, valid, mid, planes, (size_t)s * (size_t)n_frames, nbytes, n_frames, spec_flags);
 }
 #endif
 
@@ -1699,6 +1748,32 @@ __global__ __launch_bounds__(64 * LC3_WG_WAVES, LATE ? 4 : LC3_SYNTH_WAVES) void
                                }, fresh);
     if (valid) lc3_dec_state_store(c0, L, lane, gst);
 }
+// ---- decoder over a list of channels (lc3gpu_decode_list; lc3_dev_list.h) ----------------------------------------------------------------
+// The synthesis kernel with the stream's state found through the list and its freshness read per stream; both parsers and the wave-per-
+// frame reconstruction kernels run unchanged on the compact buffers.  LATE as lc3_decode_body.
+template <class CV, int LATE>
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, LATE ? 4 : LC3_SYNTH_WAVES) void lc3_decode_list_kernel(lc3_cfg_slot<CV> cfg, lc3_dec_state *states,
+                                                                                                   const int32_t *channel_of, int n_streams,
+                                                                                                   const int32_t *planes, int16_t *pcm, int nbytes,
+                                                                                                   int n_frames) {
+    const int lane = threadIdx.x & 63, wave = LC3_WAVE_ID();
+    lc3_dec_lds &L = lc3_dec_wg[wave];
+    const int s_raw = (int)blockIdx.x * LC3_WG_WAVES + wave;
+    const int valid = s_raw < n_streams;
+    const int s = valid ? s_raw : n_streams - 1;
+    typename CV::bind_t c0 = CV::bind(lc3_cfg_table[cfg.id]);
+    const int entry = lc3_list_entry(channel_of, s);
+    lc3_dec_state *gst = states + (size_t)lc3_list_channel(entry);
+#ifndef LC3_TABLES_IN_GLOBAL
+    const lc3_fft_image_regs tab_regs = lc3_fft_tables_image_issue(c0.stage_image);
+#endif
+    const size_t fbase = (size_t)s * (size_t)n_frames;
+    lc3_list_synth_stream(cfg, L, lane, gst, lc3_list_fresh(entry), valid, nbytes, planes, fbase, n_frames, pcm + fbase * (size_t)c0.nf, LATE, [&]() {
+#ifndef LC3_TABLES_IN_GLOBAL
+        lc3_fft_tables_image_commit(tab_regs);
+#endif
+    });
+}
 // ---- frame inspection (lc3gpu_inspect; lc3_dev_dec_inspect.h) ---------------------------------------------------------------------------
 // One lane per frame over a flat list of slots, the run-time view only.  Dynamic LDS: the parser's lookup, spectral and TNS models, then
 // per frame its 128-byte record (lane-major), 14 words of lsb-mode flags (word-major) and its slot of bytes.  The records leave through
@@ -2322,10 +2397,64 @@ struct HandleCommon {
         ev_join[1] = ev[3];
         return LC3GPU_OK;
     }
+    // The channel list of a list call (lc3gpu_encode_list / lc3gpu_decode_list): the caller's HOST array is checked, merged with the
+    // channels' fresh flags (lc3_dev_list.h) into a slot of PINNED host memory the handle owns, and copied from there to the handle's device
+    // copy by an asynchronous copy on the call's stream, in front of the call's kernels -- the caller's array is free when the call returns and
+    // the host waits for nothing.  LC3_LIST_SLOTS slots take turns; a slot is reused once the copy that read it has completed (its event:
+    // LC3_LIST_SLOTS calls back, long done in any steady state).  One device copy is enough: a handle's launches are ordered (order_begin).
+#define LC3_LIST_SLOTS 4
+    int32_t *h_list[LC3_LIST_SLOTS] = {}, *d_list = nullptr;
+    hipEvent_t list_ev[LC3_LIST_SLOTS] = {};
+    bool list_busy[LC3_LIST_SLOTS] = {};
+    int list_next = 0;
+    std::vector<uint32_t> list_seen;  // per channel: the number of the list call that named it last (the repeated-index check)
+    uint32_t list_call = 0;
+    // LC3GPU_OK, or LC3GPU_ECHANNEL for an index outside the handle or named twice; nothing is queued or changed
+    int list_check(const int32_t *channels, int n) {
+        if (list_seen.size() != (size_t)num_channels) list_seen.assign((size_t)num_channels, 0u);
+        if (++list_call == 0u) {  // (the counter wrapped: start over)
+            std::fill(list_seen.begin(), list_seen.end(), 0u);
+            list_call = 1u;
+        }
+        for (int i = 0; i < n; i++) {
+            const int ch = channels[i];
+            if (ch < 0 || ch >= num_channels || list_seen[(size_t)ch] == list_call) return LC3GPU_ECHANNEL;
+            list_seen[(size_t)ch] = list_call;
+        }
+        return LC3GPU_OK;
+    }
+    // entry i = channels[i] | LC3_LIST_FRESH where fresh[channels[i]] -> the device copy, in stream order on `s`
+    int list_upload(const int32_t *channels, int n, const std::vector<uint8_t> &fresh, hipStream_t s) {
+        if (!d_list) {
+            HIP_TRY(hipMalloc((void **)&d_list, sizeof(int32_t) * (size_t)num_channels));
+            for (int i = 0; i < LC3_LIST_SLOTS; i++) {
+                HIP_TRY(hipHostMalloc((void **)&h_list[i], sizeof(int32_t) * (size_t)num_channels, hipHostMallocDefault));
+                HIP_TRY(hipEventCreateWithFlags(&list_ev[i], hipEventDisableTiming));
+            }
+        }
+        const int k = list_next;
+        if (list_busy[k]) HIP_TRY(hipEventSynchronize(list_ev[k]));
+        list_busy[k] = false;
+        int32_t *dst = h_list[k];
+        for (int i = 0; i < n; i++) dst[i] = (int32_t)((uint32_t)channels[i] | (fresh[(size_t)channels[i]] ? LC3_LIST_FRESH : 0u));
+        HIP_TRY(hipMemcpyAsync(d_list, dst, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(list_ev[k], s));
+        list_busy[k] = true;
+        list_next = (k + 1) % LC3_LIST_SLOTS;
+        return LC3GPU_OK;
+    }
     const HostCfg &cfg_of_channel(int ch) const { return mixed ? groups[(size_t)streams[(size_t)ch].group].h : h; }
     int internal_of_channel(int ch) const { return mixed ? streams[(size_t)ch].internal : ch; }
     void release_common() {
         timer.release();
+        if (d_list) (void)hipFree(d_list);
+        d_list = nullptr;
+        for (int i = 0; i < LC3_LIST_SLOTS; i++) {
+            if (h_list[i]) (void)hipHostFree(h_list[i]);
+            if (list_ev[i]) (void)hipEventDestroy(list_ev[i]);
+            h_list[i] = nullptr;
+            list_ev[i] = nullptr;
+        }
         if (done) (void)hipEventDestroy(done);
         if (d_tab) (void)hipFree(d_tab);
         if (d_pc_timeouts) (void)hipFree(d_pc_timeouts);
@@ -2495,8 +2624,21 @@ struct lc3gpu_decoder : HandleCommon {
     float *d_dbg = nullptr;        // stage dumps of the diagnostic entry points (LC3_DBG_FLOATS), allocated at first use
     // lc3gpu_decoder_reset only NOTES that every channel is back to the constructed state: the next batch launch over all channels initialises
     // the states inside the synthesis kernel (fresh = 1, as the encoder's fresh_mask does); anything else that looks at the state blobs first
-    // (a range or frame call, state_save, plc_events, the diagnostic calls) materialises them with the zero-frame launch (decoder_init_states)
-    bool fresh_pending = false;
+    // (a range or frame call, state_save, plc_events, the diagnostic calls) materialises them with the zero-frame launch (decoder_init_states).
+    // The record is per channel (internal order), as the encoder's: lc3gpu_decoder_reset_channels notes single channels, a list call
+    // (lc3gpu_decode_list) starts the noted ones among its channels fresh inside its launch and leaves the others noted
+    std::vector<uint8_t> fresh_mask;
+    int fresh_count = 0;  // channels noted in fresh_mask
+    void fresh_set_all(uint8_t v) {
+        fresh_mask.assign((size_t)num_channels, v);
+        fresh_count = v ? num_channels : 0;
+    }
+    void fresh_clear(int internal) {
+        if (fresh_mask[(size_t)internal]) {
+            fresh_mask[(size_t)internal] = 0;
+            fresh_count -= 1;
+        }
+    }
 };
 
 // frames per workgroup of the lane-per-frame kernels (= threads per workgroup).  LC3GPU_FPB overrides (tuning aid).
@@ -2736,10 +2878,47 @@ static int state_blobs_load(HandleCommon &hc, ST *d_states, uint32_t magic, int 
     HIP_TRY(hipMemcpy(d_states, tmp.data(), sizeof(ST) * tmp.size(), hipMemcpyHostToDevice));
     return LC3GPU_OK;
 }
+// the same for a list of channels (caller order): blob i belongs to channels[i]; the format is that of the whole-handle calls, so a slice
+// of a whole-handle save loads through here and the other way round.  Arguments common to both sides are checked here.
+static int state_blobs_channels_args(const HandleCommon &hc, const int32_t *channels, int n, const void *host, size_t nbytes, size_t per) {
+    if (n < 0 || (n > 0 && (!channels || !host))) return LC3GPU_EINVAL;
+    for (int i = 0; i < n; i++)
+        if (channels[i] < 0 || channels[i] >= hc.num_channels) return LC3GPU_ECHANNEL;
+    return nbytes == per * (size_t)n ? LC3GPU_OK : LC3GPU_ELENGTH;
+}
+template <class ST>
+static int state_blobs_save_channels(HandleCommon &hc, const ST *d_states, uint32_t magic, int spec_flags, const int32_t *channels, int n,
+                                     void *host_dst) {
+    const size_t per = sizeof(lc3_state_header) + sizeof(ST);
+    for (int i = 0; i < n; i++) {
+        char *dst = (char *)host_dst + per * (size_t)i;
+        const lc3_state_header hd = lc3_state_header_of(hc, channels[i], magic, sizeof(ST), spec_flags);
+        std::memcpy(dst, &hd, sizeof(hd));
+        HIP_TRY(hipMemcpy(dst + sizeof(hd), d_states + hc.internal_of_channel(channels[i]), sizeof(ST), hipMemcpyDeviceToHost));
+    }
+    return LC3GPU_OK;
+}
+template <class ST>
+static int state_blobs_check_channels(HandleCommon &hc, uint32_t magic, int spec_flags, const int32_t *channels, int n, const void *host_src) {
+    const size_t per = sizeof(lc3_state_header) + sizeof(ST);
+    for (int i = 0; i < n; i++) {  // every header before any channel is written
+        const lc3_state_header want = lc3_state_header_of(hc, channels[i], magic, sizeof(ST), spec_flags);
+        if (std::memcmp((const char *)host_src + per * (size_t)i, &want, sizeof(want)) != 0) return LC3GPU_EINVAL;
+    }
+    return LC3GPU_OK;
+}
+template <class ST>
+static int state_blobs_load_channels(HandleCommon &hc, ST *d_states, const int32_t *channels, int n, const void *host_src) {
+    const size_t per = sizeof(lc3_state_header) + sizeof(ST);
+    for (int i = 0; i < n; i++)
+        HIP_TRY(hipMemcpy(d_states + hc.internal_of_channel(channels[i]), (const char *)host_src + per * (size_t)i + sizeof(lc3_state_header),
+                          sizeof(ST), hipMemcpyHostToDevice));
+    return LC3GPU_OK;
+}
 
 extern "C" {
 
-int lc3gpu_version(void) { return 300; }
+int lc3gpu_version(void) { return 310; }
 
 const char *lc3gpu_strerror(int code) {
     switch (code) {
@@ -2943,19 +3122,30 @@ static int lc3_split_stagger() {
     return v;
 }
 
+// the list kernels (lc3_dev_list.h) exist for the headline view and the run-time view, like the sized ones
+#define LC3_LAUNCH_LIST(kern, h, grid, block, lds, stream, ...)                                                                  \
+    do {                                                                                                                        \
+        if ((h).view == 1) hipLaunchKernelGGL(kern<lc3_cfg_48k10>, grid, block, lds, stream, lc3_cfg_slot<lc3_cfg_48k10>{(h).slot}, __VA_ARGS__); \
+        else hipLaunchKernelGGL(kern<lc3_cfg_any>, grid, block, lds, stream, lc3_cfg_slot<lc3_cfg_any>{(h).slot}, __VA_ARGS__);                 \
+    } while (0)
 // the four encoder kernels of channels [first, first + n) (internal order) on `stream`; the buffers and planes are those of this range.
-// chain: the timer's chain of this stream.  after_front: recorded behind the front half when not null
+// chain: the timer's chain of this stream.  after_front: recorded behind the front half when not null.  d_list (a list call): the n
+// streams are the channels of the list's entries (first and fresh are not used), planar compact buffers
 static int encode_kernels(lc3gpu_encoder *e, const HostCfg &h, int first, int n, const int16_t *d_pcm, uint8_t *d_out, float *mid,
                           int32_t *planes, int nbytes, int n_frames, int fresh, lc3_io io, hipStream_t stream, int chain,
-                          hipEvent_t after_front, float *dbg, size_t frames_of_call) {
+                          hipEvent_t after_front, float *dbg, size_t frames_of_call, const int32_t *d_list = nullptr) {
     const size_t frames = (size_t)n * (size_t)n_frames;
     // analysis front half (wave per stream) -> SNS vector quantiser (lane per frame) -> back half (wave per stream) ->
     // bitstream packing (lane per frame)
     const dim3 wg_grid((unsigned)((n + LC3_WG_WAVES - 1) / LC3_WG_WAVES)), wg_block(64 * LC3_WG_WAVES);
     int rc_stage = 0;
     e->timer.mark(stream, -1, chain);
-    LC3_LAUNCH_CFG(lc3_enc_front_kernel, h, wg_grid, wg_block, lc3_lds_pad(0), stream, e->d_states, first, n, d_pcm, mid, planes, nbytes, n_frames, fresh,
-                   dbg, io, e->spec_flags);
+    if (d_list)
+        LC3_LAUNCH_LIST(lc3_enc_front_list_kernel, h, wg_grid, wg_block, lc3_lds_pad(0), stream, e->d_states, d_list, n, d_pcm, mid, planes, nbytes,
+                        n_frames, e->spec_flags);
+    else
+        LC3_LAUNCH_CFG(lc3_enc_front_kernel, h, wg_grid, wg_block, lc3_lds_pad(0), stream, e->d_states, first, n, d_pcm, mid, planes, nbytes, n_frames, fresh,
+                       dbg, io, e->spec_flags);
     HIP_TRY(hipGetLastError());
     e->timer.mark(stream, 0, chain);
     if (after_front) HIP_TRY(hipEventRecord(after_front, stream));
@@ -2965,8 +3155,12 @@ static int encode_kernels(lc3gpu_encoder *e, const HostCfg &h, int first, int n,
     HIP_TRY(hipGetLastError());
     e->timer.mark(stream, 1, chain);
     if (chain == 0 && (rc_stage = e->stage_record(LC3GPU_ENC_STAGE_VQ, stream)) != 0) return rc_stage;
-    LC3_LAUNCH_CFG(lc3_enc_back_kernel, h, wg_grid, wg_block, lc3_lds_pad(1), stream, e->d_states, first, n, (const float *)mid, planes, nbytes, n_frames,
-                   dbg, e->spec_flags | lc3_prep_symbols_flag(frames_of_call));
+    if (d_list)
+        LC3_LAUNCH_LIST(lc3_enc_back_list_kernel, h, wg_grid, wg_block, lc3_lds_pad(1), stream, e->d_states, d_list, n, (const float *)mid, planes, nbytes,
+                        n_frames, e->spec_flags | lc3_prep_symbols_flag(frames_of_call));
+    else
+        LC3_LAUNCH_CFG(lc3_enc_back_kernel, h, wg_grid, wg_block, lc3_lds_pad(1), stream, e->d_states, first, n, (const float *)mid, planes, nbytes, n_frames,
+                       dbg, e->spec_flags | lc3_prep_symbols_flag(frames_of_call));
     HIP_TRY(hipGetLastError());
     e->timer.mark(stream, 2, chain);
     if (chain == 0 && (rc_stage = e->stage_record(LC3GPU_ENC_STAGE_BACK, stream)) != 0) return rc_stage;
@@ -3083,6 +3277,46 @@ int lc3gpu_encode_range(lc3gpu_encoder *e, int first_channel, int n_channels, co
     LC3_ON_DEVICE(e);
     return encode_launch(e, e->h, first_channel, n_channels, d_pcm, d_out, nbytes, n_frames, LC3GPU_LAYOUT_PLANAR, (hipStream_t)stream,
                          nullptr);
+}
+
+// A list of channels (lc3_dev_list.h): everything is checked on the host before anything is queued; then the list goes to the device in
+// stream order (HandleCommon::list_upload) and the four kernels run over the n_list compact streams, fresh and carried channels in the
+// same launch.  Always one part (no LC3GPU_SPLIT).
+int lc3gpu_encode_list(lc3gpu_encoder *e, const int32_t *channels, int n_list, const int16_t *d_pcm, uint8_t *d_out, int nbytes, int n_frames,
+                       void *stream_) {
+    if (!e || e->mixed || n_list < 0) return LC3GPU_EINVAL;
+    if (nbytes < 20 || nbytes > LC3_MAX_NE || n_frames <= 0) return LC3GPU_ELENGTH;
+    if (n_list == 0) return LC3GPU_OK;
+    if (!channels || !d_pcm || !d_out || ((uintptr_t)d_pcm & 3u) != 0) return LC3GPU_EINVAL;
+    int rc = e->list_check(channels, n_list);
+    if (rc) return rc;
+    LC3_ON_DEVICE(e);
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t frames = (size_t)n_list * (size_t)n_frames;
+    rc = e->order_begin(stream);
+    if (rc == LC3GPU_OK) rc = encoder_reserve_planes(e, frames, stream);
+    if (rc == LC3GPU_OK) rc = e->list_upload(channels, n_list, e->fresh_mask, stream);
+    if (rc) return rc;
+    const lc3_io io = {0, nullptr};
+    const size_t t0 = e->timer.used;
+    e->timer.arm();
+    rc = encode_kernels(e, e->h, 0, n_list, d_pcm, d_out, e->d_mid, e->d_planes, nbytes, n_frames, 0, io, stream, 0, nullptr, nullptr, frames, e->d_list);
+    if (rc) {
+        e->timer.rollback(t0);
+        (void)e->order_end(stream);
+        return rc;
+    }
+    for (int i = 0; i < n_list; i++) e->fresh_mask[(size_t)channels[i]] = 0;
+    return e->order_end(stream);
+}
+
+// the named channels are back in the constructed state from their next call on (no wait, no launch: lc3gpu_encoder_reset)
+int lc3gpu_encoder_reset_channels(lc3gpu_encoder *e, const int32_t *channels, int n) {
+    if (!e || n < 0 || (n > 0 && !channels)) return LC3GPU_EINVAL;
+    for (int i = 0; i < n; i++)
+        if (channels[i] < 0 || channels[i] >= e->num_channels) return LC3GPU_ECHANNEL;
+    for (int i = 0; i < n; i++) e->fresh_mask[(size_t)e->internal_of_channel(channels[i])] = 1;
+    return LC3GPU_OK;
 }
 
 // A frame size per frame (lc3_dev_enc_vbr.h): the four encoder stages as lc3gpu_encode runs them, with the sized front half, back half and
@@ -3311,25 +3545,55 @@ int lc3gpu_encoder_state_load(lc3gpu_encoder *e, const void *host_src, size_t nb
     return LC3GPU_OK;
 }
 
+int lc3gpu_encoder_state_save_channels(lc3gpu_encoder *e, const int32_t *channels, int n, void *host_dst, size_t nbytes) {
+    if (!e) return LC3GPU_EINVAL;
+    int rc = state_blobs_channels_args(*e, channels, n, host_dst, nbytes, lc3gpu_encoder_state_size(e));
+    if (rc) return rc;
+    LC3_ON_DEVICE(e);
+    HIP_TRY(hipDeviceSynchronize());  // (as lc3gpu_encoder_state_save)
+    for (int i = 0; i < n && rc == LC3GPU_OK; i++) rc = encoder_materialise(e, e->internal_of_channel(channels[i]), 1, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    return state_blobs_save_channels(*e, e->d_states, LC3_STATE_MAGIC_ENC, e->spec_flags & LC3GPU_SPEC_ALL, channels, n, host_dst);
+}
+
+int lc3gpu_encoder_state_load_channels(lc3gpu_encoder *e, const int32_t *channels, int n, const void *host_src, size_t nbytes) {
+    if (!e) return LC3GPU_EINVAL;
+    int rc = state_blobs_channels_args(*e, channels, n, host_src, nbytes, lc3gpu_encoder_state_size(e));
+    if (rc == LC3GPU_OK) rc = state_blobs_check_channels<lc3_enc_state>(*e, LC3_STATE_MAGIC_ENC, e->spec_flags & LC3GPU_SPEC_ALL, channels, n, host_src);
+    if (rc) return rc;
+    LC3_ON_DEVICE(e);
+    HIP_TRY(hipDeviceSynchronize());  // a launch in flight would store its state over the loaded one
+    rc = state_blobs_load_channels(*e, e->d_states, channels, n, host_src);
+    if (rc) return rc;
+    for (int i = 0; i < n; i++) e->fresh_mask[(size_t)e->internal_of_channel(channels[i])] = 0;
+    return LC3GPU_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 static int decoder_init_states(lc3gpu_decoder *d) {
     // decoder state is materialised eagerly (fresh = 1, zero frames): PLC counters must survive range launches
+    // Every maximal run of channels noted fresh, per configuration group (a handle just created or reset: one launch over all of them).
     HIP_TRY(hipDeviceSynchronize());  // nothing of this handle may still be in flight (its state is about to be rewritten)
-    d->fresh_pending = false;
     lc3_io io = {0, nullptr};
-    if (!d->mixed) {
-        LC3_LAUNCH_CFG(lc3_decode_kernel, d->h, dim3((unsigned)((d->num_channels + LC3_WG_WAVES - 1) / LC3_WG_WAVES)),
-                       dim3(64 * LC3_WG_WAVES), 0, nullptr, d->d_states, 0, d->num_channels, (const int32_t *)d->d_planes, d->d_pcm1, 20,
-                       0, 1, io);
-        HIP_TRY(hipGetLastError());
-    } else {
-        for (const GroupHost &g : d->groups) {
-            LC3_LAUNCH_CFG(lc3_decode_kernel, g.h, dim3((unsigned)((g.n_streams + LC3_WG_WAVES - 1) / LC3_WG_WAVES)),
-                           dim3(64 * LC3_WG_WAVES), 0, nullptr, d->d_states, g.first_stream, g.n_streams, (const int32_t *)d->d_planes,
-                           d->d_pcm1, 20, 0, 1, io);
+    const size_t n_groups = d->mixed ? d->groups.size() : 1;
+    for (size_t gi = 0; gi < n_groups; gi++) {
+        const HostCfg &h = d->mixed ? d->groups[gi].h : d->h;
+        const int lo = d->mixed ? d->groups[gi].first_stream : 0, hi = lo + (d->mixed ? d->groups[gi].n_streams : d->num_channels);
+        for (int i = lo; i < hi;) {
+            if (!d->fresh_mask[(size_t)i]) {
+                i++;
+                continue;
+            }
+            int j = i;
+            while (j < hi && d->fresh_mask[(size_t)j]) j++;
+            LC3_LAUNCH_CFG(lc3_decode_kernel, h, dim3((unsigned)((j - i + LC3_WG_WAVES - 1) / LC3_WG_WAVES)), dim3(64 * LC3_WG_WAVES), 0, nullptr,
+                           d->d_states, i, j - i, (const int32_t *)d->d_planes, d->d_pcm1, 20, 0, 1, io);
             HIP_TRY(hipGetLastError());
+            i = j;
         }
     }
+    d->fresh_set_all(0);
     HIP_TRY(hipDeviceSynchronize());
     return LC3GPU_OK;
 }
@@ -3346,6 +3610,7 @@ static int decoder_alloc(lc3gpu_decoder *d) {
     HIP_TRY(hipHostMalloc((void **)&d->d_in1, LC3_MAX_NE, hipHostMallocDefault));  // *_frame staging: pinned host memory, used in place
     HIP_TRY(hipHostMalloc((void **)&d->d_pcm1, sizeof(int16_t) * LC3_MAX_NF, hipHostMallocDefault));
     int rc = decoder_reserve_planes(d, (size_t)d->num_channels, nullptr);
+    d->fresh_set_all(1);
     if (rc == LC3GPU_OK) rc = decoder_init_states(d);
     return rc;
 }
@@ -3398,15 +3663,30 @@ int lc3gpu_decoder_destroy(lc3gpu_decoder *d) {
 
 int lc3gpu_decoder_reset(lc3gpu_decoder *d) {
     if (!d) return LC3GPU_EINVAL;
-    d->fresh_pending = true;  // (no wait, for the encoder's reasons: lc3gpu_encoder_reset; whoever reads the blobs first synchronises -- decoder_materialise)
+    d->fresh_set_all(1);  // (no wait, for the encoder's reasons: lc3gpu_encoder_reset; whoever reads the blobs first synchronises -- decoder_materialise)
     return LC3GPU_OK;
 }
 // the state blobs as a reader expects them: a reset that is still only noted is carried out
-static int decoder_materialise(lc3gpu_decoder *d) { return d->fresh_pending ? decoder_init_states(d) : LC3GPU_OK; }
+static int decoder_materialise(lc3gpu_decoder *d) { return d->fresh_count ? decoder_init_states(d) : LC3GPU_OK; }
+// the named channels only (lc3gpu_decoder_reset); no wait, no launch
+int lc3gpu_decoder_reset_channels(lc3gpu_decoder *d, const int32_t *channels, int n) {
+    if (!d || n < 0 || (n > 0 && !channels)) return LC3GPU_EINVAL;
+    for (int i = 0; i < n; i++)
+        if (channels[i] < 0 || channels[i] >= d->num_channels) return LC3GPU_ECHANNEL;
+    for (int i = 0; i < n; i++) {
+        const size_t k = (size_t)d->internal_of_channel(channels[i]);
+        if (!d->fresh_mask[k]) {
+            d->fresh_mask[k] = 1;
+            d->fresh_count += 1;
+        }
+    }
+    return LC3GPU_OK;
+}
 
 // the decoder kernels of channels [first, first + n) (internal order) on `stream`; buffers, flags and planes are those of this range
 static int decode_kernels(lc3gpu_decoder *d, const HostCfg &h, int first, int n, const uint8_t *d_in, const uint8_t *d_bad, int16_t *d_pcm,
-                          int32_t *planes, int nbytes, int n_frames, lc3_io io, int mode, hipStream_t stream, int chain, int fresh = 0) {
+                          int32_t *planes, int nbytes, int n_frames, lc3_io io, int mode, hipStream_t stream, int chain, int fresh = 0,
+                          const int32_t *d_list = nullptr) {  // d_list (a list call): the n streams are the channels of the list's entries
     // stage 1: parse all n * n_frames frames, one lane each (stateless); stage 2: synthesis, one wave per stream
     const size_t frames = (size_t)n * (size_t)n_frames;
     // frames per workgroup: as many as fit the default 64 KB of dynamic LDS (tables + 64 B of scale factors and nbytes of
@@ -3443,7 +3723,21 @@ static int decode_kernels(lc3gpu_decoder *d, const HostCfg &h, int first, int n,
         const int rc_stage = d->stage_record(LC3GPU_DEC_STAGE_PARSE, stream);
         if (rc_stage) return rc_stage;
     }
-    if (mode == LC3_RECON_LATE)
+    if (d_list) {
+        const dim3 grid((unsigned)((n + LC3_WG_WAVES - 1) / LC3_WG_WAVES)), block(64 * LC3_WG_WAVES);
+        const int32_t *pl = planes;
+        if (mode == LC3_RECON_LATE) {
+            if (h.view == 1) hipLaunchKernelGGL((lc3_decode_list_kernel<lc3_cfg_48k10, 1>), grid, block, 0, stream, lc3_cfg_slot<lc3_cfg_48k10>{h.slot},
+                                                d->d_states, d_list, n, pl, d_pcm, nbytes, n_frames);
+            else hipLaunchKernelGGL((lc3_decode_list_kernel<lc3_cfg_any, 1>), grid, block, 0, stream, lc3_cfg_slot<lc3_cfg_any>{h.slot}, d->d_states,
+                                    d_list, n, pl, d_pcm, nbytes, n_frames);
+        } else {
+            if (h.view == 1) hipLaunchKernelGGL((lc3_decode_list_kernel<lc3_cfg_48k10, 0>), grid, block, lc3_lds_pad(2), stream,
+                                                lc3_cfg_slot<lc3_cfg_48k10>{h.slot}, d->d_states, d_list, n, pl, d_pcm, nbytes, n_frames);
+            else hipLaunchKernelGGL((lc3_decode_list_kernel<lc3_cfg_any, 0>), grid, block, lc3_lds_pad(2), stream, lc3_cfg_slot<lc3_cfg_any>{h.slot},
+                                    d->d_states, d_list, n, pl, d_pcm, nbytes, n_frames);
+        }
+    } else if (mode == LC3_RECON_LATE)
         LC3_LAUNCH_CFG(lc3_decode_late_kernel, h, dim3((unsigned)((n + LC3_WG_WAVES - 1) / LC3_WG_WAVES)), dim3(64 * LC3_WG_WAVES), 0,
                        stream, d->d_states, first, n, (const int32_t *)planes, d_pcm, nbytes, n_frames, fresh, io);
     else
@@ -3466,8 +3760,8 @@ static int decode_launch(lc3gpu_decoder *d, const HostCfg &h, int first, int n, 
     // a reset that is only noted so far: a launch over ALL channels carries it out itself (its synthesis kernel starts from the constructed
     // state and stores what it leaves); any other launch needs the other channels' blobs initialised first
     int fresh = 0;
-    if (d->fresh_pending) {
-        if (first == 0 && n == d->num_channels && !d->mixed) fresh = 1;
+    if (d->fresh_count) {
+        if (first == 0 && n == d->num_channels && !d->mixed && d->fresh_count == d->num_channels) fresh = 1;
         else {
             const int rc0 = decoder_materialise(d);
             if (rc0) return rc0;
@@ -3515,7 +3809,7 @@ static int decode_launch(lc3gpu_decoder *d, const HostCfg &h, int first, int n, 
         if (fresh) (void)decoder_init_states(d);  // (some of the kernels may have run: leave the handle in a defined state)
         return rc;
     }
-    if (fresh) d->fresh_pending = false;
+    if (fresh) d->fresh_set_all(0);
     return d->order_end(stream, parts == 2);
 }
 
@@ -3531,6 +3825,39 @@ int lc3gpu_decode(lc3gpu_decoder *d, const uint8_t *d_in, const uint8_t *d_bad, 
     return lc3gpu_decode_layout(d, LC3GPU_LAYOUT_PLANAR, d_in, d_bad, d_pcm, nbytes, n_frames, stream);
 }
 
+// A list of channels (lc3_dev_list.h), as lc3gpu_encode_list: parser and reconstruction form as lc3gpu_decode picks them for a launch of
+// this size, on the compact buffers; the synthesis finds every stream's state through the list and starts the channels noted fresh from
+// the constructed state in the same launch (no materialising launch, no synchronisation).  Always one part.
+int lc3gpu_decode_list(lc3gpu_decoder *d, const int32_t *channels, int n_list, const uint8_t *d_in, const uint8_t *d_bad, int16_t *d_pcm,
+                       int nbytes, int n_frames, void *stream_) {
+    if (!d || d->mixed || n_list < 0) return LC3GPU_EINVAL;
+    if (nbytes < 1 || nbytes > LC3_MAX_NE || n_frames <= 0) return LC3GPU_ELENGTH;
+    if (n_list == 0) return LC3GPU_OK;
+    if (!channels || !d_in || !d_pcm || ((uintptr_t)d_pcm & 3u) != 0) return LC3GPU_EINVAL;
+    int rc = d->list_check(channels, n_list);
+    if (rc) return rc;
+    LC3_ON_DEVICE(d);
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t frames = (size_t)n_list * (size_t)n_frames;
+    const int mode = lc3_recon_mode(frames, n_frames);
+    rc = d->order_begin(stream);
+    if (rc == LC3GPU_OK) rc = decoder_reserve_planes(d, frames, stream);
+    if (rc == LC3GPU_OK && mode == LC3_RECON_WAVE) rc = lc3_tns_lds_optin();
+    if (rc == LC3GPU_OK) rc = d->list_upload(channels, n_list, d->fresh_mask, stream);
+    if (rc) return rc;
+    const lc3_io io = {0, nullptr};
+    const size_t t0 = d->timer.used;
+    d->timer.arm();
+    rc = decode_kernels(d, d->h, 0, n_list, d_in, d_bad, d_pcm, d->d_planes, nbytes, n_frames, io, mode, stream, 0, 0, d->d_list);
+    if (rc) {  // (the channels noted fresh stay noted: whatever ran, their next call starts them from the constructed state)
+        d->timer.rollback(t0);
+        (void)d->order_end(stream);
+        return rc;
+    }
+    for (int i = 0; i < n_list; i++) d->fresh_clear(channels[i]);
+    return d->order_end(stream);
+}
+
 // A frame size per frame on the decoder: the parser (one lane per frame), the reconstruction form lc3_recon_mode picks for the launch, the
 // synthesis.  Always one part (no LC3GPU_SPLIT), always the one-lane parser (no producer / consumer pair).
 int lc3gpu_decode_vbr(lc3gpu_decoder *d, const uint8_t *d_in, const uint16_t *d_nbytes, const uint8_t *d_bad, int16_t *d_pcm, int slot_bytes,
@@ -3543,7 +3870,11 @@ int lc3gpu_decode_vbr(lc3gpu_decoder *d, const uint8_t *d_in, const uint16_t *d_
     const HostCfg &h = d->h;
     const int n = d->num_channels;
     const size_t frames = (size_t)n * (size_t)n_frames;
-    const int fresh = d->fresh_pending ? 1 : 0;  // (a launch over every channel carries a noted reset out itself)
+    const int fresh = d->fresh_count == d->num_channels ? 1 : 0;  // (a launch over every channel carries a reset of ALL of them out itself)
+    if (!fresh && d->fresh_count) {
+        const int rc0 = decoder_materialise(d);
+        if (rc0) return rc0;
+    }
     int rc = d->order_begin(stream);
     if (rc == LC3GPU_OK) rc = decoder_reserve_planes(d, frames, stream);
     if (rc) return rc;
@@ -3601,7 +3932,7 @@ int lc3gpu_decode_vbr(lc3gpu_decoder *d, const uint8_t *d_in, const uint16_t *d_
         if (fresh) (void)decoder_init_states(d);
         return rc;
     }
-    if (fresh) d->fresh_pending = false;
+    if (fresh) d->fresh_set_all(0);
     return d->order_end(stream);
 }
 
@@ -3828,8 +4159,32 @@ int lc3gpu_decoder_state_load(lc3gpu_decoder *d, const void *host_src, size_t nb
     LC3_ON_DEVICE(d);
     HIP_TRY(hipDeviceSynchronize());  // a launch in flight would store its state over the loaded one
     const int rc = state_blobs_load(*d, d->d_states, LC3_STATE_MAGIC_DEC, 0, host_src, nbytes);
-    if (rc == LC3GPU_OK) d->fresh_pending = false;  // every channel now has the loaded state
+    if (rc == LC3GPU_OK) d->fresh_set_all(0);  // every channel now has the loaded state
     return rc;
+}
+
+int lc3gpu_decoder_state_save_channels(lc3gpu_decoder *d, const int32_t *channels, int n, void *host_dst, size_t nbytes) {
+    if (!d) return LC3GPU_EINVAL;
+    int rc = state_blobs_channels_args(*d, channels, n, host_dst, nbytes, lc3gpu_decoder_state_size(d));
+    if (rc) return rc;
+    LC3_ON_DEVICE(d);
+    HIP_TRY(hipDeviceSynchronize());
+    rc = decoder_materialise(d);
+    if (rc) return rc;
+    return state_blobs_save_channels(*d, d->d_states, LC3_STATE_MAGIC_DEC, 0, channels, n, host_dst);
+}
+
+int lc3gpu_decoder_state_load_channels(lc3gpu_decoder *d, const int32_t *channels, int n, const void *host_src, size_t nbytes) {
+    if (!d) return LC3GPU_EINVAL;
+    int rc = state_blobs_channels_args(*d, channels, n, host_src, nbytes, lc3gpu_decoder_state_size(d));
+    if (rc == LC3GPU_OK) rc = state_blobs_check_channels<lc3_dec_state>(*d, LC3_STATE_MAGIC_DEC, 0, channels, n, host_src);
+    if (rc) return rc;
+    LC3_ON_DEVICE(d);
+    HIP_TRY(hipDeviceSynchronize());  // a launch in flight would store its state over the loaded one
+    rc = state_blobs_load_channels(*d, d->d_states, channels, n, host_src);
+    if (rc) return rc;
+    for (int i = 0; i < n; i++) d->fresh_clear(d->internal_of_channel(channels[i]));  // these channels now have the loaded state
+    return LC3GPU_OK;
 }
 
 int lc3gpu_decoder_plc_events(lc3gpu_decoder *d, uint64_t *out) {

@@ -178,6 +178,21 @@ impl Lc3EncoderGpu {
                                     hip_stream: *mut c_void) -> i32 {
         lc3gpu_encode_vbr(self.h, d_pcm, d_out, d_nbytes, slot_bytes as i32, n_frames as i32, hip_stream)
     }
+    /// The caller's choice of channel per `encode_frame` call (examples/encode.rs:97-115) for many channels in one launch: item i of the
+    /// compact buffers holds the frames of channel `channels[i]` (any order, none twice); the other channels are left as they were.
+    ///
+    /// # Safety
+    /// `d_pcm` / `d_out` must be device allocations of [channels.len()][frame][nf] i16 / [channels.len()][frame][nbytes] u8 that outlive
+    /// the call's work; `channels` is host memory and free again when the call returns.
+    pub unsafe fn encode_list_device(&mut self, channels: &[i32], d_pcm: *const i16, d_out: *mut u8, nbytes: usize, n_frames: usize,
+                                     hip_stream: *mut c_void) -> i32 {
+        lc3gpu_encode_list(self.h, channels.as_ptr(), channels.len() as i32, d_pcm, d_out, nbytes as i32, n_frames as i32, hip_stream)
+    }
+    /// a new `EncoderChannel` for each named channel (from its next call on; no wait); the others are untouched
+    pub fn reset_channels(&mut self, channels: &[i32]) -> Result<(), i32> {
+        let rc = unsafe { lc3gpu_encoder_reset_channels(self.h, channels.as_ptr(), channels.len() as i32) };
+        if rc == 0 { Ok(()) } else { Err(rc) }
+    }
     /// frame sizes encode_vbr_device has clamped into [20, slot_bytes] (sticky)
     pub fn size_clamps(&mut self) -> Result<u64, i32> {
         let mut v: u64 = 0;
@@ -236,6 +251,21 @@ impl Lc3DecoderGpu {
     pub unsafe fn decode_vbr_device(&mut self, d_in: *const u8, d_nbytes: *const u16, d_bad_frame: *const u8, d_pcm: *mut i16, slot_bytes: usize,
                                     n_frames: usize, hip_stream: *mut c_void) -> i32 {
         lc3gpu_decode_vbr(self.h, d_in, d_nbytes, d_bad_frame, d_pcm, slot_bytes as i32, n_frames as i32, hip_stream)
+    }
+    /// The caller's choice of channel per `decode_frame` call (examples/decode.rs:93-112) for many channels in one launch: item i of the
+    /// compact buffers holds the frames of channel `channels[i]` (any order, none twice); the other channels keep state and PLC count.
+    ///
+    /// # Safety
+    /// device allocations of [channels.len()][frame][nbytes] u8, [channels.len()][frame] u8 flags or null, [channels.len()][frame][nf] i16
+    /// that outlive the call's work; `channels` is host memory and free again when the call returns.
+    pub unsafe fn decode_list_device(&mut self, channels: &[i32], d_in: *const u8, d_bad_frame: *const u8, d_pcm: *mut i16, nbytes: usize,
+                                     n_frames: usize, hip_stream: *mut c_void) -> i32 {
+        lc3gpu_decode_list(self.h, channels.as_ptr(), channels.len() as i32, d_in, d_bad_frame, d_pcm, nbytes as i32, n_frames as i32, hip_stream)
+    }
+    /// a new `DecoderChannel` for each named channel (from its next call on; no wait; its PLC count goes to zero)
+    pub fn reset_channels(&mut self, channels: &[i32]) -> Result<(), i32> {
+        let rc = unsafe { lc3gpu_decoder_reset_channels(self.h, channels.as_ptr(), channels.len() as i32) };
+        if rc == 0 { Ok(()) } else { Err(rc) }
     }
     /// frames concealed so far (decoder/packet_loss_concealment.rs:63-85)
     pub fn plc_events(&mut self) -> u64 {
