@@ -129,8 +129,9 @@ int lc3gpu_encode_range(lc3gpu_encoder *enc, int first_channel, int n_channels, 
  * a handle; a list 0 .. num_channels-1 gives the bytes of lc3gpu_encode, a contiguous ascending run those of lc3gpu_encode_range.  Channels
  * reset by lc3gpu_encoder_reset_channels start from the constructed state inside the same launch as the carried ones.  Asynchronous on
  * hip_stream, ordered after the handle's earlier work.
- * NOT provided (out of scope): lists on mixed handles, with the interleaved layout, with a frame size per frame (lc3gpu_*_vbr), on the
- * host-resident calls (lc3gpu_*_host) and in the pipeline object. */
+ * NOT provided (out of scope): lists on mixed handles (they have calls of their own: lc3gpu_encode_mixed_list / lc3gpu_decode_mixed_list),
+ * with the interleaved layout, with a frame size per frame (lc3gpu_*_vbr), on the host-resident calls (lc3gpu_*_host) and in the pipeline
+ * object. */
 int lc3gpu_encode_list(lc3gpu_encoder *enc, const int32_t *channels, int n_list, const int16_t *d_pcm, uint8_t *d_out, int nbytes,
                        int n_frames, void *hip_stream);
 /* The named channels (HOST int32[n]) are back in the freshly constructed state from their next call on -- the reference builds a new
@@ -169,6 +170,28 @@ int lc3gpu_encoder_size_clamps(lc3gpu_encoder *enc, uint64_t *out);
 int lc3gpu_encoder_create_mixed(lc3gpu_encoder **out, int n_streams, const lc3gpu_stream_desc *descs);
 int lc3gpu_encoder_create_mixed_spec(lc3gpu_encoder **out, int n_streams, const lc3gpu_stream_desc *descs, int spec_flags);
 int lc3gpu_encode_mixed(lc3gpu_encoder *enc, const int16_t *d_pcm, uint8_t *d_out, int n_frames, void *hip_stream);
+/* Batch over a LIST of a mixed handle's streams: the contract of lc3gpu_encode_list carried over to the mixed handle's buffers.  A server
+ * that holds 7.5 ms and 10 ms streams side by side cannot advance them by the same number of frames per call (four 7.5 ms frames fall into
+ * the 30 ms of three 10 ms frames): every tick it names the streams that are due, of any configurations, and gets ONE launch per kernel.
+ *   channels  HOST int32[n_list]: entry i is a descriptor index (the mixed handle's channel index); any order, no channel twice.  The array
+ *             may be reused as soon as the call returns (pinned copy of the handle's own, sent in stream order: no host synchronisation)
+ *   d_pcm     DEVICE, ragged and compact IN LIST ORDER -- the layout of lc3gpu_encode_mixed with the call's list in place of the descriptor
+ *             list: item i at element offset n_frames * sum_{j<i} nf(channels[j]), int16[n_frames][nf_i]; 4-byte aligned base
+ *   d_out     DEVICE: item i at byte offset n_frames * sum_{j<i} nbytes(channels[j]), uint8[n_frames][nbytes_i]; every stream is encoded
+ *             at the frame size of its descriptor (no nbytes argument)
+ * Checked on the host before anything is queued: an index outside [0, n_streams) or named twice: LC3GPU_ECHANNEL; null pointers, a negative
+ * n_list, misaligned PCM, a UNIFORM handle: LC3GPU_EINVAL; n_frames <= 0: LC3GPU_ELENGTH.  A call that returns an error has launched nothing,
+ * written nothing and changed no channel; n_list = 0 launches nothing and returns LC3GPU_OK.  A bound handle takes the call on its bound
+ * stream only; LC3GPU_EPAIR as for the other batch calls.  Every listed channel advances by n_frames frames exactly as under
+ * lc3gpu_encode_mixed; every channel not listed keeps its state blob byte for byte.  Channels reset by lc3gpu_encoder_reset_channels start
+ * from the constructed state inside the same launch as the carried ones (no extra launch).  Mixed-list, lc3gpu_encode_mixed and *_frame
+ * calls may alternate on a handle; a list 0 .. n_streams-1 gives the bytes of lc3gpu_encode_mixed.  Groups of the handle without a listed
+ * stream take no workgroups.  8 kHz streams: refused at encoder creation as ever, allowed on the decoder.  Asynchronous on hip_stream,
+ * ordered after the handle's earlier work.
+ * NOT provided by the mixed-list calls (out of scope): the interleaved layout, a frame size per frame (lc3gpu_*_vbr), the host-resident
+ * calls (lc3gpu_*_host), the pipeline object, and a frame count per listed channel (n_frames holds for every item of a call). */
+int lc3gpu_encode_mixed_list(lc3gpu_encoder *enc, const int32_t *channels, int n_list, const int16_t *d_pcm, uint8_t *d_out, int n_frames,
+                             void *hip_stream);
 
 /* per-channel state blobs (checkpoint / CPU cross-checks): size per channel, device->host copy, host->device.
  * nbytes must equal state_size * num_channels (LC3GPU_ELENGTH otherwise); both calls synchronise the device.  A channel's blob
@@ -277,6 +300,13 @@ int lc3gpu_decode_layout(lc3gpu_decoder *dec, int layout, const uint8_t *d_in, c
 int lc3gpu_decoder_create_mixed(lc3gpu_decoder **out, int n_streams, const lc3gpu_stream_desc *descs);
 int lc3gpu_decode_mixed(lc3gpu_decoder *dec, const uint8_t *d_in, const uint8_t *d_bad_frame, int16_t *d_pcm, int n_frames,
                         void *hip_stream);
+/* Batch decode over a LIST of a mixed handle's streams: the contract of lc3gpu_encode_mixed_list (which see: host list of descriptor
+ * indices, ragged device buffers compact in list order, host-side checks, what is out of scope) with d_in like that call's d_out, d_pcm like
+ * its d_pcm and d_bad_frame uint8[n_list][n_frames] in list order or NULL.  Channels not listed keep their state and their PLC count;
+ * channels reset by lc3gpu_decoder_reset_channels start from the constructed state inside the same launch, without the device
+ * synchronisation lc3gpu_decode_mixed spends on materialising them. */
+int lc3gpu_decode_mixed_list(lc3gpu_decoder *dec, const int32_t *channels, int n_list, const uint8_t *d_in, const uint8_t *d_bad_frame,
+                             int16_t *d_pcm, int n_frames, void *hip_stream);
 
 size_t lc3gpu_decoder_state_size(const lc3gpu_decoder *dec);
 int lc3gpu_decoder_state_save(lc3gpu_decoder *dec, void *host_dst, size_t nbytes);

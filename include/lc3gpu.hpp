@@ -73,6 +73,12 @@ public:
         int rc = lc3gpu_encode_list(h_, channels.data(), (int)channels.size(), d_pcm, d_out, nbytes, n_frames, hip_stream);
         if (rc) throw Error(rc, "encode_list");
     }
+    // mixed handle: a list of its streams (HOST descriptor indices, any order, none twice); ragged DEVICE buffers compact in LIST order,
+    // every stream at its descriptor's frame size; the streams not listed are left as they were
+    void encode_mixed_list(const std::vector<int32_t> &channels, const int16_t *d_pcm, uint8_t *d_out, int n_frames, void *hip_stream = nullptr) {
+        int rc = lc3gpu_encode_mixed_list(h_, channels.data(), (int)channels.size(), d_pcm, d_out, n_frames, hip_stream);
+        if (rc) throw Error(rc, "encode_mixed_list");
+    }
     // back to the freshly constructed state from the next call on: every channel, or the named ones (a new EncoderChannel); no wait
     void reset() {
         int rc = lc3gpu_encoder_reset(h_);
@@ -151,6 +157,12 @@ public:
                      const uint8_t *d_bad_frame = nullptr) {
         int rc = lc3gpu_decode_list(h_, channels.data(), (int)channels.size(), d_in, d_bad_frame, d_pcm, nbytes, n_frames, hip_stream);
         if (rc) throw Error(rc, "decode_list");
+    }
+    // mixed handle: a list of its streams, buffers (and flags) compact in LIST order; the streams not listed keep state and PLC count
+    void decode_mixed_list(const std::vector<int32_t> &channels, const uint8_t *d_in, int16_t *d_pcm, int n_frames, void *hip_stream = nullptr,
+                           const uint8_t *d_bad_frame = nullptr) {
+        int rc = lc3gpu_decode_mixed_list(h_, channels.data(), (int)channels.size(), d_in, d_bad_frame, d_pcm, n_frames, hip_stream);
+        if (rc) throw Error(rc, "decode_mixed_list");
     }
     // every channel, or the named ones (a new DecoderChannel; their PLC counts go to zero); no wait
     void reset() {

@@ -250,6 +250,8 @@ def load_library():
     L.lc3gpu_encode_vbr.argtypes = [vp, vp, vp, vp, i, i, vp]
     L.lc3gpu_encode_list.argtypes = [vp, vp, i, vp, vp, i, i, vp]
     L.lc3gpu_decode_list.argtypes = [vp, vp, i, vp, vp, vp, i, i, vp]
+    L.lc3gpu_encode_mixed_list.argtypes = [vp, vp, i, vp, vp, i, vp]
+    L.lc3gpu_decode_mixed_list.argtypes = [vp, vp, i, vp, vp, vp, i, vp]
     L.lc3gpu_encoder_reset_channels.argtypes = [vp, vp, i]
     L.lc3gpu_decoder_reset_channels.argtypes = [vp, vp, i]
     L.lc3gpu_encoder_state_save_channels.argtypes = [vp, vp, i, vp, ctypes.c_size_t]
@@ -340,7 +342,7 @@ ABI_SYMBOLS = [
     "lc3gpu_pipeline_groups", "lc3gpu_pipeline_group", "lc3gpu_pipeline_last_hip_error", "lc3gpu_encode_vbr", "lc3gpu_encoder_size_clamps", "lc3gpu_decode_vbr",
     "lc3gpu_inspect", "lc3gpu_encode_list", "lc3gpu_decode_list", "lc3gpu_encoder_reset_channels", "lc3gpu_decoder_reset_channels",
     "lc3gpu_encoder_state_save_channels", "lc3gpu_encoder_state_load_channels", "lc3gpu_decoder_state_save_channels",
-    "lc3gpu_decoder_state_load_channels",
+    "lc3gpu_decoder_state_load_channels", "lc3gpu_encode_mixed_list", "lc3gpu_decode_mixed_list",
 ]
 
 # LC3GPU_SPEC_*: opt-in corrections of the reference's deviations from the LC3 specification (default 0 = reference behaviour)
@@ -611,6 +613,15 @@ class Lc3Encoder:
         if rc:
             raise Lc3EncoderError(rc, "encode_list")
 
+    def encode_mixed_list(self, channels, d_pcm, d_out, n_frames, stream=None):
+        """a mixed handle's batch over a list of its streams (HOST descriptor indices, any order, none twice): ragged DEVICE buffers, compact
+        in LIST order, as encode_mixed's with the list in place of the descriptor list; every stream at its descriptor's frame size; the
+        streams not listed are left as they were.  One launch per kernel; asynchronous on `stream` (lc3gpu_encode_mixed_list)"""
+        ch = _channel_list(channels)
+        rc = self._L.lc3gpu_encode_mixed_list(self._h, _ptr(ch), int(ch.size), _ptr(d_pcm), _ptr(d_out), int(n_frames), _ptr(stream))
+        if rc:
+            raise Lc3EncoderError(rc, "encode_mixed_list")
+
     def reset(self, channels=None):
         """every channel (channels=None) or the named ones back to the freshly constructed state from their next call on; no wait"""
         if channels is None:
@@ -835,6 +846,16 @@ class Lc3Decoder:
                                         _ptr(stream))
         if rc:
             raise Lc3DecoderError(rc, "decode_list")
+
+    def decode_mixed_list(self, channels, d_in, d_pcm, n_frames, stream=None, d_bad_frame=None):
+        """a mixed handle's batch over a list of its streams (HOST descriptor indices, any order, none twice): ragged DEVICE buffers,
+        compact in LIST order, as decode_mixed's with the list in place of the descriptor list (flags uint8[len(channels)][T]); the streams
+        not listed keep their state and PLC count.  One launch per kernel; asynchronous on `stream` (lc3gpu_decode_mixed_list)"""
+        ch = _channel_list(channels)
+        rc = self._L.lc3gpu_decode_mixed_list(self._h, _ptr(ch), int(ch.size), _ptr(d_in), _ptr(d_bad_frame), _ptr(d_pcm), int(n_frames),
+                                              _ptr(stream))
+        if rc:
+            raise Lc3DecoderError(rc, "decode_mixed_list")
 
     def reset(self, channels=None):
         """every channel (channels=None) or the named ones back to the freshly constructed state (PLC count 0) from their next call on; no wait"""

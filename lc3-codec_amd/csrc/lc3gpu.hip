@@ -63,6 +63,14 @@
 #else
 #define LC3_MIXED_LAUNCH(name) name
 #endif
+// the twins of the wave-per-stream mixed kernels for a LIST of a mixed handle's streams (lc3gpu_*_mixed_list): beside <name>_all in the
+// per-kernel units of a multi-unit library, in the whole-source build as every other kernel; the main unit of a multi-unit library does
+// not compile them at all (it launches <name>_all), so its module -- and the register allocation of its tuned kernels -- is what it was.
+// The two analysis twins sit in their twins' units (0, 1).  The two synthesis twins sit in the unit of the wave-per-frame reconstruction
+// (4), the shortest one, whose copy of the device-filled tables is already a real one: beside lc3_decode_mixed_kernel_all /
+// lc3_decode_mixed_late_kernel_all (6, 7) they moved the spill counts of those kernels' run-time-view body by one or two registers, and
+// an existing kernel is to compile as it did
+#define LC3_IN_MIXED_LIST_TU(k) (!LC3_MULTI_TU || (LC3_TU_KIND == 2 && LC3_TU_INDEX == (k)))
 #define LC3_CAT_(a, b) a##b
 #define LC3_CAT(a, b) LC3_CAT_(a, b)
 
@@ -550,13 +558,11 @@ LC3_TU_STATIC __device__ unsigned long long lc3_prof_acc[64];  // 0..31 stage su
 //                reference's callers convert from and to on the host (examples/encode.rs:95-115, examples/decode.rs:86-112)
 //   ragged       a mixed-configuration handle: stream i's PCM at element T * tab[i].pcm_off1, its bytes at T * tab[i].byte_off1,
 //                its flags at tab[i].flag_idx * T (the streams in the caller's order, each planar)
-struct lc3_stream_io {
-    long long pcm_off1, byte_off1;  // per frame of the batch: sum of nf / of nbytes over the caller's earlier streams
-    int flag_idx, pad;              // the stream's index in the caller's order
-};
+// (lc3_stream_io and the group tables of a mixed launch: lc3_host_mixed_list.h, shared with the host-side plan of a list call)
+#include "lc3_host_mixed_list.h"
 struct lc3_io {
     int ilv;
-    const lc3_stream_io *tab;  // indexed by the handle's internal stream index (first_channel + s)
+    const lc3_stream_io *tab;  // indexed by the handle's internal stream index (first_channel + s); a list call: by launch position
 };
 __device__ __forceinline__ const int16_t *lc3_io_pcm(const lc3_io &io, const int16_t *pcm, int nf, int first, int s, int t, int T,
                                                      int *stride) {
@@ -588,20 +594,22 @@ __device__ __forceinline__ size_t lc3_io_flag_idx(const lc3_io &io, int first, s
         default: BODY<lc3_cfg_any>(lc3_cfg_slot<lc3_cfg_any>{(g).slot}, __VA_ARGS__); break; \
         }                                                                                    \
     } while (0)
+// The same dispatch for the list twins.  In a unit of their own every standard configuration has its compile-time view (lc3_cfg_views.h:
+// twelve views, twelve configurations), so the run-time view's body -- 25 spilled vector registers in the synthesis twins -- is left out;
+// the host refuses a group without a view there (mixed_list_views_ok).  The whole-source build carries it for the other eight.
+#if LC3_TU_KIND == 2
+#define LC3_GROUP_VIEW_LIST(BODY, g, ...)               \
+    do {                                                \
+        switch ((g).fixed) {                            \
+            LC3_VIEW_CASES(BODY, (g).slot, __VA_ARGS__) \
+        default: break;                                 \
+        }                                               \
+    } while (0)
+#else
+#define LC3_GROUP_VIEW_LIST(BODY, g, ...) LC3_GROUP_VIEW(BODY, g, __VA_ARGS__)
+#endif
 // A mixed-configuration handle keeps its streams sorted by configuration; a "group" is one run of streams of equal
 // (rate, duration, frame bytes).  Every kernel of a mixed batch is ONE launch: a workgroup finds its group from its index.
-#define LC3_MAX_GROUPS 24
-struct lc3_group {
-    int slot, fixed;              // configuration slot; the compile-time view that applies (lc3_cfg_views.h: 1..4), 0 = the run-time view
-    int first_stream, n_streams;  // [first_stream, first_stream + n_streams) in the handle's internal order
-    int wg_stream, wg_frame;      // the group's first workgroup in a stream-kernel / frame-kernel launch
-    int nbytes, ne, nb, pad;
-    long long frame_base;         // first plane column of the group
-};
-struct lc3_groups {
-    int n, pad;
-    lc3_group g[LC3_MAX_GROUPS];
-};
 __device__ __forceinline__ int lc3_find_group(const lc3_groups &G, unsigned wg, int frame_kernel) {
     int gi = 0;
     while (gi + 1 < G.n && wg >= (unsigned)(frame_kernel ? G.g[gi + 1].wg_frame : G.g[gi + 1].wg_stream)) gi++;
@@ -701,6 +709,60 @@ __global__ __launch_bounds__(64 * LC3_WG_WAVES, LC3_FRONT_WAVES) void lc3_enc_fr
                                                                                    int n_frames, int fresh, lc3_io io, int spec_flags);
 #endif
 
+// ---- a list of a mixed handle's streams (lc3gpu_encode_mixed_list / lc3gpu_decode_mixed_list; lc3_dev_list.h, lc3_host_mixed_list.h) -----
+// The mixed kernel's group dispatch around the stream bodies of the list kernels.  G, entries and io.tab are PER CALL and indexed by LAUNCH
+// POSITION (the list bucketed by group, stable): position p's state is states[entry p & 0x7fffffff] (the handle's internal index), it starts
+// fresh when bit 31 of entry p says so, its PCM is at pcm + n_frames * tab[p].pcm_off1 (compact in the caller's list order), its plane
+// columns are [p * n_frames, (p + 1) * n_frames).  Entry and table row are read by scalar loads through the constant address space (the
+// copy that wrote them precedes the launch in stream order; a vector load at a uniform address cost the list synthesis kernel 9 %).
+// Barrier rule: a workgroup belongs to ONE group, so its four streams share configuration and frame size and meet at every workgroup
+// barrier -- table staging, the gathered LTPF blocks -- in step; they may differ in FRESHNESS, and the rule of lc3_dev_list.h applies
+// unchanged: the per-stream branch (state init / load, the ring rule of the synthesis) holds wave-level fences only, nothing after it
+// branches on freshness, and the hooks that hold a workgroup barrier run for every wave outside that branch.
+// Partial workgroups: every group's LAST workgroup may be partial, so shadow waves (valid = 0) sit in the MIDDLE of the grid.  A shadow wave
+// repeats the last listed stream of ITS OWN group (pos < first_stream + n_streams: it reads that stream's state, PCM and columns, never
+// another group's) and stores nothing: no plane column, no PCM, no state.
+__device__ __forceinline__ long long lc3_mlist_off(const long long *field) {  // one 64-bit table field, wave-uniform, by scalar loads
+    const int lo = lc3_list_entry((const int32_t *)field, 0), hi = lc3_list_entry((const int32_t *)field, 1);
+    return (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned long long)(unsigned)lo);
+}
+template <class CV>
+__device__ __forceinline__ void lc3_enc_front_body_mixed_list(lc3_cfg_slot<CV> cfg, unsigned wg, lc3_enc_state *states, const int32_t *entries,
+                                                              int first_pos, int n_streams, const int16_t *pcm, float *mid, int32_t *planes,
+                                                              int nbytes, int n_frames, const lc3_stream_io *tab, int spec_flags) {
+    const int lane = threadIdx.x & 63, wave = LC3_WAVE_ID();
+    lc3_enc_lds &L = lc3_enc_wg[wave];
+    const int s_raw = (int)wg * LC3_WG_WAVES + wave;
+    const int valid = s_raw < n_streams;
+    const int s = valid ? s_raw : n_streams - 1;  // (a shadow wave stays inside its own group)
+    typename CV::bind_t c0 = CV::bind(lc3_cfg_table[cfg.id]);
+    const int entry = lc3_list_entry(entries, first_pos + s);
+    lc3_enc_state *gst = states + (size_t)lc3_list_channel(entry);
+    const int16_t *pcm_s = pcm + (size_t)n_frames * (size_t)lc3_mlist_off(&tab[first_pos + s].pcm_off1);
+#ifndef LC3_TABLES_IN_GLOBAL
+    lc3_front_tables_stage_image(c0.stage_image);
+    lc3_fft_tables_stage_image(c0.stage_image);  // ends with the workgroup barrier
+#endif
+    lc3_list_front_stream(cfg, L, lane, gst, lc3_list_fresh(entry), valid, pcm_s, mid, planes, (size_t)s * (size_t)n_frames, nbytes, n_frames,
+                          spec_flags, 1);  // (the LTPF stage outlined, as in lc3_enc_front_body_mixed)
+}
+#if LC3_IN_MIXED_LIST_TU(0)
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, LC3_FRONT_WAVES) void LC3_MIXED_KERNEL(lc3_enc_front_mixed_list_kernel)(
+    lc3_groups G, lc3_enc_state *states, const int32_t *entries, const int16_t *pcm, float *mid, int32_t *planes, int n_frames, lc3_io io,
+    int spec_flags) {
+    const lc3_group &g = G.g[lc3_find_group(G, blockIdx.x, 0)];
+    float *m = mid + (size_t)g.frame_base * (size_t)MP_WORDS;
+    int32_t *p = planes + (size_t)g.frame_base * (size_t)EP_WORDS;
+    LC3_GROUP_VIEW_LIST(lc3_enc_front_body_mixed_list, g, blockIdx.x - g.wg_stream, states, entries, g.first_stream, g.n_streams, pcm, m, p, g.nbytes,
+                        n_frames, io.tab, spec_flags);
+}
+#endif
+#if LC3_MULTI_TU && LC3_TU_KIND == 0
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, LC3_FRONT_WAVES) void lc3_enc_front_mixed_list_kernel_all(
+    lc3_groups G, lc3_enc_state *states, const int32_t *entries, const int16_t *pcm, float *mid, int32_t *planes, int n_frames, lc3_io io,
+    int spec_flags);
+#endif
+
 // SNS vector quantiser, one LANE per frame (lc3_dev_enc_vq.h): 16 targets -> indices (packer plane) + 64 band gains.
 __device__ __forceinline__ void lc3_sns_vq_body(unsigned wg, int nb, float *mid, int32_t *planes, int n_frames, int spec_flags) {
     LC3_LANE_KERNEL_BEGIN();
@@ -786,6 +848,43 @@ __global__ __launch_bounds__(64 * LC3_WG_WAVES, LC3_BACK_WAVES) void LC3_MIXED_K
 __global__ __launch_bounds__(64 * LC3_WG_WAVES, LC3_BACK_WAVES) void lc3_enc_back_mixed_kernel_all(lc3_groups G, lc3_enc_state *states,
                                                                                                 const float *mid, int32_t *planes,
                                                                                                 int n_frames, int spec_flags);
+#endif
+
+// the back half over a list of a mixed handle's streams (see lc3_enc_front_mixed_list_kernel)
+template <class CV>
+__device__ __forceinline__ void lc3_enc_back_body_mixed_list(lc3_cfg_slot<CV> cfg, unsigned wg, lc3_enc_state *states, const int32_t *entries,
+                                                             int first_pos, int n_streams, const float *mid, int32_t *planes, int nbytes,
+                                                             int n_frames, int spec_flags) {
+    const int lane = threadIdx.x & 63, wave = LC3_WAVE_ID();
+    lc3_enc_lds &L = lc3_enc_wg[wave];
+    const int s_raw = (int)wg * LC3_WG_WAVES + wave;
+    const int valid = s_raw < n_streams;
+    const int s = valid ? s_raw : n_streams - 1;
+    lc3_enc_state *gst = states + (size_t)lc3_list_channel(lc3_list_entry(entries, first_pos + s));
+#if LC3_SPEC_IN_LDS
+    {   // spectral-model tables -> LDS, once per workgroup
+        const uint32_t *lk = (const uint32_t *)LC3T_AC_SPEC_LOOKUP, *bt = (const uint32_t *)&LC3T_AC_SPEC_BITS[0][0];
+        uint32_t *dl = (uint32_t *)lc3_spec_tab.lookup, *db = (uint32_t *)lc3_spec_tab.bits;
+        for (int i = threadIdx.x; i < 1024; i += 64 * LC3_WG_WAVES) dl[i] = lk[i];
+        for (int i = threadIdx.x; i < 64 * 17 / 2; i += 64 * LC3_WG_WAVES) db[i] = bt[i];
+        __syncthreads();
+    }
+#endif
+    lc3_list_back_stream(cfg, L, lane, gst, valid, mid, planes, (size_t)s * (size_t)n_frames, nbytes, n_frames, spec_flags);
+}
+#if LC3_IN_MIXED_LIST_TU(1)
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, LC3_BACK_WAVES) void LC3_MIXED_KERNEL(lc3_enc_back_mixed_list_kernel)(
+    lc3_groups G, lc3_enc_state *states, const int32_t *entries, const float *mid, int32_t *planes, int n_frames, int spec_flags) {
+    const lc3_group &g = G.g[lc3_find_group(G, blockIdx.x, 0)];
+    const float *m = mid + (size_t)g.frame_base * (size_t)MP_WORDS;
+    int32_t *p = planes + (size_t)g.frame_base * (size_t)EP_WORDS;
+    LC3_GROUP_VIEW_LIST(lc3_enc_back_body_mixed_list, g, blockIdx.x - g.wg_stream, states, entries, g.first_stream, g.n_streams, m, p, g.nbytes, n_frames,
+                        spec_flags);
+}
+#endif
+#if LC3_MULTI_TU && LC3_TU_KIND == 0
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, LC3_BACK_WAVES) void lc3_enc_back_mixed_list_kernel_all(
+    lc3_groups G, lc3_enc_state *states, const int32_t *entries, const float *mid, int32_t *planes, int n_frames, int spec_flags);
 #endif
 
 // Bitstream packer, one LANE per frame (lc3_dev_enc_pack.h).  blockDim.x frames per workgroup; context lookup and the
@@ -1622,6 +1721,69 @@ __global__ __launch_bounds__(64 * LC3_WG_WAVES, 4) void lc3_decode_mixed_late_ke
                                                                                      int fresh, lc3_io io);
 #endif
 
+// the synthesis over a list of a mixed handle's streams, in its lane and late reconstruction forms (see lc3_enc_front_mixed_list_kernel)
+template <class CV, int LATE>
+__device__ __forceinline__ void lc3_decode_body_mixed_list(lc3_cfg_slot<CV> cfg, unsigned wg, lc3_dec_state *states, const int32_t *entries,
+                                                           int first_pos, int n_streams, const int32_t *planes, int16_t *pcm, int nbytes,
+                                                           int n_frames, const lc3_stream_io *tab) {
+    const int lane = threadIdx.x & 63, wave = LC3_WAVE_ID();
+    lc3_dec_lds &L = lc3_dec_wg[wave];
+    const int s_raw = (int)wg * LC3_WG_WAVES + wave;
+    const int valid = s_raw < n_streams;
+    const int s = valid ? s_raw : n_streams - 1;  // (a shadow wave stays inside its own group)
+    typename CV::bind_t c0 = CV::bind(lc3_cfg_table[cfg.id]);
+    const int entry = lc3_list_entry(entries, first_pos + s);
+    lc3_dec_state *gst = states + (size_t)lc3_list_channel(entry);
+    int16_t *pcm_s = pcm + (size_t)n_frames * (size_t)lc3_mlist_off(&tab[first_pos + s].pcm_off1);
+#ifndef LC3_TABLES_IN_GLOBAL
+    const lc3_fft_image_regs tab_regs = lc3_fft_tables_image_issue(c0.stage_image);
+#endif
+    lc3_list_synth_stream(cfg, L, lane, gst, lc3_list_fresh(entry), valid, nbytes, planes, (size_t)s * (size_t)n_frames, n_frames, pcm_s, LATE, [&]() {
+#ifndef LC3_TABLES_IN_GLOBAL
+        lc3_fft_tables_image_commit(tab_regs);
+#endif
+    });
+}
+template <class CV>
+__device__ __forceinline__ void lc3_decode_body_mixed_list_now(lc3_cfg_slot<CV> cfg, unsigned wg, lc3_dec_state *states, const int32_t *entries,
+                                                               int first_pos, int n_streams, const int32_t *planes, int16_t *pcm, int nbytes,
+                                                               int n_frames, const lc3_stream_io *tab) {
+    lc3_decode_body_mixed_list<CV, 0>(cfg, wg, states, entries, first_pos, n_streams, planes, pcm, nbytes, n_frames, tab);
+}
+template <class CV>
+__device__ __forceinline__ void lc3_decode_body_mixed_list_late(lc3_cfg_slot<CV> cfg, unsigned wg, lc3_dec_state *states, const int32_t *entries,
+                                                                int first_pos, int n_streams, const int32_t *planes, int16_t *pcm, int nbytes,
+                                                                int n_frames, const lc3_stream_io *tab) {
+    lc3_decode_body_mixed_list<CV, 1>(cfg, wg, states, entries, first_pos, n_streams, planes, pcm, nbytes, n_frames, tab);
+}
+#if LC3_IN_MIXED_LIST_TU(4)  // (not beside its twin: see LC3_IN_MIXED_LIST_TU)
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, 4) void LC3_MIXED_KERNEL(lc3_decode_mixed_list_kernel)(lc3_groups G, lc3_dec_state *states,
+                                                                                     const int32_t *entries, const int32_t *planes,
+                                                                                     int16_t *pcm, int n_frames, lc3_io io) {
+    const lc3_group &g = G.g[lc3_find_group(G, blockIdx.x, 0)];
+    const int32_t *p = planes + (size_t)g.frame_base * (size_t)LC3_PLANE_WORDS;
+    LC3_GROUP_VIEW_LIST(lc3_decode_body_mixed_list_now, g, blockIdx.x - g.wg_stream, states, entries, g.first_stream, g.n_streams, p, pcm, g.nbytes,
+                        n_frames, io.tab);
+}
+#endif
+#if LC3_IN_MIXED_LIST_TU(4)
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, 4) void LC3_MIXED_KERNEL(lc3_decode_mixed_list_late_kernel)(lc3_groups G, lc3_dec_state *states,
+                                                                                          const int32_t *entries, const int32_t *planes,
+                                                                                          int16_t *pcm, int n_frames, lc3_io io) {
+    const lc3_group &g = G.g[lc3_find_group(G, blockIdx.x, 0)];
+    const int32_t *p = planes + (size_t)g.frame_base * (size_t)LC3_PLANE_WORDS;
+    LC3_GROUP_VIEW_LIST(lc3_decode_body_mixed_list_late, g, blockIdx.x - g.wg_stream, states, entries, g.first_stream, g.n_streams, p, pcm, g.nbytes,
+                        n_frames, io.tab);
+}
+#endif
+#if LC3_MULTI_TU && LC3_TU_KIND == 0
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, 4) void lc3_decode_mixed_list_kernel_all(lc3_groups G, lc3_dec_state *states, const int32_t *entries,
+                                                                                     const int32_t *planes, int16_t *pcm, int n_frames, lc3_io io);
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, 4) void lc3_decode_mixed_list_late_kernel_all(lc3_groups G, lc3_dec_state *states,
+                                                                                          const int32_t *entries, const int32_t *planes,
+                                                                                          int16_t *pcm, int n_frames, lc3_io io);
+#endif
+
 // ---------------------------------------------------------------------------------------------
 // per translation unit: the unit's kernels, its copy of the tables
 // ---------------------------------------------------------------------------------------------
@@ -2443,12 +2605,67 @@ struct HandleCommon {
         list_next = (k + 1) % LC3_LIST_SLOTS;
         return LC3GPU_OK;
     }
+    // The plan of a list call on a MIXED handle (lc3gpu_*_mixed_list; lc3_host_mixed_list.h): entries int32[n] and, 8-byte aligned behind
+    // them, the per-call lc3_stream_io table [n], both in launch order, built straight into a pinned slot and sent by ONE asynchronous copy
+    // on the call's stream in front of the kernels -- the uniform list's scheme (list_upload) with 24 bytes more per item
+    uint8_t *h_mlist[LC3_LIST_SLOTS] = {}, *d_mlist = nullptr;
+    hipEvent_t mlist_ev[LC3_LIST_SLOTS] = {};
+    bool mlist_busy[LC3_LIST_SLOTS] = {};
+    int mlist_next = 0;
+    std::vector<lc3_mlist_group> mlist_groups;    // per group of the handle
+    std::vector<lc3_mlist_stream> mlist_streams;  // per caller stream
+    static size_t mlist_tab_offset(int n) { return (sizeof(int32_t) * (size_t)n + 7) & ~(size_t)7; }
+    // a free pinned slot (waits for the copy that read it LC3_LIST_SLOTS calls ago, long done in any steady state)
+    int mlist_slot(uint8_t **slot) {
+        if (!d_mlist) {
+            const size_t bytes = mlist_tab_offset(num_channels) + sizeof(lc3_stream_io) * (size_t)num_channels;
+            HIP_TRY(hipMalloc((void **)&d_mlist, bytes));
+            for (int i = 0; i < LC3_LIST_SLOTS; i++) {
+                HIP_TRY(hipHostMalloc((void **)&h_mlist[i], bytes, hipHostMallocDefault));
+                HIP_TRY(hipEventCreateWithFlags(&mlist_ev[i], hipEventDisableTiming));
+            }
+            mlist_groups.resize(groups.size());
+            for (size_t g = 0; g < groups.size(); g++)
+                mlist_groups[g] = {groups[g].h.slot, groups[g].h.view, groups[g].nbytes, groups[g].h.c.ne, groups[g].h.c.nb, groups[g].h.c.nf};
+            mlist_streams.resize(streams.size());
+            for (size_t i = 0; i < streams.size(); i++) mlist_streams[i] = {streams[i].group, streams[i].internal};
+        }
+        const int k = mlist_next;
+        if (mlist_busy[k]) HIP_TRY(hipEventSynchronize(mlist_ev[k]));
+        mlist_busy[k] = false;
+        *slot = h_mlist[k];
+        return LC3GPU_OK;
+    }
+    int mlist_upload(int n, hipStream_t s) {
+        const int k = mlist_next;
+        HIP_TRY(hipMemcpyAsync(d_mlist, h_mlist[k], mlist_tab_offset(n) + sizeof(lc3_stream_io) * (size_t)n, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(mlist_ev[k], s));
+        mlist_busy[k] = true;
+        mlist_next = (k + 1) % LC3_LIST_SLOTS;
+        return LC3GPU_OK;
+    }
+    // a multi-unit library's list twins carry a body per compile-time view and none for the run-time view (LC3_GROUP_VIEW_LIST)
+    bool mixed_list_views_ok() const {
+#if LC3_MULTI_TU
+        for (const GroupHost &g : groups)
+            if (g.h.view == 0) return false;
+#endif
+        return true;
+    }
     const HostCfg &cfg_of_channel(int ch) const { return mixed ? groups[(size_t)streams[(size_t)ch].group].h : h; }
     int internal_of_channel(int ch) const { return mixed ? streams[(size_t)ch].internal : ch; }
     void release_common() {
         timer.release();
         if (d_list) (void)hipFree(d_list);
         d_list = nullptr;
+        if (d_mlist) (void)hipFree(d_mlist);
+        d_mlist = nullptr;
+        for (int i = 0; i < LC3_LIST_SLOTS; i++) {
+            if (h_mlist[i]) (void)hipHostFree(h_mlist[i]);
+            if (mlist_ev[i]) (void)hipEventDestroy(mlist_ev[i]);
+            h_mlist[i] = nullptr;
+            mlist_ev[i] = nullptr;
+        }
         for (int i = 0; i < LC3_LIST_SLOTS; i++) {
             if (h_list[i]) (void)hipHostFree(h_list[i]);
             if (list_ev[i]) (void)hipEventDestroy(list_ev[i]);
@@ -2918,7 +3135,7 @@ static int state_blobs_load_channels(HandleCommon &hc, ST *d_states, const int32
 
 extern "C" {
 
-int lc3gpu_version(void) { return 310; }
+int lc3gpu_version(void) { return 320; }
 
 const char *lc3gpu_strerror(int code) {
     switch (code) {
@@ -3490,6 +3707,82 @@ int lc3gpu_encode_mixed(lc3gpu_encoder *e, const int16_t *d_pcm, uint8_t *d_out,
     return e->order_end(stream);
 }
 
+// A list of a mixed handle's streams: everything is checked on the host before anything is queued; the plan (lc3_host_mixed_list.h) is
+// built into a pinned slot and goes to the device in stream order; then ONE launch per kernel over the listed streams of every group --
+// the list twins of the wave-per-stream kernels, the mixed lane-per-frame kernels unchanged on the compact planes.  Fresh and carried
+// streams run in the same launch: no materialising launch in front.
+int lc3gpu_encode_mixed_list(lc3gpu_encoder *e, const int32_t *channels, int n_list, const int16_t *d_pcm, uint8_t *d_out, int n_frames,
+                             void *stream_) {
+    if (!e || !e->mixed || n_list < 0) return LC3GPU_EINVAL;
+    if (n_frames <= 0) return LC3GPU_ELENGTH;
+    if (n_list == 0) return LC3GPU_OK;
+    if (!channels || !d_pcm || !d_out || ((uintptr_t)d_pcm & 3u) != 0) return LC3GPU_EINVAL;
+    if (!e->mixed_list_views_ok()) return LC3GPU_EUNSUPPORTED;
+    int rc = e->list_check(channels, n_list);
+    if (rc) return rc;
+    LC3_ON_DEVICE(e);
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t frames = (size_t)n_list * (size_t)n_frames;
+    uint8_t *slot = nullptr;
+    rc = e->order_begin(stream);
+    if (rc == LC3GPU_OK) rc = encoder_reserve_planes(e, frames, stream);
+    if (rc == LC3GPU_OK) rc = e->mlist_slot(&slot);
+    if (rc) return rc;
+    lc3_mlist_plan P;
+    lc3_mlist_build(e->mlist_groups.data(), (int)e->mlist_groups.size(), e->mlist_streams.data(), e->fresh_mask.data(), channels, n_list,
+                    (int32_t *)slot, (lc3_stream_io *)(slot + HandleCommon::mlist_tab_offset(n_list)), P);
+    if ((rc = e->mlist_upload(n_list, stream)) != LC3GPU_OK) return rc;
+    const int32_t *d_entries = (const int32_t *)e->d_mlist;
+    const lc3_io io = {0, (const lc3_stream_io *)(e->d_mlist + HandleCommon::mlist_tab_offset(n_list))};
+    const lc3_mlist_group *mg = e->mlist_groups.data();
+    const int ng = (int)e->mlist_groups.size();
+    const unsigned fpb = lc3_frame_block_fit(LC3_PACK_LDS_FIXED, (size_t)P.max_nbytes);
+    lc3_groups G;
+    unsigned wg_stream, wg_frame;
+    lc3_mlist_groups(mg, ng, P, n_frames, (unsigned)LC3_WG_WAVES, fpb, G, wg_stream, wg_frame);
+    const size_t t0 = e->timer.used;
+    e->timer.begin(stream);
+    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_enc_front_mixed_list_kernel), dim3(wg_stream), dim3(64 * LC3_WG_WAVES), 0, stream, G, e->d_states, d_entries,
+                       d_pcm, e->d_mid, e->d_planes, n_frames, io, e->spec_flags);
+    LC3_LAUNCH_CHECK(e, stream, t0);
+    e->timer.mark(stream, 0);
+    LC3_STAGE_RECORD(e, LC3GPU_ENC_STAGE_FRONT, stream, t0);
+    {
+        lc3_groups G256;  // the vector quantiser runs 256 frames per workgroup
+        unsigned a, b;
+        lc3_mlist_groups(mg, ng, P, n_frames, (unsigned)LC3_WG_WAVES, 256u, G256, a, b);
+        hipLaunchKernelGGL(lc3_sns_vq_mixed_kernel, dim3(b), dim3(256), 0, stream, G256, e->d_mid, e->d_planes, n_frames, e->spec_flags);
+        LC3_LAUNCH_CHECK(e, stream, t0);
+    }
+    e->timer.mark(stream, 1);
+    LC3_STAGE_RECORD(e, LC3GPU_ENC_STAGE_VQ, stream, t0);
+    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_enc_back_mixed_list_kernel), dim3(wg_stream), dim3(64 * LC3_WG_WAVES), 0, stream, G, e->d_states, d_entries,
+                       (const float *)e->d_mid, e->d_planes, n_frames, e->spec_flags | lc3_prep_symbols_flag(frames, true));
+    LC3_LAUNCH_CHECK(e, stream, t0);
+    e->timer.mark(stream, 2);
+    LC3_STAGE_RECORD(e, LC3GPU_ENC_STAGE_BACK, stream, t0);
+    if (lc3_prep_symbols_mode(frames) == 0 && lc3_pack_pc_enabled()) {  // full batches: the producer / consumer pairs, as lc3gpu_encode_mixed
+        if ((rc = lc3_pack_pc_optin()) != LC3GPU_OK) {
+            e->timer.rollback(t0);
+            (void)e->order_end(stream);
+            return rc;
+        }
+        const unsigned pfpb = lc3_pack_pc_fpb(P.max_nbytes);
+        lc3_groups Gp;
+        unsigned a, b;
+        lc3_mlist_groups(mg, ng, P, n_frames, (unsigned)LC3_WG_WAVES, pfpb, Gp, a, b);
+        hipLaunchKernelGGL(lc3_pack_pc_mixed_kernel, dim3(b), dim3(2 * pfpb), lc3_pack_pc_lds(pfpb, P.max_nbytes), stream, Gp, (const int32_t *)e->d_planes,
+                           d_out, n_frames, io, e->d_pc_timeouts);
+    } else {
+        const size_t lds = LC3_PACK_LDS_FIXED + (((size_t)fpb * (size_t)P.max_nbytes + 3) & ~(size_t)3) + 4;
+        hipLaunchKernelGGL(lc3_pack_mixed_kernel, dim3(wg_frame), dim3(fpb), lds, stream, G, (const int32_t *)e->d_planes, d_out, n_frames, io);
+    }
+    LC3_LAUNCH_CHECK(e, stream, t0);
+    e->timer.mark(stream, 3);
+    for (int i = 0; i < n_list; i++) e->fresh_mask[(size_t)e->streams[(size_t)channels[i]].internal] = 0;
+    return e->order_end(stream);
+}
+
 static int encode_frame_host(lc3gpu_encoder *e, int channel_index, const int16_t *samples_in, int n_samples,
                              uint8_t *buf_out, int nbytes, float *dbg) {
     if (!e || !samples_in || !buf_out) return LC3GPU_EINVAL;
@@ -4031,6 +4324,84 @@ int lc3gpu_decode_mixed(lc3gpu_decoder *d, const uint8_t *d_in, const uint8_t *d
                            (const int32_t *)d->d_planes, d_pcm, n_frames, 0, io);
     LC3_LAUNCH_CHECK(d, stream, t0);
     d->timer.mark(stream, 3);
+    return d->order_end(stream);
+}
+
+// A list of a mixed handle's streams, as lc3gpu_encode_mixed_list: parser and reconstruction form as lc3gpu_decode_mixed picks them for a
+// launch of this size, on the compact buffers; the synthesis twin starts the channels noted fresh from the constructed state in the same
+// launch (no materialising launch and none of its synchronisation; the channels not listed stay noted).
+int lc3gpu_decode_mixed_list(lc3gpu_decoder *d, const int32_t *channels, int n_list, const uint8_t *d_in, const uint8_t *d_bad, int16_t *d_pcm,
+                             int n_frames, void *stream_) {
+    if (!d || !d->mixed || n_list < 0) return LC3GPU_EINVAL;
+    if (n_frames <= 0) return LC3GPU_ELENGTH;
+    if (n_list == 0) return LC3GPU_OK;
+    if (!channels || !d_in || !d_pcm || ((uintptr_t)d_pcm & 3u) != 0) return LC3GPU_EINVAL;
+    if (!d->mixed_list_views_ok()) return LC3GPU_EUNSUPPORTED;
+    int rc = d->list_check(channels, n_list);
+    if (rc) return rc;
+    LC3_ON_DEVICE(d);
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t frames = (size_t)n_list * (size_t)n_frames;
+    const int mode = lc3_recon_mode(frames, n_frames);
+    uint8_t *slot = nullptr;
+    rc = d->order_begin(stream);
+    if (rc == LC3GPU_OK) rc = decoder_reserve_planes(d, frames, stream);
+    if (rc == LC3GPU_OK && mode == LC3_RECON_WAVE) rc = lc3_tns_lds_optin();
+    if (rc == LC3GPU_OK) rc = d->mlist_slot(&slot);
+    if (rc) return rc;
+    lc3_mlist_plan P;
+    lc3_mlist_build(d->mlist_groups.data(), (int)d->mlist_groups.size(), d->mlist_streams.data(), d->fresh_mask.data(), channels, n_list,
+                    (int32_t *)slot, (lc3_stream_io *)(slot + HandleCommon::mlist_tab_offset(n_list)), P);
+    if ((rc = d->mlist_upload(n_list, stream)) != LC3GPU_OK) return rc;
+    const int32_t *d_entries = (const int32_t *)d->d_mlist;
+    const lc3_io io = {0, (const lc3_stream_io *)(d->d_mlist + HandleCommon::mlist_tab_offset(n_list))};
+    const lc3_mlist_group *mg = d->mlist_groups.data();
+    const int ng = (int)d->mlist_groups.size();
+    const unsigned fpb = lc3_frame_block_fit(LC3_PARSE_LDS_FIXED, (size_t)(64 + P.max_nbytes));
+    const size_t lds = LC3_PARSE_LDS_FIXED + (size_t)fpb * (size_t)(64 + P.max_nbytes);
+    lc3_groups G;
+    unsigned wg_stream, wg_frame;
+    lc3_mlist_groups(mg, ng, P, n_frames, (unsigned)LC3_WG_WAVES, fpb, G, wg_stream, wg_frame);
+    const size_t t0 = d->timer.used;
+    d->timer.begin(stream);
+    if (mode == LC3_RECON_LANE && lc3_parse_pc_enabled()) {  // full batches: the producer / consumer pairs, as lc3gpu_decode_mixed
+        if ((rc = lc3_parse_pc_optin()) != LC3GPU_OK) {
+            d->timer.rollback(t0);
+            (void)d->order_end(stream);
+            return rc;
+        }
+        const unsigned pfpb = lc3_parse_pc_fpb(P.max_nbytes);
+        lc3_groups Gp;
+        unsigned a, b;
+        lc3_mlist_groups(mg, ng, P, n_frames, (unsigned)LC3_WG_WAVES, pfpb, Gp, a, b);
+        hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_parse_pc_mixed_kernel), dim3(b), dim3(2 * pfpb), lc3_parse_pc_lds(pfpb, P.max_nbytes), stream, Gp, d_in, d_bad,
+                           d->d_planes, n_frames, io, d->d_pc_timeouts);
+    } else
+        hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_parse_mixed_kernel), dim3(wg_frame), dim3(fpb), lds, stream, G, d_in, d_bad, d->d_planes, n_frames, io, mode);
+    LC3_LAUNCH_CHECK(d, stream, t0);
+    d->timer.mark(stream, 0);
+    if (mode == LC3_RECON_WAVE) {
+        lc3_groups Gx;
+        unsigned a, b;
+        lc3_mlist_groups(mg, ng, P, n_frames, (unsigned)LC3_WG_WAVES, (unsigned)LC3_WG_WAVES, Gx, a, b);
+        hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_recon_mixed_kernel), dim3(b), dim3(64 * LC3_WG_WAVES), 0, stream, Gx, d->d_planes, n_frames);
+        LC3_LAUNCH_CHECK(d, stream, t0);
+        d->timer.mark(stream, 1);
+        lc3_mlist_groups(mg, ng, P, n_frames, (unsigned)LC3_WG_WAVES, (unsigned)LC3_TNS_FPB, Gx, a, b);
+        hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_tns_mixed_kernel), dim3(b), dim3(LC3_TNS_FPB), LC3_TNS_LDS, stream, Gx, d->d_planes, n_frames);
+        LC3_LAUNCH_CHECK(d, stream, t0);
+        d->timer.mark(stream, 2);
+    }
+    LC3_STAGE_RECORD(d, LC3GPU_DEC_STAGE_PARSE, stream, t0);
+    if (mode == LC3_RECON_LATE)
+        hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_decode_mixed_list_late_kernel), dim3(wg_stream), dim3(64 * LC3_WG_WAVES), 0, stream, G, d->d_states, d_entries,
+                           (const int32_t *)d->d_planes, d_pcm, n_frames, io);
+    else
+        hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_decode_mixed_list_kernel), dim3(wg_stream), dim3(64 * LC3_WG_WAVES), 0, stream, G, d->d_states, d_entries,
+                           (const int32_t *)d->d_planes, d_pcm, n_frames, io);
+    LC3_LAUNCH_CHECK(d, stream, t0);  // (the channels noted fresh stay noted: whatever ran, their next call starts them from the constructed state)
+    d->timer.mark(stream, 3);
+    for (int i = 0; i < n_list; i++) d->fresh_clear(d->streams[(size_t)channels[i]].internal);
     return d->order_end(stream);
 }
 

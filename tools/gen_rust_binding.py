@@ -188,6 +188,16 @@ impl Lc3EncoderGpu {
                                      hip_stream: *mut c_void) -> i32 {
         lc3gpu_encode_list(self.h, channels.as_ptr(), channels.len() as i32, d_pcm, d_out, nbytes as i32, n_frames as i32, hip_stream)
     }
+    /// The same choice on a mixed-configuration handle (several `Lc3Encoder` objects of different configurations driven as one): item i of
+    /// the ragged buffers, compact in list order, holds the frames of stream `channels[i]` at its descriptor's frame size.
+    ///
+    /// # Safety
+    /// `d_pcm` / `d_out` must be device allocations laid out as include/lc3gpu.h states for lc3gpu_encode_mixed_list that outlive the
+    /// call's work; `channels` is host memory and free again when the call returns.
+    pub unsafe fn encode_mixed_list_device(&mut self, channels: &[i32], d_pcm: *const i16, d_out: *mut u8, n_frames: usize,
+                                           hip_stream: *mut c_void) -> i32 {
+        lc3gpu_encode_mixed_list(self.h, channels.as_ptr(), channels.len() as i32, d_pcm, d_out, n_frames as i32, hip_stream)
+    }
     /// a new `EncoderChannel` for each named channel (from its next call on; no wait); the others are untouched
     pub fn reset_channels(&mut self, channels: &[i32]) -> Result<(), i32> {
         let rc = unsafe { lc3gpu_encoder_reset_channels(self.h, channels.as_ptr(), channels.len() as i32) };
@@ -261,6 +271,15 @@ impl Lc3DecoderGpu {
     pub unsafe fn decode_list_device(&mut self, channels: &[i32], d_in: *const u8, d_bad_frame: *const u8, d_pcm: *mut i16, nbytes: usize,
                                      n_frames: usize, hip_stream: *mut c_void) -> i32 {
         lc3gpu_decode_list(self.h, channels.as_ptr(), channels.len() as i32, d_in, d_bad_frame, d_pcm, nbytes as i32, n_frames as i32, hip_stream)
+    }
+    /// The same choice on a mixed-configuration handle: ragged buffers (and flags) compact in list order, include/lc3gpu.h.
+    ///
+    /// # Safety
+    /// device allocations laid out as include/lc3gpu.h states for lc3gpu_decode_mixed_list that outlive the call's work; `channels` is
+    /// host memory and free again when the call returns.
+    pub unsafe fn decode_mixed_list_device(&mut self, channels: &[i32], d_in: *const u8, d_bad_frame: *const u8, d_pcm: *mut i16,
+                                           n_frames: usize, hip_stream: *mut c_void) -> i32 {
+        lc3gpu_decode_mixed_list(self.h, channels.as_ptr(), channels.len() as i32, d_in, d_bad_frame, d_pcm, n_frames as i32, hip_stream)
     }
     /// a new `DecoderChannel` for each named channel (from its next call on; no wait; its PLC count goes to zero)
     pub fn reset_channels(&mut self, channels: &[i32]) -> Result<(), i32> {
