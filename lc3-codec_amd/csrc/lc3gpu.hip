@@ -1,12 +1,13 @@
 // lc3gpu -- kernels and C ABI of the MI355X-native batched LC3 codec.  gfx950 only.
-// Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared (see __graft_entry__.build()).
+// Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared (see build_native in lc3-codec_amd/api.py).
 //
-// Six kernels.  Stream kernels (lc3_enc_front_kernel, lc3_enc_back_kernel, lc3_decode_kernel): one workgroup = four
-// wavefronts = four streams; a launch covers `n_streams` streams x `n_frames` frames, each wave loads its stream's
-// state scalars from HBM into LDS once, runs the frames in time order and writes the state back.  Frame kernels
-// (lc3_sns_vq_kernel, lc3_pack_kernel, lc3_parse_kernel): one LANE per frame for the serial, frame-local stages.
-// Stages meet in HBM "planes" (one contiguous column of words per frame).  blockIdx -> stream / frame is the identity:
-// streams share nothing but read-only tables, so XCD placement only affects table L2 hits.
+// Two kinds of kernel; a batch call of a uniform handle launches six, and the other kernels of this file are forms of these six (for
+// channel lists, a size per frame, mixed-configuration handles, the alternative stage forms).  Stream kernels (lc3_enc_front_kernel,
+// lc3_enc_back_kernel, lc3_decode_kernel): one workgroup = four wavefronts = four streams; a launch covers `n_streams` streams x
+// `n_frames` frames, each wave loads its stream's state scalars from HBM into LDS once, runs the frames in time order and writes the
+// state back.  Frame kernels (lc3_sns_vq_kernel, lc3_pack_kernel, lc3_parse_kernel): one LANE per frame for the serial, frame-local
+// stages.  Stages meet in HBM "planes" (one contiguous column of words per frame).  blockIdx -> stream / frame is the identity: streams
+// share nothing but read-only tables, so XCD placement only affects table L2 hits.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -2268,28 +2269,6 @@ int cfg_acquire(HostCfg &h, int frame_us, int fs_hz) {
 
 // optional per-kernel timing with HIP events recorded on the launch stream (bench.py roofline).  Events come from a pool
 // that lives as long as the handle: nothing is created inside a timed region once the pool has warmed up.
-// after a kernel launch inside a batch call: on failure the marks of this call are forgotten (the timer's intervals stay aligned) and
-// what was already enqueued is still recorded as the handle's work in flight, so that a later call or quiesce() orders behind it
-#define LC3_LAUNCH_CHECK(h, stream, t0)               \
-    do {                                              \
-        hipError_t e_ = hipGetLastError();            \
-        if (e_ != hipSuccess) {                       \
-            g_last_hip = (int)e_;                     \
-            (h)->timer.rollback(t0);                  \
-            (void)(h)->order_end(stream);             \
-            return LC3GPU_EHIP;                       \
-        }                                             \
-    } while (0)
-// a stage event of the caller behind the kernel just queued (mixed handles; the uniform ones: encode_kernels / decode_kernels)
-#define LC3_STAGE_RECORD(h, stage, stream, t0)        \
-    do {                                              \
-        const int rc_ = (h)->stage_record(stage, stream); \
-        if (rc_) {                                    \
-            (h)->timer.rollback(t0);                  \
-            (void)(h)->order_end(stream);             \
-            return rc_;                               \
-        }                                             \
-    } while (0)
 struct KernelTimer {
     bool enabled = false;
     std::vector<hipEvent_t> pool;  // every event ever created for this handle
@@ -2303,18 +2282,14 @@ struct KernelTimer {
     int period = 1;                // every period-th batch call is timed (an event after every kernel costs the stream ~4 us each)
     long calls = 0;
     bool active = false;           // the current call is one of them
-    // a batch call: arm(); then per HIP stream it launches on (chain), mark(stream, -1, chain) before its first kernel there and
-    // mark(stream, slot of that kernel, chain) after every kernel.  begin(stream) = arm + the first mark of chain 0.
+    // a batch call: arm() (BatchCall); then per HIP stream it launches on (chain), mark(stream, -1, chain) before its first kernel there and
+    // mark(stream, slot of that kernel, chain) after every kernel (encode_stages / decode_stages)
     bool arm() {
         active = enabled && (calls++ % (long)period) == 0;
         call_start = used;
         last[0] = last[1] = last[2] = -1;
         if (active) launches += 1;
         return active;
-    }
-    void begin(hipStream_t s) {
-        arm();
-        mark(s, -1);
     }
     void set(int enable) {
         enabled = enable != 0;
@@ -2397,6 +2372,51 @@ struct GroupHost {
     int nbytes = 0, first_stream = 0, n_streams = 0;
 };
 
+// What a list call sends to the device in front of its kernels: LC3_LIST_SLOTS slots of PINNED host memory the handle owns and one device
+// copy.  The call builds its data in a slot (acquire), and an asynchronous copy on the call's stream takes it from there to the device copy
+// (upload) -- the caller's array is free when the call returns and the host waits for nothing.  The slots take turns; a slot is reused
+// once the copy that read it has completed (its event: LC3_LIST_SLOTS calls back, long done in any steady state).  One device copy is
+// enough: a handle's launches are ordered (order_begin).
+#define LC3_LIST_SLOTS 4
+struct PinnedRing {
+    uint8_t *h[LC3_LIST_SLOTS] = {}, *d = nullptr;
+    hipEvent_t ev[LC3_LIST_SLOTS] = {};
+    bool busy[LC3_LIST_SLOTS] = {};
+    int next = 0;
+    // the slot whose turn it is, free to be written; the buffers are allocated at the first call, `capacity` bytes each
+    int acquire(size_t capacity, uint8_t **slot) {
+        if (!d) {
+            HIP_TRY(hipMalloc((void **)&d, capacity));
+            for (int i = 0; i < LC3_LIST_SLOTS; i++) {
+                HIP_TRY(hipHostMalloc((void **)&h[i], capacity, hipHostMallocDefault));
+                HIP_TRY(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
+            }
+        }
+        if (busy[next]) HIP_TRY(hipEventSynchronize(ev[next]));
+        busy[next] = false;
+        *slot = h[next];
+        return LC3GPU_OK;
+    }
+    // the first `bytes` of that slot -> the device copy, in stream order on `s`; the turn passes on
+    int upload(size_t bytes, hipStream_t s) {
+        HIP_TRY(hipMemcpyAsync(d, h[next], bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(ev[next], s));
+        busy[next] = true;
+        next = (next + 1) % LC3_LIST_SLOTS;
+        return LC3GPU_OK;
+    }
+    void release() {
+        if (d) (void)hipFree(d);
+        d = nullptr;
+        for (int i = 0; i < LC3_LIST_SLOTS; i++) {
+            if (h[i]) (void)hipHostFree(h[i]);
+            if (ev[i]) (void)hipEventDestroy(ev[i]);
+            h[i] = nullptr;
+            ev[i] = nullptr;
+        }
+    }
+};
+
 // what encoder and decoder handles share: the device binding, the ordering of launches across HIP streams (every launch of a
 // handle uses the handle's plane buffers: a launch on another stream than the previous one first waits for it), the timer,
 // and the description of a mixed-configuration handle
@@ -2407,6 +2427,7 @@ struct HandleCommon {
     int num_channels = 0;
     bool mixed = false;
     std::vector<GroupHost> groups;
+    int max_nbytes = 0;                    // a mixed handle: the largest frame size among its groups (fixed at construction, as groups[].nbytes is)
     std::vector<MixedStream> streams;      // caller order
     std::vector<int> caller_of_internal;   // internal index -> caller index
     lc3_stream_io *d_tab = nullptr;        // per internal stream
@@ -2559,16 +2580,35 @@ struct HandleCommon {
         ev_join[1] = ev[3];
         return LC3GPU_OK;
     }
+    // A batch call as two parts on the handle's internal streams (lc3_split_parts): fork behind everything the caller's stream holds so
+    // far, part_a(sub[0], chain 1), part_b(sub[1], chain 2), join back into the caller's stream; the stage events are recorded there.
+    // stagger: part B waits for ev_stage, which part A records where it wants B to start (lc3_split_stagger)
+    template <class PartA, class PartB>
+    int split_run(hipStream_t stream, bool stagger, PartA part_a, PartB part_b) {
+        int rc = LC3GPU_OK;
+        if (hipEventRecord(ev_fork, stream) != hipSuccess || hipStreamWaitEvent(sub[0], ev_fork, 0) != hipSuccess ||
+            hipStreamWaitEvent(sub[1], ev_fork, 0) != hipSuccess) {
+            g_last_hip = (int)hipGetLastError();
+            rc = LC3GPU_EHIP;
+        }
+        if (rc == LC3GPU_OK) rc = part_a(sub[0], 1);
+        if (rc == LC3GPU_OK && stagger && hipStreamWaitEvent(sub[1], ev_stage, 0) != hipSuccess) {
+            g_last_hip = (int)hipGetLastError();
+            rc = LC3GPU_EHIP;
+        }
+        if (rc == LC3GPU_OK) rc = part_b(sub[1], 2);
+        // whatever was queued, the caller's stream (and the handle's next call) orders behind it
+        for (int i = 0; i < 2; i++)
+            if (hipEventRecord(ev_join[i], sub[i]) != hipSuccess || hipStreamWaitEvent(stream, ev_join[i], 0) != hipSuccess) {
+                g_last_hip = (int)hipGetLastError();
+                if (rc == LC3GPU_OK) rc = LC3GPU_EHIP;
+            }
+        if (rc == LC3GPU_OK) rc = stage_record_all(stream);
+        return rc;
+    }
     // The channel list of a list call (lc3gpu_encode_list / lc3gpu_decode_list): the caller's HOST array is checked, merged with the
-    // channels' fresh flags (lc3_dev_list.h) into a slot of PINNED host memory the handle owns, and copied from there to the handle's device
-    // copy by an asynchronous copy on the call's stream, in front of the call's kernels -- the caller's array is free when the call returns and
-    // the host waits for nothing.  LC3_LIST_SLOTS slots take turns; a slot is reused once the copy that read it has completed (its event:
-    // LC3_LIST_SLOTS calls back, long done in any steady state).  One device copy is enough: a handle's launches are ordered (order_begin).
-#define LC3_LIST_SLOTS 4
-    int32_t *h_list[LC3_LIST_SLOTS] = {}, *d_list = nullptr;
-    hipEvent_t list_ev[LC3_LIST_SLOTS] = {};
-    bool list_busy[LC3_LIST_SLOTS] = {};
-    int list_next = 0;
+    // channels' fresh flags (lc3_dev_list.h) and sent through a pinned ring (PinnedRing)
+    PinnedRing list_ring;
     std::vector<uint32_t> list_seen;  // per channel: the number of the list call that named it last (the repeated-index check)
     uint32_t list_call = 0;
     // LC3GPU_OK, or LC3GPU_ECHANNEL for an index outside the handle or named twice; nothing is queued or changed
@@ -2585,65 +2625,43 @@ struct HandleCommon {
         }
         return LC3GPU_OK;
     }
-    // entry i = channels[i] | LC3_LIST_FRESH where fresh[channels[i]] -> the device copy, in stream order on `s`
+    // entry i = channels[i] | LC3_LIST_FRESH where fresh[channels[i]] -> the device copy (d_list), in stream order on `s`
     int list_upload(const int32_t *channels, int n, const std::vector<uint8_t> &fresh, hipStream_t s) {
-        if (!d_list) {
-            HIP_TRY(hipMalloc((void **)&d_list, sizeof(int32_t) * (size_t)num_channels));
-            for (int i = 0; i < LC3_LIST_SLOTS; i++) {
-                HIP_TRY(hipHostMalloc((void **)&h_list[i], sizeof(int32_t) * (size_t)num_channels, hipHostMallocDefault));
-                HIP_TRY(hipEventCreateWithFlags(&list_ev[i], hipEventDisableTiming));
-            }
-        }
-        const int k = list_next;
-        if (list_busy[k]) HIP_TRY(hipEventSynchronize(list_ev[k]));
-        list_busy[k] = false;
-        int32_t *dst = h_list[k];
+        uint8_t *slot = nullptr;
+        const int rc = list_ring.acquire(sizeof(int32_t) * (size_t)num_channels, &slot);
+        if (rc) return rc;
+        int32_t *dst = (int32_t *)slot;
         for (int i = 0; i < n; i++) dst[i] = (int32_t)((uint32_t)channels[i] | (fresh[(size_t)channels[i]] ? LC3_LIST_FRESH : 0u));
-        HIP_TRY(hipMemcpyAsync(d_list, dst, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipEventRecord(list_ev[k], s));
-        list_busy[k] = true;
-        list_next = (k + 1) % LC3_LIST_SLOTS;
-        return LC3GPU_OK;
+        return list_ring.upload(sizeof(int32_t) * (size_t)n, s);
     }
+    const int32_t *d_list() const { return (const int32_t *)list_ring.d; }
     // The plan of a list call on a MIXED handle (lc3gpu_*_mixed_list; lc3_host_mixed_list.h): entries int32[n] and, 8-byte aligned behind
     // them, the per-call lc3_stream_io table [n], both in launch order, built straight into a pinned slot and sent by ONE asynchronous copy
     // on the call's stream in front of the kernels -- the uniform list's scheme (list_upload) with 24 bytes more per item
-    uint8_t *h_mlist[LC3_LIST_SLOTS] = {}, *d_mlist = nullptr;
-    hipEvent_t mlist_ev[LC3_LIST_SLOTS] = {};
-    bool mlist_busy[LC3_LIST_SLOTS] = {};
-    int mlist_next = 0;
+    PinnedRing mlist_ring;
     std::vector<lc3_mlist_group> mlist_groups;    // per group of the handle
     std::vector<lc3_mlist_stream> mlist_streams;  // per caller stream
     static size_t mlist_tab_offset(int n) { return (sizeof(int32_t) * (size_t)n + 7) & ~(size_t)7; }
-    // a free pinned slot (waits for the copy that read it LC3_LIST_SLOTS calls ago, long done in any steady state)
-    int mlist_slot(uint8_t **slot) {
-        if (!d_mlist) {
-            const size_t bytes = mlist_tab_offset(num_channels) + sizeof(lc3_stream_io) * (size_t)num_channels;
-            HIP_TRY(hipMalloc((void **)&d_mlist, bytes));
-            for (int i = 0; i < LC3_LIST_SLOTS; i++) {
-                HIP_TRY(hipHostMalloc((void **)&h_mlist[i], bytes, hipHostMallocDefault));
-                HIP_TRY(hipEventCreateWithFlags(&mlist_ev[i], hipEventDisableTiming));
-            }
+    static size_t mlist_bytes(int n) { return mlist_tab_offset(n) + sizeof(lc3_stream_io) * (size_t)n; }
+    // builds the plan P of a call over channels[n] (already checked; fresh: per internal index) in a free pinned slot and sends it, in
+    // stream order on `s`; the handle's description in the plan's terms is written down at the first call
+    int mlist_send(const int32_t *channels, int n, const uint8_t *fresh, hipStream_t s, lc3_mlist_plan &P) {
+        if (mlist_groups.empty()) {
             mlist_groups.resize(groups.size());
             for (size_t g = 0; g < groups.size(); g++)
                 mlist_groups[g] = {groups[g].h.slot, groups[g].h.view, groups[g].nbytes, groups[g].h.c.ne, groups[g].h.c.nb, groups[g].h.c.nf};
             mlist_streams.resize(streams.size());
             for (size_t i = 0; i < streams.size(); i++) mlist_streams[i] = {streams[i].group, streams[i].internal};
         }
-        const int k = mlist_next;
-        if (mlist_busy[k]) HIP_TRY(hipEventSynchronize(mlist_ev[k]));
-        mlist_busy[k] = false;
-        *slot = h_mlist[k];
-        return LC3GPU_OK;
+        uint8_t *slot = nullptr;
+        const int rc = mlist_ring.acquire(mlist_bytes(num_channels), &slot);
+        if (rc) return rc;
+        lc3_mlist_build(mlist_groups.data(), (int)mlist_groups.size(), mlist_streams.data(), fresh, channels, n, (int32_t *)slot,
+                        (lc3_stream_io *)(slot + mlist_tab_offset(n)), P);
+        return mlist_ring.upload(mlist_bytes(n), s);
     }
-    int mlist_upload(int n, hipStream_t s) {
-        const int k = mlist_next;
-        HIP_TRY(hipMemcpyAsync(d_mlist, h_mlist[k], mlist_tab_offset(n) + sizeof(lc3_stream_io) * (size_t)n, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipEventRecord(mlist_ev[k], s));
-        mlist_busy[k] = true;
-        mlist_next = (k + 1) % LC3_LIST_SLOTS;
-        return LC3GPU_OK;
-    }
+    const int32_t *d_mlist_entries() const { return (const int32_t *)mlist_ring.d; }
+    const lc3_stream_io *d_mlist_tab(int n) const { return (const lc3_stream_io *)(mlist_ring.d + mlist_tab_offset(n)); }
     // a multi-unit library's list twins carry a body per compile-time view and none for the run-time view (LC3_GROUP_VIEW_LIST)
     bool mixed_list_views_ok() const {
 #if LC3_MULTI_TU
@@ -2656,22 +2674,8 @@ struct HandleCommon {
     int internal_of_channel(int ch) const { return mixed ? streams[(size_t)ch].internal : ch; }
     void release_common() {
         timer.release();
-        if (d_list) (void)hipFree(d_list);
-        d_list = nullptr;
-        if (d_mlist) (void)hipFree(d_mlist);
-        d_mlist = nullptr;
-        for (int i = 0; i < LC3_LIST_SLOTS; i++) {
-            if (h_mlist[i]) (void)hipHostFree(h_mlist[i]);
-            if (mlist_ev[i]) (void)hipEventDestroy(mlist_ev[i]);
-            h_mlist[i] = nullptr;
-            mlist_ev[i] = nullptr;
-        }
-        for (int i = 0; i < LC3_LIST_SLOTS; i++) {
-            if (h_list[i]) (void)hipHostFree(h_list[i]);
-            if (list_ev[i]) (void)hipEventDestroy(list_ev[i]);
-            h_list[i] = nullptr;
-            list_ev[i] = nullptr;
-        }
+        list_ring.release();
+        mlist_ring.release();
         if (done) (void)hipEventDestroy(done);
         if (d_tab) (void)hipFree(d_tab);
         if (d_pc_timeouts) (void)hipFree(d_pc_timeouts);
@@ -2701,6 +2705,34 @@ struct HandleCommon {
         done = ev_fork = ev_stage = ev_join[0] = ev_join[1] = nullptr;
         sub[0] = sub[1] = nullptr;
         d_tab = nullptr;
+    }
+};
+
+// The protocol of one batch call of a handle on `stream`, the same for every entry point:
+//   begin()        orders the stream behind the handle's work in flight (order_begin).  What follows it and fails before a kernel of the
+//                  call is queued -- growing the planes, the split's streams, an LDS opt-in, a list's pinned slot -- returns its code as it
+//                  is: nothing is recorded as the handle's work
+//   arm()          the timer's decision for this call, in front of the call's stage sequence (encode_stages / decode_stages)
+//   end(rc, split) rc: what the stage sequence returned.  On failure the marks of this call are forgotten (the timer's intervals stay
+//                  aligned) and what was already enqueued is still recorded as the handle's work in flight, so that a later call or
+//                  quiesce() orders behind it
+struct BatchCall {
+    HandleCommon &hc;
+    hipStream_t stream;
+    size_t t0 = 0;
+    BatchCall(HandleCommon &hc_, hipStream_t stream_) : hc(hc_), stream(stream_) {}
+    int begin() { return hc.order_begin(stream); }
+    void arm() {
+        t0 = hc.timer.used;
+        hc.timer.arm();
+    }
+    int end(int rc, bool split = false) {
+        if (rc) {
+            hc.timer.rollback(t0);
+            (void)hc.order_end(stream, split);
+            return rc;
+        }
+        return hc.order_end(stream, split);
     }
 };
 
@@ -2782,39 +2814,58 @@ int build_mixed(HandleCommon &hc, int n, const lc3gpu_stream_desc *descs, bool r
     }
     HIP_TRY(hipMalloc((void **)&hc.d_tab, sizeof(lc3_stream_io) * (size_t)n));
     HIP_TRY(hipMemcpy(hc.d_tab, tab.data(), sizeof(lc3_stream_io) * (size_t)n, hipMemcpyHostToDevice));
+    for (const GroupHost &g : hc.groups) hc.max_nbytes = std::max(hc.max_nbytes, g.nbytes);
     hc.mixed = true;
     hc.num_channels = n;
     return LC3GPU_OK;
 }
 
-// the group table of one mixed launch (T frames per stream, fpb frames per workgroup of the frame kernels)
-void fill_groups(const HandleCommon &hc, int T, unsigned fpb, lc3_groups &G, unsigned &wg_stream, unsigned &wg_frame, size_t &frames,
-                 int &max_nbytes) {
-    G.n = (int)hc.groups.size();
-    G.pad = 0;
-    wg_stream = wg_frame = 0;
-    frames = 0;
-    max_nbytes = 0;
-    for (size_t i = 0; i < hc.groups.size(); i++) {
-        const GroupHost &gh = hc.groups[i];
-        lc3_group &g = G.g[i];
-        g.slot = gh.h.slot;
-        g.fixed = gh.h.view;  // the mixed kernels carry one body per configuration view
-        g.first_stream = gh.first_stream;
-        g.n_streams = gh.n_streams;
-        g.wg_stream = (int)wg_stream;
-        g.wg_frame = (int)wg_frame;
-        g.nbytes = gh.nbytes;
-        g.ne = gh.h.c.ne;
-        g.nb = gh.h.c.nb;
-        g.pad = 0;
-        g.frame_base = (long long)frames;
-        wg_stream += (unsigned)((gh.n_streams + LC3_WG_WAVES - 1) / LC3_WG_WAVES);
-        wg_frame += (unsigned)(((size_t)gh.n_streams * (size_t)T + fpb - 1) / fpb);
-        frames += (size_t)gh.n_streams * (size_t)T;
-        if (gh.nbytes > max_nbytes) max_nbytes = gh.nbytes;
+// The group table of one mixed launch (T frames per stream, fpb frames per workgroup of the lane-per-frame kernels) and the launch's
+// workgroups: wg_stream for a wave-per-stream kernel, wg_frame for a lane-per-frame kernel.  A mixed call hands its kernels' launches
+// a callable (fpb, GroupTable &) that builds it: HandleGroups or ListGroups
+struct GroupTable {
+    lc3_groups G;
+    unsigned wg_stream = 0, wg_frame = 0;
+};
+// every stream of the handle, T frames each
+struct HandleGroups {
+    const HandleCommon &hc;
+    int T;
+    void operator()(unsigned fpb, GroupTable &t) const {
+        lc3_groups &G = t.G;
+        G.n = (int)hc.groups.size();
+        G.pad = 0;
+        t.wg_stream = t.wg_frame = 0;
+        size_t frames = 0;
+        for (size_t i = 0; i < hc.groups.size(); i++) {
+            const GroupHost &gh = hc.groups[i];
+            lc3_group &g = G.g[i];
+            g.slot = gh.h.slot;
+            g.fixed = gh.h.view;  // the mixed kernels carry one body per configuration view
+            g.first_stream = gh.first_stream;
+            g.n_streams = gh.n_streams;
+            g.wg_stream = (int)t.wg_stream;
+            g.wg_frame = (int)t.wg_frame;
+            g.nbytes = gh.nbytes;
+            g.ne = gh.h.c.ne;
+            g.nb = gh.h.c.nb;
+            g.pad = 0;
+            g.frame_base = (long long)frames;
+            t.wg_stream += (unsigned)((gh.n_streams + LC3_WG_WAVES - 1) / LC3_WG_WAVES);
+            t.wg_frame += (unsigned)(((size_t)gh.n_streams * (size_t)T + fpb - 1) / fpb);
+            frames += (size_t)gh.n_streams * (size_t)T;
+        }
     }
-}
+};
+// the listed streams of plan P (lc3_host_mixed_list.h)
+struct ListGroups {
+    const HandleCommon &hc;
+    const lc3_mlist_plan &P;
+    int T;
+    void operator()(unsigned fpb, GroupTable &t) const {
+        lc3_mlist_groups(hc.mlist_groups.data(), (int)hc.mlist_groups.size(), P, T, (unsigned)LC3_WG_WAVES, fpb, t.G, t.wg_stream, t.wg_frame);
+    }
+};
 
 }  // namespace
 
@@ -3339,72 +3390,150 @@ static int lc3_split_stagger() {
     return v;
 }
 
-// the list kernels (lc3_dev_list.h) exist for the headline view and the run-time view, like the sized ones
-#define LC3_LAUNCH_LIST(kern, h, grid, block, lds, stream, ...)                                                                  \
+// a kernel that exists for the headline view and the run-time view: the list kernels (lc3_dev_list.h) and the sized ones (lc3_dev_enc_vbr.h,
+// lc3_dev_dec_vbr.h)
+#define LC3_LAUNCH_HEADLINE(kern, h, grid, block, lds, stream, ...)                                                              \
     do {                                                                                                                        \
         if ((h).view == 1) hipLaunchKernelGGL(kern<lc3_cfg_48k10>, grid, block, lds, stream, lc3_cfg_slot<lc3_cfg_48k10>{(h).slot}, __VA_ARGS__); \
         else hipLaunchKernelGGL(kern<lc3_cfg_any>, grid, block, lds, stream, lc3_cfg_slot<lc3_cfg_any>{(h).slot}, __VA_ARGS__);                 \
     } while (0)
-// the four encoder kernels of channels [first, first + n) (internal order) on `stream`; the buffers and planes are those of this range.
-// chain: the timer's chain of this stream.  after_front: recorded behind the front half when not null.  d_list (a list call): the n
-// streams are the channels of the list's entries (first and fresh are not used), planar compact buffers
-static int encode_kernels(lc3gpu_encoder *e, const HostCfg &h, int first, int n, const int16_t *d_pcm, uint8_t *d_out, float *mid,
-                          int32_t *planes, int nbytes, int n_frames, int fresh, lc3_io io, hipStream_t stream, int chain,
-                          hipEvent_t after_front, float *dbg, size_t frames_of_call, const int32_t *d_list = nullptr) {
-    const size_t frames = (size_t)n * (size_t)n_frames;
-    // analysis front half (wave per stream) -> SNS vector quantiser (lane per frame) -> back half (wave per stream) ->
-    // bitstream packing (lane per frame)
-    const dim3 wg_grid((unsigned)((n + LC3_WG_WAVES - 1) / LC3_WG_WAVES)), wg_block(64 * LC3_WG_WAVES);
-    int rc_stage = 0;
-    e->timer.mark(stream, -1, chain);
-    if (d_list)
-        LC3_LAUNCH_LIST(lc3_enc_front_list_kernel, h, wg_grid, wg_block, lc3_lds_pad(0), stream, e->d_states, d_list, n, d_pcm, mid, planes, nbytes,
-                        n_frames, e->spec_flags);
-    else
-        LC3_LAUNCH_CFG(lc3_enc_front_kernel, h, wg_grid, wg_block, lc3_lds_pad(0), stream, e->d_states, first, n, d_pcm, mid, planes, nbytes, n_frames, fresh,
-                       dbg, io, e->spec_flags);
+
+// ---- the stage sequence of a batch call.  One function template per direction runs the launches of a call's kernels on one HIP stream
+// and does, between them, what every call variant owes the handle: the check of each launch, the timer's marks (chain: the timer's chain
+// of this stream) and, on chain 0, the caller's stage events (the split path records those at its join).  What a variant launches comes
+// in as callables, each -> LC3GPU_* code (its launch is checked here).
+extern "C++" {
+// a stage's callable has returned rc: its own failure (an LDS opt-in), else whatever its launch left with the runtime
+static int launch_result(int rc) {
+    if (rc) return rc;
     HIP_TRY(hipGetLastError());
+    return LC3GPU_OK;
+}
+// analysis front half (wave per stream) -> SNS vector quantiser (lane per frame) -> back half (wave per stream) -> bitstream packing
+// (lane per frame).  after_front: recorded behind the front half when not null.  symbols: the symbol preparation as a kernel of its own
+// where the call has one (symbols_launch: checked there, timed together with the packer)
+template <class Front, class Vq, class Back, class Symbols, class Pack>
+static int encode_stages(lc3gpu_encoder *e, hipStream_t stream, int chain, hipEvent_t after_front, Front front, Vq vq, Back back, Symbols symbols,
+                         Pack pack) {
+    int rc;
+    e->timer.mark(stream, -1, chain);
+    if ((rc = launch_result(front())) != LC3GPU_OK) return rc;
     e->timer.mark(stream, 0, chain);
     if (after_front) HIP_TRY(hipEventRecord(after_front, stream));
-    if (chain == 0 && (rc_stage = e->stage_record(LC3GPU_ENC_STAGE_FRONT, stream)) != 0) return rc_stage;
+    if (chain == 0 && (rc = e->stage_record(LC3GPU_ENC_STAGE_FRONT, stream)) != LC3GPU_OK) return rc;
+    if ((rc = launch_result(vq())) != LC3GPU_OK) return rc;
+    e->timer.mark(stream, 1, chain);
+    if (chain == 0 && (rc = e->stage_record(LC3GPU_ENC_STAGE_VQ, stream)) != LC3GPU_OK) return rc;
+    if ((rc = launch_result(back())) != LC3GPU_OK) return rc;
+    e->timer.mark(stream, 2, chain);
+    if (chain == 0 && (rc = e->stage_record(LC3GPU_ENC_STAGE_BACK, stream)) != LC3GPU_OK) return rc;
+    if ((rc = symbols()) != LC3GPU_OK) return rc;
+    if ((rc = launch_result(pack())) != LC3GPU_OK) return rc;
+    e->timer.mark(stream, 3, chain);
+    return LC3GPU_OK;
+}
+}  // extern "C++"
+
+// ---- the launches the encoder's call variants share (uniform handles: `frames` frames in `planes`; frames_of_call: of the whole call, which
+// decides the kernel forms)
+static dim3 lc3_stream_grid(int n_streams) { return dim3((unsigned)((n_streams + LC3_WG_WAVES - 1) / LC3_WG_WAVES)); }
+static int vq_launch(lc3gpu_encoder *e, const HostCfg &h, float *mid, int32_t *planes, size_t frames, hipStream_t stream) {
     hipLaunchKernelGGL(lc3_sns_vq_kernel, dim3((unsigned)((frames + 255) / 256)), dim3(256), 0, stream, h.c.nb, mid, planes, (int)frames,
                        e->spec_flags);
-    HIP_TRY(hipGetLastError());
-    e->timer.mark(stream, 1, chain);
-    if (chain == 0 && (rc_stage = e->stage_record(LC3GPU_ENC_STAGE_VQ, stream)) != 0) return rc_stage;
-    if (d_list)
-        LC3_LAUNCH_LIST(lc3_enc_back_list_kernel, h, wg_grid, wg_block, lc3_lds_pad(1), stream, e->d_states, d_list, n, (const float *)mid, planes, nbytes,
-                        n_frames, e->spec_flags | lc3_prep_symbols_flag(frames_of_call));
-    else
-        LC3_LAUNCH_CFG(lc3_enc_back_kernel, h, wg_grid, wg_block, lc3_lds_pad(1), stream, e->d_states, first, n, (const float *)mid, planes, nbytes, n_frames,
-                       dbg, e->spec_flags | lc3_prep_symbols_flag(frames_of_call));
-    HIP_TRY(hipGetLastError());
-    e->timer.mark(stream, 2, chain);
-    if (chain == 0 && (rc_stage = e->stage_record(LC3GPU_ENC_STAGE_BACK, stream)) != 0) return rc_stage;
-    if (lc3_prep_symbols_mode(frames_of_call) == 2) {  // (timed together with the packer)
-        const size_t wgs = (frames + LC3_WG_WAVES - 1) / LC3_WG_WAVES;
-        LC3_LAUNCH_CFG(lc3_symbols_kernel, h, dim3((unsigned)(wgs < lc3_recon_grid() ? wgs : lc3_recon_grid())), dim3(64 * LC3_WG_WAVES), 0, stream,
-                       planes, (int)frames);
-        HIP_TRY(hipGetLastError());
-    }
+    return LC3GPU_OK;
+}
+// A module holds its kernel templates' instantiations in the order the host side first names them, and the listings of
+// tools/kernel_resources_all.sh (profiles/*_kernel_resources.txt) follow it.  The list kernels and the back half are named here, where the
+// one function that launched the four encoder kernels of every uniform variant named them, so that the listings keep their order
+static const void *const lc3_listing_order[] = {
+    (const void *)lc3_enc_front_list_kernel<lc3_cfg_48k10>, (const void *)lc3_enc_front_list_kernel<lc3_cfg_any>,
+    (const void *)lc3_enc_back_list_kernel<lc3_cfg_48k10>,  (const void *)lc3_enc_back_list_kernel<lc3_cfg_any>,
+    (const void *)lc3_enc_back_kernel<lc3_cfg_48k10>,       (const void *)lc3_enc_back_kernel<lc3_cfg_48k75>,
+    (const void *)lc3_enc_back_kernel<lc3_cfg_32k10>,       (const void *)lc3_enc_back_kernel<lc3_cfg_16k10>,
+    (const void *)lc3_enc_back_kernel<lc3_cfg_any>};
+static int symbols_launch(const HostCfg &h, int32_t *planes, size_t frames, size_t frames_of_call, hipStream_t stream) {
+    if (lc3_prep_symbols_mode(frames_of_call) != 2) return LC3GPU_OK;
+    const size_t wgs = (frames + LC3_WG_WAVES - 1) / LC3_WG_WAVES;
+    LC3_LAUNCH_CFG(lc3_symbols_kernel, h, dim3((unsigned)(wgs < lc3_recon_grid() ? wgs : lc3_recon_grid())), dim3(64 * LC3_WG_WAVES), 0, stream,
+                   planes, (int)frames);
+    return launch_result(LC3GPU_OK);
+}
+// the pair kernels' LDS opt-in, once per handle: the opt-in itself takes a process-wide lock
+static int pc_optin_once(HandleCommon &hc, int (*optin)()) {
+    if (hc.pc_optin_done) return LC3GPU_OK;
+    const int rc = optin();
+    if (rc == LC3GPU_OK) hc.pc_optin_done = true;
+    return rc;
+}
+// the packer: the producer / consumer pairs where the packer derives its symbols itself (full batches), else one lane per frame
+static int pack_launch(lc3gpu_encoder *e, const HostCfg &h, const int32_t *planes, uint8_t *d_out, int nbytes, size_t frames, int n_frames,
+                       lc3_io io, size_t frames_of_call, hipStream_t stream) {
     if (lc3_prep_symbols_mode(frames_of_call) == 0 && lc3_pack_pc_enabled()) {
-        if (!e->pc_optin_done) {  // (once per handle: the opt-in itself takes a process-wide lock)
-            int rc = lc3_pack_pc_optin();
-            if (rc) return rc;
-            e->pc_optin_done = true;
-        }
+        const int rc = pc_optin_once(*e, lc3_pack_pc_optin);
+        if (rc) return rc;
         const unsigned pfpb = lc3_pack_pc_fpb(nbytes);
         hipLaunchKernelGGL(lc3_pack_pc_kernel, dim3((unsigned)((frames + pfpb - 1) / pfpb)), dim3(2 * pfpb), lc3_pack_pc_lds(pfpb, nbytes), stream,
-                           h.c.ne, (const int32_t *)planes, d_out, nbytes, (int)frames, n_frames, io, e->d_pc_timeouts);
+                           h.c.ne, planes, d_out, nbytes, (int)frames, n_frames, io, e->d_pc_timeouts);
     } else {
         const unsigned fpb = lc3_frame_block_fit(LC3_PACK_LDS_FIXED, (size_t)nbytes);
         const size_t lds = LC3_PACK_LDS_FIXED + (((size_t)fpb * (size_t)nbytes + 3) & ~(size_t)3) + 4;  // + the packer's sink byte
-        hipLaunchKernelGGL(lc3_pack_kernel, dim3((unsigned)((frames + fpb - 1) / fpb)), dim3(fpb), lds, stream, h.c.ne, (const int32_t *)planes,
-                           d_out, nbytes, (int)frames, n_frames, io);
+        hipLaunchKernelGGL(lc3_pack_kernel, dim3((unsigned)((frames + fpb - 1) / fpb)), dim3(fpb), lds, stream, h.c.ne, planes, d_out, nbytes,
+                           (int)frames, n_frames, io);
     }
-    HIP_TRY(hipGetLastError());
-    e->timer.mark(stream, 3, chain);
     return LC3GPU_OK;
+}
+// ... and their forms for a mixed handle, every stream or a list of them: `groups` builds the group table (GroupTable)
+extern "C++" {
+template <class Groups>
+static int vq_mixed_launch(lc3gpu_encoder *e, Groups groups, int n_frames, hipStream_t stream) {
+    GroupTable t;  // the vector quantiser runs 256 frames per workgroup
+    groups(256u, t);
+    hipLaunchKernelGGL(lc3_sns_vq_mixed_kernel, dim3(t.wg_frame), dim3(256), 0, stream, t.G, e->d_mid, e->d_planes, n_frames, e->spec_flags);
+    return LC3GPU_OK;
+}
+template <class Groups>
+static int pack_mixed_launch(lc3gpu_encoder *e, Groups groups, int max_nbytes, uint8_t *d_out, int n_frames, lc3_io io, size_t frames_of_call,
+                             hipStream_t stream) {
+    GroupTable t;  // (a group table of the packer's own number of frames per workgroup)
+    if (lc3_prep_symbols_mode(frames_of_call) == 0 && lc3_pack_pc_enabled()) {
+        const int rc = pc_optin_once(*e, lc3_pack_pc_optin);
+        if (rc) return rc;
+        const unsigned pfpb = lc3_pack_pc_fpb(max_nbytes);
+        groups(pfpb, t);
+        hipLaunchKernelGGL(lc3_pack_pc_mixed_kernel, dim3(t.wg_frame), dim3(2 * pfpb), lc3_pack_pc_lds(pfpb, max_nbytes), stream, t.G,
+                           (const int32_t *)e->d_planes, d_out, n_frames, io, e->d_pc_timeouts);
+    } else {
+        const unsigned fpb = lc3_frame_block_fit(LC3_PACK_LDS_FIXED, (size_t)max_nbytes);
+        const size_t lds = LC3_PACK_LDS_FIXED + (((size_t)fpb * (size_t)max_nbytes + 3) & ~(size_t)3) + 4;
+        groups(fpb, t);
+        hipLaunchKernelGGL(lc3_pack_mixed_kernel, dim3(t.wg_frame), dim3(fpb), lds, stream, t.G, (const int32_t *)e->d_planes, d_out, n_frames, io);
+    }
+    return LC3GPU_OK;
+}
+}  // extern "C++"
+
+// the four encoder kernels of channels [first, first + n) (internal order) of a uniform handle on `stream`; the buffers and planes are
+// those of this range
+static int encode_kernels(lc3gpu_encoder *e, const HostCfg &h, int first, int n, const int16_t *d_pcm, uint8_t *d_out, float *mid,
+                          int32_t *planes, int nbytes, int n_frames, int fresh, lc3_io io, hipStream_t stream, int chain,
+                          hipEvent_t after_front, float *dbg, size_t frames_of_call) {
+    const size_t frames = (size_t)n * (size_t)n_frames;
+    const dim3 wg_grid = lc3_stream_grid(n), wg_block(64 * LC3_WG_WAVES);
+    return encode_stages(
+        e, stream, chain, after_front,
+        [&] {
+            LC3_LAUNCH_CFG(lc3_enc_front_kernel, h, wg_grid, wg_block, lc3_lds_pad(0), stream, e->d_states, first, n, d_pcm, mid, planes, nbytes, n_frames,
+                           fresh, dbg, io, e->spec_flags);
+            return LC3GPU_OK;
+        },
+        [&] { return vq_launch(e, h, mid, planes, frames, stream); },
+        [&] {
+            LC3_LAUNCH_CFG(lc3_enc_back_kernel, h, wg_grid, wg_block, lc3_lds_pad(1), stream, e->d_states, first, n, (const float *)mid, planes, nbytes,
+                           n_frames, dbg, e->spec_flags | lc3_prep_symbols_flag(frames_of_call));
+            return LC3GPU_OK;
+        },
+        [&] { return symbols_launch(h, planes, frames, frames_of_call, stream); },
+        [&] { return pack_launch(e, h, planes, d_out, nbytes, frames, n_frames, io, frames_of_call, stream); });
 }
 
 // one configuration, channels [first, first + n) in internal order; the buffers hold only those channels
@@ -3422,7 +3551,8 @@ static int encode_launch(lc3gpu_encoder *e, const HostCfg &h, int first, int n, 
     // planar PCM is read as 32-bit words: the second half starts na * n_frames * nf samples in (nf is even), its bytes are copied out as
     // words when aligned and as bytes otherwise
     if (parts == 2 && (na <= 0 || na >= n)) parts = 1;
-    int rc = e->order_begin(stream);
+    BatchCall call(*e, stream);
+    int rc = call.begin();
     if (rc == LC3GPU_OK) rc = encoder_reserve_planes(e, frames, stream);
     if (rc == LC3GPU_OK && parts == 2) rc = e->ensure_split();
     if (rc) return rc;
@@ -3434,48 +3564,29 @@ static int encode_launch(lc3gpu_encoder *e, const HostCfg &h, int first, int n, 
         if (rc) return rc;
     }
     lc3_io io = {layout == LC3GPU_LAYOUT_INTERLEAVED ? n : 0, nullptr};
-    const size_t t0 = e->timer.used;
-    e->timer.arm();
+    call.arm();
     if (parts == 1) {
         rc = encode_kernels(e, h, first, n, d_pcm, d_out, e->d_mid, e->d_planes, nbytes, n_frames, fresh, io, stream, 0, nullptr, dbg, frames);
     } else {
-        // two halves [first, first + na) and [first + na, first + n) on the handle's streams: fork behind everything the caller's stream
-        // holds so far, join back into it
-        rc = LC3GPU_OK;
-        if (hipEventRecord(e->ev_fork, stream) != hipSuccess || hipStreamWaitEvent(e->sub[0], e->ev_fork, 0) != hipSuccess ||
-            hipStreamWaitEvent(e->sub[1], e->ev_fork, 0) != hipSuccess) {
-            g_last_hip = (int)hipGetLastError();
-            rc = LC3GPU_EHIP;
-        }
+        // two halves [first, first + na) and [first + na, first + n) on the handle's streams
         const size_t fa = (size_t)na * (size_t)n_frames;
         const bool ilv = layout == LC3GPU_LAYOUT_INTERLEAVED;
-        const int stagger = lc3_split_stagger();
-        if (rc == LC3GPU_OK)
-            rc = encode_kernels(e, h, first, na, d_pcm, d_out, e->d_mid, e->d_planes, nbytes, n_frames, fresh, io, e->sub[0], 1,
-                                stagger == 1 ? e->ev_stage : nullptr, nullptr, frames);
-        if (rc == LC3GPU_OK && stagger == 1 && hipStreamWaitEvent(e->sub[1], e->ev_stage, 0) != hipSuccess) {
-            g_last_hip = (int)hipGetLastError();
-            rc = LC3GPU_EHIP;
-        }
-        if (rc == LC3GPU_OK)
-            rc = encode_kernels(e, h, first + na, n - na, ilv ? d_pcm + na : d_pcm + fa * (size_t)nf, ilv ? d_out + (size_t)na * (size_t)nbytes : d_out + fa * (size_t)nbytes,
-                                e->d_mid + fa * (size_t)MP_WORDS, e->d_planes + fa * (size_t)EP_WORDS, nbytes, n_frames, fresh, io, e->sub[1], 2,
-                                nullptr, nullptr, frames);
-        // whatever was queued, the caller's stream (and the handle's next call) orders behind it
-        for (int i = 0; i < 2; i++)
-            if (hipEventRecord(e->ev_join[i], e->sub[i]) != hipSuccess || hipStreamWaitEvent(stream, e->ev_join[i], 0) != hipSuccess) {
-                g_last_hip = (int)hipGetLastError();
-                if (rc == LC3GPU_OK) rc = LC3GPU_EHIP;
-            }
-        if (rc == LC3GPU_OK) rc = e->stage_record_all(stream);
+        const bool stagger = lc3_split_stagger() == 1;
+        rc = e->split_run(
+            stream, stagger,
+            [&](hipStream_t s, int chain) {
+                return encode_kernels(e, h, first, na, d_pcm, d_out, e->d_mid, e->d_planes, nbytes, n_frames, fresh, io, s, chain,
+                                      stagger ? e->ev_stage : nullptr, nullptr, frames);
+            },
+            [&](hipStream_t s, int chain) {
+                return encode_kernels(e, h, first + na, n - na, ilv ? d_pcm + na : d_pcm + fa * (size_t)nf,
+                                      ilv ? d_out + (size_t)na * (size_t)nbytes : d_out + fa * (size_t)nbytes, e->d_mid + fa * (size_t)MP_WORDS,
+                                      e->d_planes + fa * (size_t)EP_WORDS, nbytes, n_frames, fresh, io, s, chain, nullptr, nullptr, frames);
+            });
     }
-    if (rc) {
-        e->timer.rollback(t0);
-        (void)e->order_end(stream, parts == 2);
-        return rc;
-    }
-    for (int i = first; i < first + n; i++) e->fresh_mask[(size_t)i] = 0;
-    return e->order_end(stream, parts == 2);
+    if (rc == LC3GPU_OK)
+        for (int i = first; i < first + n; i++) e->fresh_mask[(size_t)i] = 0;
+    return call.end(rc, parts == 2);
 }
 
 int lc3gpu_encode_layout(lc3gpu_encoder *e, int layout, const int16_t *d_pcm, uint8_t *d_out, int nbytes, int n_frames, void *stream) {
@@ -3497,8 +3608,8 @@ int lc3gpu_encode_range(lc3gpu_encoder *e, int first_channel, int n_channels, co
 }
 
 // A list of channels (lc3_dev_list.h): everything is checked on the host before anything is queued; then the list goes to the device in
-// stream order (HandleCommon::list_upload) and the four kernels run over the n_list compact streams, fresh and carried channels in the
-// same launch.  Always one part (no LC3GPU_SPLIT).
+// stream order (HandleCommon::list_upload) and the four kernels run over the n_list compact streams (planar compact buffers; the streams
+// are the channels of the list's entries), fresh and carried channels in the same launch.  Always one part (no LC3GPU_SPLIT).
 int lc3gpu_encode_list(lc3gpu_encoder *e, const int32_t *channels, int n_list, const int16_t *d_pcm, uint8_t *d_out, int nbytes, int n_frames,
                        void *stream_) {
     if (!e || e->mixed || n_list < 0) return LC3GPU_EINVAL;
@@ -3509,22 +3620,34 @@ int lc3gpu_encode_list(lc3gpu_encoder *e, const int32_t *channels, int n_list, c
     if (rc) return rc;
     LC3_ON_DEVICE(e);
     hipStream_t stream = (hipStream_t)stream_;
+    const HostCfg &h = e->h;
     const size_t frames = (size_t)n_list * (size_t)n_frames;
-    rc = e->order_begin(stream);
+    BatchCall call(*e, stream);
+    rc = call.begin();
     if (rc == LC3GPU_OK) rc = encoder_reserve_planes(e, frames, stream);
     if (rc == LC3GPU_OK) rc = e->list_upload(channels, n_list, e->fresh_mask, stream);
     if (rc) return rc;
     const lc3_io io = {0, nullptr};
-    const size_t t0 = e->timer.used;
-    e->timer.arm();
-    rc = encode_kernels(e, e->h, 0, n_list, d_pcm, d_out, e->d_mid, e->d_planes, nbytes, n_frames, 0, io, stream, 0, nullptr, nullptr, frames, e->d_list);
-    if (rc) {
-        e->timer.rollback(t0);
-        (void)e->order_end(stream);
-        return rc;
-    }
-    for (int i = 0; i < n_list; i++) e->fresh_mask[(size_t)channels[i]] = 0;
-    return e->order_end(stream);
+    const dim3 wg_grid = lc3_stream_grid(n_list), wg_block(64 * LC3_WG_WAVES);
+    call.arm();
+    rc = encode_stages(
+        e, stream, 0, nullptr,
+        [&] {
+            LC3_LAUNCH_HEADLINE(lc3_enc_front_list_kernel, h, wg_grid, wg_block, lc3_lds_pad(0), stream, e->d_states, e->d_list(), n_list, d_pcm, e->d_mid,
+                                e->d_planes, nbytes, n_frames, e->spec_flags);
+            return LC3GPU_OK;
+        },
+        [&] { return vq_launch(e, h, e->d_mid, e->d_planes, frames, stream); },
+        [&] {
+            LC3_LAUNCH_HEADLINE(lc3_enc_back_list_kernel, h, wg_grid, wg_block, lc3_lds_pad(1), stream, e->d_states, e->d_list(), n_list,
+                                (const float *)e->d_mid, e->d_planes, nbytes, n_frames, e->spec_flags | lc3_prep_symbols_flag(frames));
+            return LC3GPU_OK;
+        },
+        [&] { return symbols_launch(h, e->d_planes, frames, frames, stream); },
+        [&] { return pack_launch(e, h, e->d_planes, d_out, nbytes, frames, n_frames, io, frames, stream); });
+    if (rc == LC3GPU_OK)
+        for (int i = 0; i < n_list; i++) e->fresh_mask[(size_t)channels[i]] = 0;
+    return call.end(rc);
 }
 
 // the named channels are back in the constructed state from their next call on (no wait, no launch: lc3gpu_encoder_reset)
@@ -3539,11 +3662,6 @@ int lc3gpu_encoder_reset_channels(lc3gpu_encoder *e, const int32_t *channels, in
 // A frame size per frame (lc3_dev_enc_vbr.h): the four encoder stages as lc3gpu_encode runs them, with the sized front half, back half and
 // packer; the vector quantiser and the symbol preparation do not look at the size.  Always one part (no LC3GPU_SPLIT), always the
 // one-lane-per-frame packer (no producer / consumer pair).
-#define LC3_LAUNCH_VBR(kern, h, grid, block, lds, stream, ...)                                                                   \
-    do {                                                                                                                        \
-        if ((h).view == 1) hipLaunchKernelGGL(kern<lc3_cfg_48k10>, grid, block, lds, stream, lc3_cfg_slot<lc3_cfg_48k10>{(h).slot}, __VA_ARGS__); \
-        else hipLaunchKernelGGL(kern<lc3_cfg_any>, grid, block, lds, stream, lc3_cfg_slot<lc3_cfg_any>{(h).slot}, __VA_ARGS__);                 \
-    } while (0)
 int lc3gpu_encode_vbr(lc3gpu_encoder *e, const int16_t *d_pcm, uint8_t *d_out, const uint16_t *d_nbytes, int slot_bytes, int n_frames,
                       void *stream_) {
     if (!e || e->mixed || !d_pcm || !d_out || !d_nbytes) return LC3GPU_EINVAL;
@@ -3554,7 +3672,8 @@ int lc3gpu_encode_vbr(lc3gpu_encoder *e, const int16_t *d_pcm, uint8_t *d_out, c
     const HostCfg &h = e->h;
     const int n = e->num_channels;
     const size_t frames = (size_t)n * (size_t)n_frames;
-    int rc = e->order_begin(stream);
+    BatchCall call(*e, stream);
+    int rc = call.begin();
     if (rc == LC3GPU_OK) rc = encoder_reserve_planes(e, frames, stream);
     if (rc == LC3GPU_OK && !e->d_vbr_clamps) {
         HIP_TRY(hipMalloc((void **)&e->d_vbr_clamps, sizeof(unsigned long long)));
@@ -3564,62 +3683,32 @@ int lc3gpu_encode_vbr(lc3gpu_encoder *e, const int16_t *d_pcm, uint8_t *d_out, c
     int fresh = 1;
     for (int i = 0; i < n; i++) fresh &= e->fresh_mask[(size_t)i];
     if (!fresh && (rc = encoder_materialise(e, 0, n, stream)) != 0) return rc;
-    auto launched = [] {
-        const hipError_t er = hipGetLastError();
-        if (er == hipSuccess) return LC3GPU_OK;
-        g_last_hip = (int)er;
-        return LC3GPU_EHIP;
-    };
-    const size_t t0 = e->timer.used;
-    e->timer.arm();
-    const dim3 wg_grid((unsigned)((n + LC3_WG_WAVES - 1) / LC3_WG_WAVES)), wg_block(64 * LC3_WG_WAVES);
-    e->timer.mark(stream, -1, 0);
-    LC3_LAUNCH_VBR(lc3_enc_front_vbr_kernel, h, wg_grid, wg_block, lc3_lds_pad(0), stream, e->d_states, n, d_pcm, e->d_mid, e->d_planes, d_nbytes,
-                   slot_bytes, e->d_vbr_clamps, n_frames, fresh, e->spec_flags);
-    rc = launched();
-    if (rc == LC3GPU_OK) {
-        e->timer.mark(stream, 0, 0);
-        rc = e->stage_record(LC3GPU_ENC_STAGE_FRONT, stream);
-    }
-    if (rc == LC3GPU_OK) {
-        hipLaunchKernelGGL(lc3_sns_vq_kernel, dim3((unsigned)((frames + 255) / 256)), dim3(256), 0, stream, h.c.nb, e->d_mid, e->d_planes,
-                           (int)frames, e->spec_flags);
-        rc = launched();
-    }
-    if (rc == LC3GPU_OK) {
-        e->timer.mark(stream, 1, 0);
-        rc = e->stage_record(LC3GPU_ENC_STAGE_VQ, stream);
-    }
-    if (rc == LC3GPU_OK) {
-        LC3_LAUNCH_VBR(lc3_enc_back_vbr_kernel, h, wg_grid, wg_block, lc3_lds_pad(1), stream, e->d_states, n, (const float *)e->d_mid, e->d_planes,
-                       d_nbytes, slot_bytes, n_frames, e->spec_flags | lc3_prep_symbols_flag(frames));
-        rc = launched();
-    }
-    if (rc == LC3GPU_OK) {
-        e->timer.mark(stream, 2, 0);
-        rc = e->stage_record(LC3GPU_ENC_STAGE_BACK, stream);
-    }
-    if (rc == LC3GPU_OK && lc3_prep_symbols_mode(frames) == 2) {
-        const size_t wgs = (frames + LC3_WG_WAVES - 1) / LC3_WG_WAVES;
-        LC3_LAUNCH_CFG(lc3_symbols_kernel, h, dim3((unsigned)(wgs < lc3_recon_grid() ? wgs : lc3_recon_grid())), dim3(64 * LC3_WG_WAVES), 0, stream,
-                       e->d_planes, (int)frames);
-        rc = launched();
-    }
-    if (rc == LC3GPU_OK) {
-        const unsigned fpb = lc3_frame_block_fit(LC3_PACK_LDS_FIXED + 256 * sizeof(int), (size_t)slot_bytes);
-        const size_t lds = LC3_PACK_LDS_FIXED + (((size_t)fpb * (size_t)slot_bytes + 3) & ~(size_t)3) + 4;  // + the packer's sink byte
-        hipLaunchKernelGGL(lc3_pack_vbr_kernel, dim3((unsigned)((frames + fpb - 1) / fpb)), dim3(fpb), lds, stream, h.c.ne,
-                           (const int32_t *)e->d_planes, d_out, d_nbytes, slot_bytes, (int)frames);
-        rc = launched();
-    }
-    if (rc == LC3GPU_OK) e->timer.mark(stream, 3, 0);
-    if (rc) {
-        e->timer.rollback(t0);
-        (void)e->order_end(stream);
-        return rc;
-    }
-    for (int i = 0; i < n; i++) e->fresh_mask[(size_t)i] = 0;
-    return e->order_end(stream);
+    const dim3 wg_grid = lc3_stream_grid(n), wg_block(64 * LC3_WG_WAVES);
+    call.arm();
+    rc = encode_stages(
+        e, stream, 0, nullptr,
+        [&] {
+            LC3_LAUNCH_HEADLINE(lc3_enc_front_vbr_kernel, h, wg_grid, wg_block, lc3_lds_pad(0), stream, e->d_states, n, d_pcm, e->d_mid, e->d_planes,
+                                d_nbytes, slot_bytes, e->d_vbr_clamps, n_frames, fresh, e->spec_flags);
+            return LC3GPU_OK;
+        },
+        [&] { return vq_launch(e, h, e->d_mid, e->d_planes, frames, stream); },
+        [&] {
+            LC3_LAUNCH_HEADLINE(lc3_enc_back_vbr_kernel, h, wg_grid, wg_block, lc3_lds_pad(1), stream, e->d_states, n, (const float *)e->d_mid,
+                                e->d_planes, d_nbytes, slot_bytes, n_frames, e->spec_flags | lc3_prep_symbols_flag(frames));
+            return LC3GPU_OK;
+        },
+        [&] { return symbols_launch(h, e->d_planes, frames, frames, stream); },
+        [&] {
+            const unsigned fpb = lc3_frame_block_fit(LC3_PACK_LDS_FIXED + 256 * sizeof(int), (size_t)slot_bytes);
+            const size_t lds = LC3_PACK_LDS_FIXED + (((size_t)fpb * (size_t)slot_bytes + 3) & ~(size_t)3) + 4;  // + the packer's sink byte
+            hipLaunchKernelGGL(lc3_pack_vbr_kernel, dim3((unsigned)((frames + fpb - 1) / fpb)), dim3(fpb), lds, stream, h.c.ne,
+                               (const int32_t *)e->d_planes, d_out, d_nbytes, slot_bytes, (int)frames);
+            return LC3GPU_OK;
+        });
+    if (rc == LC3GPU_OK)
+        for (int i = 0; i < n; i++) e->fresh_mask[(size_t)i] = 0;
+    return call.end(rc);
 }
 int lc3gpu_encoder_size_clamps(lc3gpu_encoder *e, uint64_t *out) {
     if (!e || !out) return LC3GPU_EINVAL;
@@ -3634,23 +3723,18 @@ int lc3gpu_encoder_size_clamps(lc3gpu_encoder *e, uint64_t *out) {
     return LC3GPU_OK;
 }
 
-// every stream of a mixed-configuration handle, ONE launch per kernel
+// every stream of a mixed-configuration handle, ONE launch per kernel.  The symbol preparation is the back half's (lc3_prep_symbols_flag,
+// mixed) where a uniform handle has a kernel of its own for it
 int lc3gpu_encode_mixed(lc3gpu_encoder *e, const int16_t *d_pcm, uint8_t *d_out, int n_frames, void *stream_) {
     if (!e || !e->mixed || !d_pcm || !d_out) return LC3GPU_EINVAL;
     if (n_frames <= 0) return LC3GPU_ELENGTH;
     if (((uintptr_t)d_pcm & 3u) != 0) return LC3GPU_EINVAL;
     LC3_ON_DEVICE(e);
     hipStream_t stream = (hipStream_t)stream_;
-    int rc = e->order_begin(stream);
-    if (rc) return rc;
-    lc3_groups G;
-    unsigned wg_stream, wg_frame;
-    size_t frames;
-    int max_nbytes;
-    fill_groups(*e, n_frames, 256u, G, wg_stream, wg_frame, frames, max_nbytes);
-    const unsigned fpb = lc3_frame_block_fit(LC3_PACK_LDS_FIXED, (size_t)max_nbytes);
-    fill_groups(*e, n_frames, fpb, G, wg_stream, wg_frame, frames, max_nbytes);
-    rc = encoder_reserve_planes(e, frames, stream);
+    const size_t frames = (size_t)e->num_channels * (size_t)n_frames;
+    BatchCall call(*e, stream);
+    int rc = call.begin();
+    if (rc == LC3GPU_OK) rc = encoder_reserve_planes(e, frames, stream);
     if (rc) return rc;
     int fresh = 1;
     for (uint8_t m : e->fresh_mask) fresh &= m;
@@ -3659,52 +3743,27 @@ int lc3gpu_encode_mixed(lc3gpu_encoder *e, const int16_t *d_pcm, uint8_t *d_out,
         if (rc) return rc;
     }
     lc3_io io = {0, e->d_tab};
-    const size_t t0 = e->timer.used;
-    e->timer.begin(stream);
-    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_enc_front_mixed_kernel), dim3(wg_stream), dim3(64 * LC3_WG_WAVES), 0, stream, G, e->d_states, d_pcm, e->d_mid,
-                       e->d_planes, n_frames, fresh, io, e->spec_flags);
-    LC3_LAUNCH_CHECK(e, stream, t0);
-    e->timer.mark(stream, 0);
-    LC3_STAGE_RECORD(e, LC3GPU_ENC_STAGE_FRONT, stream, t0);
-    lc3_groups G256;  // the vector quantiser runs 256 frames per workgroup
-    {
-        unsigned a, b;
-        size_t f;
-        int m;
-        fill_groups(*e, n_frames, 256u, G256, a, b, f, m);
-        hipLaunchKernelGGL(lc3_sns_vq_mixed_kernel, dim3(b), dim3(256), 0, stream, G256, e->d_mid, e->d_planes, n_frames, e->spec_flags);
-        LC3_LAUNCH_CHECK(e, stream, t0);
-    }
-    e->timer.mark(stream, 1);
-    LC3_STAGE_RECORD(e, LC3GPU_ENC_STAGE_VQ, stream, t0);
-    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_enc_back_mixed_kernel), dim3(wg_stream), dim3(64 * LC3_WG_WAVES), 0, stream, G, e->d_states,
-                       (const float *)e->d_mid, e->d_planes, n_frames, e->spec_flags | lc3_prep_symbols_flag((size_t)e->num_channels * (size_t)n_frames, true));
-    LC3_LAUNCH_CHECK(e, stream, t0);
-    e->timer.mark(stream, 2);
-    LC3_STAGE_RECORD(e, LC3GPU_ENC_STAGE_BACK, stream, t0);
-    if (lc3_prep_symbols_mode((size_t)e->num_channels * (size_t)n_frames) == 0 && lc3_pack_pc_enabled()) {
-        // full batches: the producer / consumer pairs (as lc3gpu_encode does), a group table of their own number of frames per workgroup
-        if ((rc = lc3_pack_pc_optin()) != LC3GPU_OK) {
-            e->timer.rollback(t0);
-            (void)e->order_end(stream);
-            return rc;
-        }
-        const unsigned pfpb = lc3_pack_pc_fpb(max_nbytes);
-        lc3_groups Gp;
-        unsigned a, b;
-        size_t f;
-        int m;
-        fill_groups(*e, n_frames, pfpb, Gp, a, b, f, m);
-        hipLaunchKernelGGL(lc3_pack_pc_mixed_kernel, dim3(b), dim3(2 * pfpb), lc3_pack_pc_lds(pfpb, max_nbytes), stream, Gp, (const int32_t *)e->d_planes,
-                           d_out, n_frames, io, e->d_pc_timeouts);
-    } else {
-        const size_t lds = LC3_PACK_LDS_FIXED + (((size_t)fpb * (size_t)max_nbytes + 3) & ~(size_t)3) + 4;
-        hipLaunchKernelGGL(lc3_pack_mixed_kernel, dim3(wg_frame), dim3(fpb), lds, stream, G, (const int32_t *)e->d_planes, d_out, n_frames, io);
-    }
-    LC3_LAUNCH_CHECK(e, stream, t0);
-    e->timer.mark(stream, 3);
-    e->fresh_mask.assign((size_t)e->num_channels, 0);
-    return e->order_end(stream);
+    const HandleGroups groups{*e, n_frames};
+    GroupTable t;  // (the wave-per-stream kernels' workgroups do not depend on the frames per workgroup of the others)
+    groups(256u, t);
+    call.arm();
+    rc = encode_stages(
+        e, stream, 0, nullptr,
+        [&] {
+            hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_enc_front_mixed_kernel), dim3(t.wg_stream), dim3(64 * LC3_WG_WAVES), 0, stream, t.G, e->d_states, d_pcm,
+                               e->d_mid, e->d_planes, n_frames, fresh, io, e->spec_flags);
+            return LC3GPU_OK;
+        },
+        [&] { return vq_mixed_launch(e, groups, n_frames, stream); },
+        [&] {
+            hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_enc_back_mixed_kernel), dim3(t.wg_stream), dim3(64 * LC3_WG_WAVES), 0, stream, t.G, e->d_states,
+                               (const float *)e->d_mid, e->d_planes, n_frames, e->spec_flags | lc3_prep_symbols_flag(frames, true));
+            return LC3GPU_OK;
+        },
+        [] { return LC3GPU_OK; },
+        [&] { return pack_mixed_launch(e, groups, e->max_nbytes, d_out, n_frames, io, frames, stream); });
+    if (rc == LC3GPU_OK) e->fresh_mask.assign((size_t)e->num_channels, 0);
+    return call.end(rc);
 }
 
 // A list of a mixed handle's streams: everything is checked on the host before anything is queued; the plan (lc3_host_mixed_list.h) is
@@ -3723,64 +3782,36 @@ int lc3gpu_encode_mixed_list(lc3gpu_encoder *e, const int32_t *channels, int n_l
     LC3_ON_DEVICE(e);
     hipStream_t stream = (hipStream_t)stream_;
     const size_t frames = (size_t)n_list * (size_t)n_frames;
-    uint8_t *slot = nullptr;
-    rc = e->order_begin(stream);
-    if (rc == LC3GPU_OK) rc = encoder_reserve_planes(e, frames, stream);
-    if (rc == LC3GPU_OK) rc = e->mlist_slot(&slot);
-    if (rc) return rc;
     lc3_mlist_plan P;
-    lc3_mlist_build(e->mlist_groups.data(), (int)e->mlist_groups.size(), e->mlist_streams.data(), e->fresh_mask.data(), channels, n_list,
-                    (int32_t *)slot, (lc3_stream_io *)(slot + HandleCommon::mlist_tab_offset(n_list)), P);
-    if ((rc = e->mlist_upload(n_list, stream)) != LC3GPU_OK) return rc;
-    const int32_t *d_entries = (const int32_t *)e->d_mlist;
-    const lc3_io io = {0, (const lc3_stream_io *)(e->d_mlist + HandleCommon::mlist_tab_offset(n_list))};
-    const lc3_mlist_group *mg = e->mlist_groups.data();
-    const int ng = (int)e->mlist_groups.size();
-    const unsigned fpb = lc3_frame_block_fit(LC3_PACK_LDS_FIXED, (size_t)P.max_nbytes);
-    lc3_groups G;
-    unsigned wg_stream, wg_frame;
-    lc3_mlist_groups(mg, ng, P, n_frames, (unsigned)LC3_WG_WAVES, fpb, G, wg_stream, wg_frame);
-    const size_t t0 = e->timer.used;
-    e->timer.begin(stream);
-    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_enc_front_mixed_list_kernel), dim3(wg_stream), dim3(64 * LC3_WG_WAVES), 0, stream, G, e->d_states, d_entries,
-                       d_pcm, e->d_mid, e->d_planes, n_frames, io, e->spec_flags);
-    LC3_LAUNCH_CHECK(e, stream, t0);
-    e->timer.mark(stream, 0);
-    LC3_STAGE_RECORD(e, LC3GPU_ENC_STAGE_FRONT, stream, t0);
-    {
-        lc3_groups G256;  // the vector quantiser runs 256 frames per workgroup
-        unsigned a, b;
-        lc3_mlist_groups(mg, ng, P, n_frames, (unsigned)LC3_WG_WAVES, 256u, G256, a, b);
-        hipLaunchKernelGGL(lc3_sns_vq_mixed_kernel, dim3(b), dim3(256), 0, stream, G256, e->d_mid, e->d_planes, n_frames, e->spec_flags);
-        LC3_LAUNCH_CHECK(e, stream, t0);
-    }
-    e->timer.mark(stream, 1);
-    LC3_STAGE_RECORD(e, LC3GPU_ENC_STAGE_VQ, stream, t0);
-    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_enc_back_mixed_list_kernel), dim3(wg_stream), dim3(64 * LC3_WG_WAVES), 0, stream, G, e->d_states, d_entries,
-                       (const float *)e->d_mid, e->d_planes, n_frames, e->spec_flags | lc3_prep_symbols_flag(frames, true));
-    LC3_LAUNCH_CHECK(e, stream, t0);
-    e->timer.mark(stream, 2);
-    LC3_STAGE_RECORD(e, LC3GPU_ENC_STAGE_BACK, stream, t0);
-    if (lc3_prep_symbols_mode(frames) == 0 && lc3_pack_pc_enabled()) {  // full batches: the producer / consumer pairs, as lc3gpu_encode_mixed
-        if ((rc = lc3_pack_pc_optin()) != LC3GPU_OK) {
-            e->timer.rollback(t0);
-            (void)e->order_end(stream);
-            return rc;
-        }
-        const unsigned pfpb = lc3_pack_pc_fpb(P.max_nbytes);
-        lc3_groups Gp;
-        unsigned a, b;
-        lc3_mlist_groups(mg, ng, P, n_frames, (unsigned)LC3_WG_WAVES, pfpb, Gp, a, b);
-        hipLaunchKernelGGL(lc3_pack_pc_mixed_kernel, dim3(b), dim3(2 * pfpb), lc3_pack_pc_lds(pfpb, P.max_nbytes), stream, Gp, (const int32_t *)e->d_planes,
-                           d_out, n_frames, io, e->d_pc_timeouts);
-    } else {
-        const size_t lds = LC3_PACK_LDS_FIXED + (((size_t)fpb * (size_t)P.max_nbytes + 3) & ~(size_t)3) + 4;
-        hipLaunchKernelGGL(lc3_pack_mixed_kernel, dim3(wg_frame), dim3(fpb), lds, stream, G, (const int32_t *)e->d_planes, d_out, n_frames, io);
-    }
-    LC3_LAUNCH_CHECK(e, stream, t0);
-    e->timer.mark(stream, 3);
-    for (int i = 0; i < n_list; i++) e->fresh_mask[(size_t)e->streams[(size_t)channels[i]].internal] = 0;
-    return e->order_end(stream);
+    BatchCall call(*e, stream);
+    rc = call.begin();
+    if (rc == LC3GPU_OK) rc = encoder_reserve_planes(e, frames, stream);
+    if (rc == LC3GPU_OK) rc = e->mlist_send(channels, n_list, e->fresh_mask.data(), stream, P);
+    if (rc) return rc;
+    const int32_t *d_entries = e->d_mlist_entries();
+    const lc3_io io = {0, e->d_mlist_tab(n_list)};
+    const ListGroups groups{*e, P, n_frames};
+    GroupTable t;  // (as in lc3gpu_encode_mixed: the wave-per-stream kernels read wg_stream only)
+    groups(256u, t);
+    call.arm();
+    rc = encode_stages(
+        e, stream, 0, nullptr,
+        [&] {
+            hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_enc_front_mixed_list_kernel), dim3(t.wg_stream), dim3(64 * LC3_WG_WAVES), 0, stream, t.G, e->d_states,
+                               d_entries, d_pcm, e->d_mid, e->d_planes, n_frames, io, e->spec_flags);
+            return LC3GPU_OK;
+        },
+        [&] { return vq_mixed_launch(e, groups, n_frames, stream); },
+        [&] {
+            hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_enc_back_mixed_list_kernel), dim3(t.wg_stream), dim3(64 * LC3_WG_WAVES), 0, stream, t.G, e->d_states,
+                               d_entries, (const float *)e->d_mid, e->d_planes, n_frames, e->spec_flags | lc3_prep_symbols_flag(frames, true));
+            return LC3GPU_OK;
+        },
+        [] { return LC3GPU_OK; },
+        [&] { return pack_mixed_launch(e, groups, P.max_nbytes, d_out, n_frames, io, frames, stream); });
+    if (rc == LC3GPU_OK)
+        for (int i = 0; i < n_list; i++) e->fresh_mask[(size_t)e->streams[(size_t)channels[i]].internal] = 0;
+    return call.end(rc);
 }
 
 static int encode_frame_host(lc3gpu_encoder *e, int channel_index, const int16_t *samples_in, int n_samples,
@@ -3976,69 +4007,131 @@ int lc3gpu_decoder_reset_channels(lc3gpu_decoder *d, const int32_t *channels, in
     return LC3GPU_OK;
 }
 
-// the decoder kernels of channels [first, first + n) (internal order) on `stream`; buffers, flags and planes are those of this range
-static int decode_kernels(lc3gpu_decoder *d, const HostCfg &h, int first, int n, const uint8_t *d_in, const uint8_t *d_bad, int16_t *d_pcm,
-                          int32_t *planes, int nbytes, int n_frames, lc3_io io, int mode, hipStream_t stream, int chain, int fresh = 0,
-                          const int32_t *d_list = nullptr) {  // d_list (a list call): the n streams are the channels of the list's entries
-    // stage 1: parse all n * n_frames frames, one lane each (stateless); stage 2: synthesis, one wave per stream
-    const size_t frames = (size_t)n * (size_t)n_frames;
-    // frames per workgroup: as many as fit the default 64 KB of dynamic LDS (tables + 64 B of scale factors and nbytes of
-    // frame data per frame)
-    const unsigned fpb = lc3_frame_block_fit(LC3_PARSE_LDS_FIXED, (size_t)(64 + nbytes));
-    const size_t lds = LC3_PARSE_LDS_FIXED + (size_t)fpb * (size_t)(64 + nbytes);
+// the synthesis of a list call / a sized call: a template kernel with a LATE flag (reconstruction in the synthesis kernel: lc3_recon_mode),
+// for the headline view and the run-time view
+#define LC3_LAUNCH_SYNTH_LATE(kern, LATE, h, grid, block, lds, stream, ...)                                                              \
+    do {                                                                                                                                \
+        if ((h).view == 1) hipLaunchKernelGGL((kern<lc3_cfg_48k10, LATE>), grid, block, lds, stream, lc3_cfg_slot<lc3_cfg_48k10>{(h).slot}, __VA_ARGS__); \
+        else hipLaunchKernelGGL((kern<lc3_cfg_any, LATE>), grid, block, lds, stream, lc3_cfg_slot<lc3_cfg_any>{(h).slot}, __VA_ARGS__);                 \
+    } while (0)
+#define LC3_LAUNCH_SYNTH(kern, h, late, grid, block, stream, ...)                                            \
+    do {                                                                                                    \
+        if (late) LC3_LAUNCH_SYNTH_LATE(kern, 1, h, grid, block, 0, stream, __VA_ARGS__);                    \
+        else LC3_LAUNCH_SYNTH_LATE(kern, 0, h, grid, block, lc3_lds_pad(2), stream, __VA_ARGS__);            \
+    } while (0)
+
+extern "C++" {
+// The decoder's stage sequence (as encode_stages): parser (one lane per frame, stateless) -> where mode says so (LC3_RECON_WAVE) the
+// reconstruction and TNS kernels -> synthesis (one wave per stream)
+template <class Parse, class Recon, class Tns, class Synth>
+static int decode_stages(lc3gpu_decoder *d, hipStream_t stream, int chain, int mode, Parse parse, Recon recon, Tns tns, Synth synth) {
+    int rc;
     d->timer.mark(stream, -1, chain);
+    if ((rc = launch_result(parse())) != LC3GPU_OK) return rc;
+    d->timer.mark(stream, 0, chain);
+    if (mode == LC3_RECON_WAVE) {
+        if ((rc = launch_result(recon())) != LC3GPU_OK) return rc;
+        d->timer.mark(stream, 1, chain);
+        if ((rc = launch_result(tns())) != LC3GPU_OK) return rc;
+        d->timer.mark(stream, 2, chain);
+    }
+    if (chain == 0 && (rc = d->stage_record(LC3GPU_DEC_STAGE_PARSE, stream)) != LC3GPU_OK) return rc;
+    if ((rc = launch_result(synth())) != LC3GPU_OK) return rc;
+    d->timer.mark(stream, 3, chain);
+    return LC3GPU_OK;
+}
+}  // extern "C++"
+
+// ---- the launches the decoder's call variants share (uniform handles: `frames` frames in `planes`)
+// the parser: the producer / consumer pairs where the parsing lane reconstructs the spectrum (full batches), else one lane per frame
+static int parse_launch(lc3gpu_decoder *d, const HostCfg &h, const uint8_t *d_in, const uint8_t *d_bad, int32_t *planes, int nbytes, size_t frames,
+                        int n_frames, lc3_io io, int mode, hipStream_t stream) {
     if (mode == LC3_RECON_LANE && lc3_parse_pc_enabled()) {
-        if (!d->pc_optin_done) {  // (once per handle: the opt-in itself takes a process-wide lock)
-            int rc = lc3_parse_pc_optin();
-            if (rc) return rc;
-            d->pc_optin_done = true;
-        }
+        const int rc = pc_optin_once(*d, lc3_parse_pc_optin);
+        if (rc) return rc;
         const unsigned pfpb = lc3_parse_pc_fpb(nbytes);
         LC3_LAUNCH_CFG(lc3_parse_pc_kernel, h, dim3((unsigned)((frames + pfpb - 1) / pfpb)), dim3(2 * pfpb), lc3_parse_pc_lds(pfpb, nbytes), stream,
                        d_in, d_bad, planes, nbytes, (int)frames, n_frames, io, d->d_pc_timeouts);
-    } else
+    } else {
+        // frames per workgroup: as many as fit the default 64 KB of dynamic LDS (tables + 64 B of scale factors and nbytes of
+        // frame data per frame)
+        const unsigned fpb = lc3_frame_block_fit(LC3_PARSE_LDS_FIXED, (size_t)(64 + nbytes));
+        const size_t lds = LC3_PARSE_LDS_FIXED + (size_t)fpb * (size_t)(64 + nbytes);
         LC3_LAUNCH_CFG(lc3_parse_kernel, h, dim3((unsigned)((frames + fpb - 1) / fpb)), dim3(fpb), lds, stream, d_in, d_bad, planes, nbytes,
                        (int)frames, n_frames, io, mode);
-    HIP_TRY(hipGetLastError());
-    d->timer.mark(stream, 0, chain);
-    if (mode == LC3_RECON_WAVE) {
-        const size_t wgs = (frames + LC3_WG_WAVES - 1) / LC3_WG_WAVES;
-        LC3_LAUNCH_CFG(lc3_recon_kernel, h, dim3((unsigned)(wgs < lc3_recon_grid() ? wgs : lc3_recon_grid())), dim3(64 * LC3_WG_WAVES), 0, stream,
-                       planes, nbytes, (int)frames);
-        HIP_TRY(hipGetLastError());
-        d->timer.mark(stream, 1, chain);
-        LC3_LAUNCH_CFG(lc3_tns_kernel, h, dim3((unsigned)((frames + LC3_TNS_FPB - 1) / LC3_TNS_FPB)), dim3(LC3_TNS_FPB), LC3_TNS_LDS, stream,
-                       planes, (int)frames);
-        HIP_TRY(hipGetLastError());
-        d->timer.mark(stream, 2, chain);
     }
-    if (chain == 0) {
-        const int rc_stage = d->stage_record(LC3GPU_DEC_STAGE_PARSE, stream);
-        if (rc_stage) return rc_stage;
-    }
-    if (d_list) {
-        const dim3 grid((unsigned)((n + LC3_WG_WAVES - 1) / LC3_WG_WAVES)), block(64 * LC3_WG_WAVES);
-        const int32_t *pl = planes;
-        if (mode == LC3_RECON_LATE) {
-            if (h.view == 1) hipLaunchKernelGGL((lc3_decode_list_kernel<lc3_cfg_48k10, 1>), grid, block, 0, stream, lc3_cfg_slot<lc3_cfg_48k10>{h.slot},
-                                                d->d_states, d_list, n, pl, d_pcm, nbytes, n_frames);
-            else hipLaunchKernelGGL((lc3_decode_list_kernel<lc3_cfg_any, 1>), grid, block, 0, stream, lc3_cfg_slot<lc3_cfg_any>{h.slot}, d->d_states,
-                                    d_list, n, pl, d_pcm, nbytes, n_frames);
-        } else {
-            if (h.view == 1) hipLaunchKernelGGL((lc3_decode_list_kernel<lc3_cfg_48k10, 0>), grid, block, lc3_lds_pad(2), stream,
-                                                lc3_cfg_slot<lc3_cfg_48k10>{h.slot}, d->d_states, d_list, n, pl, d_pcm, nbytes, n_frames);
-            else hipLaunchKernelGGL((lc3_decode_list_kernel<lc3_cfg_any, 0>), grid, block, lc3_lds_pad(2), stream, lc3_cfg_slot<lc3_cfg_any>{h.slot},
-                                    d->d_states, d_list, n, pl, d_pcm, nbytes, n_frames);
-        }
-    } else if (mode == LC3_RECON_LATE)
-        LC3_LAUNCH_CFG(lc3_decode_late_kernel, h, dim3((unsigned)((n + LC3_WG_WAVES - 1) / LC3_WG_WAVES)), dim3(64 * LC3_WG_WAVES), 0,
-                       stream, d->d_states, first, n, (const int32_t *)planes, d_pcm, nbytes, n_frames, fresh, io);
-    else
-        LC3_LAUNCH_CFG(lc3_decode_kernel, h, dim3((unsigned)((n + LC3_WG_WAVES - 1) / LC3_WG_WAVES)), dim3(64 * LC3_WG_WAVES), lc3_lds_pad(2), stream,
-                       d->d_states, first, n, (const int32_t *)planes, d_pcm, nbytes, n_frames, fresh, io);
-    HIP_TRY(hipGetLastError());
-    d->timer.mark(stream, 3, chain);
     return LC3GPU_OK;
+}
+static int recon_launch(const HostCfg &h, int32_t *planes, int nbytes, size_t frames, hipStream_t stream) {
+    const size_t wgs = (frames + LC3_WG_WAVES - 1) / LC3_WG_WAVES;
+    LC3_LAUNCH_CFG(lc3_recon_kernel, h, dim3((unsigned)(wgs < lc3_recon_grid() ? wgs : lc3_recon_grid())), dim3(64 * LC3_WG_WAVES), 0, stream,
+                   planes, nbytes, (int)frames);
+    return LC3GPU_OK;
+}
+static int tns_launch(const HostCfg &h, int32_t *planes, size_t frames, hipStream_t stream) {
+    LC3_LAUNCH_CFG(lc3_tns_kernel, h, dim3((unsigned)((frames + LC3_TNS_FPB - 1) / LC3_TNS_FPB)), dim3(LC3_TNS_FPB), LC3_TNS_LDS, stream, planes,
+                   (int)frames);
+    return LC3GPU_OK;
+}
+// (the list synthesis in front of lc3_decode_late_kernel, for the listings: lc3_listing_order)
+static const void *const lc3_listing_order_dec[] = {
+    (const void *)lc3_decode_list_kernel<lc3_cfg_48k10, 1>, (const void *)lc3_decode_list_kernel<lc3_cfg_any, 1>,
+    (const void *)lc3_decode_list_kernel<lc3_cfg_48k10, 0>, (const void *)lc3_decode_list_kernel<lc3_cfg_any, 0>};
+// ... and their forms for a mixed handle, every stream or a list of them: `groups` builds the group table (GroupTable)
+extern "C++" {
+template <class Groups>
+static int parse_mixed_launch(lc3gpu_decoder *d, Groups groups, int max_nbytes, const uint8_t *d_in, const uint8_t *d_bad, int n_frames, lc3_io io,
+                              int mode, hipStream_t stream) {
+    GroupTable t;  // (a group table of the parser's own number of frames per workgroup)
+    if (mode == LC3_RECON_LANE && lc3_parse_pc_enabled()) {
+        const int rc = pc_optin_once(*d, lc3_parse_pc_optin);
+        if (rc) return rc;
+        const unsigned pfpb = lc3_parse_pc_fpb(max_nbytes);
+        groups(pfpb, t);
+        hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_parse_pc_mixed_kernel), dim3(t.wg_frame), dim3(2 * pfpb), lc3_parse_pc_lds(pfpb, max_nbytes), stream, t.G,
+                           d_in, d_bad, d->d_planes, n_frames, io, d->d_pc_timeouts);
+    } else {
+        const unsigned fpb = lc3_frame_block_fit(LC3_PARSE_LDS_FIXED, (size_t)(64 + max_nbytes));
+        const size_t lds = LC3_PARSE_LDS_FIXED + (size_t)fpb * (size_t)(64 + max_nbytes);
+        groups(fpb, t);
+        hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_parse_mixed_kernel), dim3(t.wg_frame), dim3(fpb), lds, stream, t.G, d_in, d_bad, d->d_planes, n_frames,
+                           io, mode);
+    }
+    return LC3GPU_OK;
+}
+template <class Groups>
+static int recon_mixed_launch(lc3gpu_decoder *d, Groups groups, int n_frames, hipStream_t stream) {
+    GroupTable t;
+    groups((unsigned)LC3_WG_WAVES, t);
+    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_recon_mixed_kernel), dim3(t.wg_frame), dim3(64 * LC3_WG_WAVES), 0, stream, t.G, d->d_planes, n_frames);
+    return LC3GPU_OK;
+}
+template <class Groups>
+static int tns_mixed_launch(lc3gpu_decoder *d, Groups groups, int n_frames, hipStream_t stream) {
+    GroupTable t;
+    groups((unsigned)LC3_TNS_FPB, t);
+    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_tns_mixed_kernel), dim3(t.wg_frame), dim3(LC3_TNS_FPB), LC3_TNS_LDS, stream, t.G, d->d_planes, n_frames);
+    return LC3GPU_OK;
+}
+}  // extern "C++"
+
+// the decoder kernels of channels [first, first + n) (internal order) of a uniform handle on `stream`; buffers, flags and planes are those
+// of this range
+static int decode_kernels(lc3gpu_decoder *d, const HostCfg &h, int first, int n, const uint8_t *d_in, const uint8_t *d_bad, int16_t *d_pcm,
+                          int32_t *planes, int nbytes, int n_frames, lc3_io io, int mode, hipStream_t stream, int chain, int fresh) {
+    const size_t frames = (size_t)n * (size_t)n_frames;
+    return decode_stages(
+        d, stream, chain, mode, [&] { return parse_launch(d, h, d_in, d_bad, planes, nbytes, frames, n_frames, io, mode, stream); },
+        [&] { return recon_launch(h, planes, nbytes, frames, stream); }, [&] { return tns_launch(h, planes, frames, stream); },
+        [&] {
+            if (mode == LC3_RECON_LATE)
+                LC3_LAUNCH_CFG(lc3_decode_late_kernel, h, lc3_stream_grid(n), dim3(64 * LC3_WG_WAVES), 0, stream, d->d_states, first, n,
+                               (const int32_t *)planes, d_pcm, nbytes, n_frames, fresh, io);
+            else
+                LC3_LAUNCH_CFG(lc3_decode_kernel, h, lc3_stream_grid(n), dim3(64 * LC3_WG_WAVES), lc3_lds_pad(2), stream, d->d_states, first, n,
+                               (const int32_t *)planes, d_pcm, nbytes, n_frames, fresh, io);
+            return LC3GPU_OK;
+        });
 }
 
 static int decode_launch(lc3gpu_decoder *d, const HostCfg &h, int first, int n, const uint8_t *d_in, const uint8_t *d_bad,
@@ -4063,47 +4156,35 @@ static int decode_launch(lc3gpu_decoder *d, const HostCfg &h, int first, int n, 
     int parts = (d->in_host_call || d->is_bound) ? 1 : lc3_split_parts(frames, n);
     const int na = parts == 2 ? lc3_split_point(n, n_frames) : n;
     if (parts == 2 && (na <= 0 || na >= n)) parts = 1;
-    int rc = d->order_begin(stream);
+    BatchCall call(*d, stream);
+    int rc = call.begin();
     if (rc == LC3GPU_OK) rc = decoder_reserve_planes(d, frames, stream);
     if (rc == LC3GPU_OK && parts == 2) rc = d->ensure_split();
     if (rc) return rc;
     lc3_io io = {layout == LC3GPU_LAYOUT_INTERLEAVED ? n : 0, nullptr};
     const int mode = lc3_recon_mode(frames, n_frames);
     if (mode == LC3_RECON_WAVE && (rc = lc3_tns_lds_optin()) != LC3GPU_OK) return rc;
-    const size_t t0 = d->timer.used;
-    d->timer.arm();
+    call.arm();
     if (parts == 1) {
         rc = decode_kernels(d, h, first, n, d_in, d_bad, d_pcm, d->d_planes, nbytes, n_frames, io, mode, stream, 0, fresh);
     } else {
-        rc = LC3GPU_OK;
-        if (hipEventRecord(d->ev_fork, stream) != hipSuccess || hipStreamWaitEvent(d->sub[0], d->ev_fork, 0) != hipSuccess ||
-            hipStreamWaitEvent(d->sub[1], d->ev_fork, 0) != hipSuccess) {
-            g_last_hip = (int)hipGetLastError();
-            rc = LC3GPU_EHIP;
-        }
         const size_t fa = (size_t)na * (size_t)n_frames;
         const bool ilv = layout == LC3GPU_LAYOUT_INTERLEAVED;
-        if (rc == LC3GPU_OK)
-            rc = decode_kernels(d, h, first, na, d_in, d_bad, d_pcm, d->d_planes, nbytes, n_frames, io, mode, d->sub[0], 1, fresh);
-        if (rc == LC3GPU_OK)
-            rc = decode_kernels(d, h, first + na, n - na, ilv ? d_in + (size_t)na * (size_t)nbytes : d_in + fa * (size_t)nbytes,
-                                d_bad ? (ilv ? d_bad + na : d_bad + fa) : nullptr, ilv ? d_pcm + na : d_pcm + fa * (size_t)nf,
-                                d->d_planes + fa * (size_t)LC3_PLANE_WORDS, nbytes, n_frames, io, mode, d->sub[1], 2, fresh);
-        for (int i = 0; i < 2; i++)
-            if (hipEventRecord(d->ev_join[i], d->sub[i]) != hipSuccess || hipStreamWaitEvent(stream, d->ev_join[i], 0) != hipSuccess) {
-                g_last_hip = (int)hipGetLastError();
-                if (rc == LC3GPU_OK) rc = LC3GPU_EHIP;
-            }
-        if (rc == LC3GPU_OK) rc = d->stage_record_all(stream);
+        rc = d->split_run(
+            stream, false,
+            [&](hipStream_t s, int chain) {
+                return decode_kernels(d, h, first, na, d_in, d_bad, d_pcm, d->d_planes, nbytes, n_frames, io, mode, s, chain, fresh);
+            },
+            [&](hipStream_t s, int chain) {
+                return decode_kernels(d, h, first + na, n - na, ilv ? d_in + (size_t)na * (size_t)nbytes : d_in + fa * (size_t)nbytes,
+                                      d_bad ? (ilv ? d_bad + na : d_bad + fa) : nullptr, ilv ? d_pcm + na : d_pcm + fa * (size_t)nf,
+                                      d->d_planes + fa * (size_t)LC3_PLANE_WORDS, nbytes, n_frames, io, mode, s, chain, fresh);
+            });
     }
-    if (rc) {
-        d->timer.rollback(t0);
-        (void)d->order_end(stream, parts == 2);
-        if (fresh) (void)decoder_init_states(d);  // (some of the kernels may have run: leave the handle in a defined state)
-        return rc;
-    }
-    if (fresh) d->fresh_set_all(0);
-    return d->order_end(stream, parts == 2);
+    if (rc == LC3GPU_OK && fresh) d->fresh_set_all(0);
+    const int rc_end = call.end(rc, parts == 2);
+    if (rc && fresh) (void)decoder_init_states(d);  // (some of the kernels may have run: leave the handle in a defined state)
+    return rc_end;
 }
 
 int lc3gpu_decode_layout(lc3gpu_decoder *d, int layout, const uint8_t *d_in, const uint8_t *d_bad, int16_t *d_pcm, int nbytes,
@@ -4131,24 +4212,29 @@ int lc3gpu_decode_list(lc3gpu_decoder *d, const int32_t *channels, int n_list, c
     if (rc) return rc;
     LC3_ON_DEVICE(d);
     hipStream_t stream = (hipStream_t)stream_;
+    const HostCfg &h = d->h;
     const size_t frames = (size_t)n_list * (size_t)n_frames;
     const int mode = lc3_recon_mode(frames, n_frames);
-    rc = d->order_begin(stream);
+    BatchCall call(*d, stream);
+    rc = call.begin();
     if (rc == LC3GPU_OK) rc = decoder_reserve_planes(d, frames, stream);
     if (rc == LC3GPU_OK && mode == LC3_RECON_WAVE) rc = lc3_tns_lds_optin();
     if (rc == LC3GPU_OK) rc = d->list_upload(channels, n_list, d->fresh_mask, stream);
     if (rc) return rc;
     const lc3_io io = {0, nullptr};
-    const size_t t0 = d->timer.used;
-    d->timer.arm();
-    rc = decode_kernels(d, d->h, 0, n_list, d_in, d_bad, d_pcm, d->d_planes, nbytes, n_frames, io, mode, stream, 0, 0, d->d_list);
-    if (rc) {  // (the channels noted fresh stay noted: whatever ran, their next call starts them from the constructed state)
-        d->timer.rollback(t0);
-        (void)d->order_end(stream);
-        return rc;
-    }
-    for (int i = 0; i < n_list; i++) d->fresh_clear(channels[i]);
-    return d->order_end(stream);
+    call.arm();
+    rc = decode_stages(
+        d, stream, 0, mode, [&] { return parse_launch(d, h, d_in, d_bad, d->d_planes, nbytes, frames, n_frames, io, mode, stream); },
+        [&] { return recon_launch(h, d->d_planes, nbytes, frames, stream); }, [&] { return tns_launch(h, d->d_planes, frames, stream); },
+        [&] {
+            LC3_LAUNCH_SYNTH(lc3_decode_list_kernel, h, mode == LC3_RECON_LATE, lc3_stream_grid(n_list), dim3(64 * LC3_WG_WAVES), stream, d->d_states,
+                             d->d_list(), n_list, (const int32_t *)d->d_planes, d_pcm, nbytes, n_frames);
+            return LC3GPU_OK;
+        });
+    // (on failure the channels noted fresh stay noted: whatever ran, their next call starts them from the constructed state)
+    if (rc == LC3GPU_OK)
+        for (int i = 0; i < n_list; i++) d->fresh_clear(channels[i]);
+    return call.end(rc);
 }
 
 // A frame size per frame on the decoder: the parser (one lane per frame), the reconstruction form lc3_recon_mode picks for the launch, the
@@ -4168,65 +4254,38 @@ int lc3gpu_decode_vbr(lc3gpu_decoder *d, const uint8_t *d_in, const uint16_t *d_
         const int rc0 = decoder_materialise(d);
         if (rc0) return rc0;
     }
-    int rc = d->order_begin(stream);
+    BatchCall call(*d, stream);
+    int rc = call.begin();
     if (rc == LC3GPU_OK) rc = decoder_reserve_planes(d, frames, stream);
     if (rc) return rc;
     const int mode = lc3_recon_mode(frames, n_frames);
     if (mode == LC3_RECON_WAVE && (rc = lc3_tns_lds_optin()) != LC3GPU_OK) return rc;
-    auto launched = [] {
-        const hipError_t er = hipGetLastError();
-        if (er == hipSuccess) return LC3GPU_OK;
-        g_last_hip = (int)er;
-        return LC3GPU_EHIP;
-    };
-    const size_t t0 = d->timer.used;
-    d->timer.arm();
-    d->timer.mark(stream, -1, 0);
-    const unsigned fpb = lc3_frame_block_fit(LC3_PARSE_LDS_FIXED, (size_t)(64 + slot_bytes));
-    const size_t lds = LC3_PARSE_LDS_FIXED + (size_t)fpb * (size_t)(64 + slot_bytes);
-    LC3_LAUNCH_VBR(lc3_parse_vbr_kernel, h, dim3((unsigned)((frames + fpb - 1) / fpb)), dim3(fpb), lds, stream, d_in, d_bad, d_nbytes, slot_bytes,
-                   d->d_planes, (int)frames, mode);
-    rc = launched();
-    if (rc == LC3GPU_OK) d->timer.mark(stream, 0, 0);
-    if (rc == LC3GPU_OK && mode == LC3_RECON_WAVE) {
-        const size_t wgs = (frames + LC3_WG_WAVES - 1) / LC3_WG_WAVES;
-        LC3_LAUNCH_VBR(lc3_recon_vbr_kernel, h, dim3((unsigned)(wgs < lc3_recon_grid() ? wgs : lc3_recon_grid())), dim3(64 * LC3_WG_WAVES), 0,
-                       stream, d->d_planes, d_nbytes, slot_bytes, (int)frames);
-        rc = launched();
-        if (rc == LC3GPU_OK) d->timer.mark(stream, 1, 0);
-        if (rc == LC3GPU_OK) {
-            LC3_LAUNCH_CFG(lc3_tns_kernel, h, dim3((unsigned)((frames + LC3_TNS_FPB - 1) / LC3_TNS_FPB)), dim3(LC3_TNS_FPB), LC3_TNS_LDS, stream,
-                           d->d_planes, (int)frames);
-            rc = launched();
-        }
-        if (rc == LC3GPU_OK) d->timer.mark(stream, 2, 0);
-    }
-    if (rc == LC3GPU_OK) rc = d->stage_record(LC3GPU_DEC_STAGE_PARSE, stream);
-    if (rc == LC3GPU_OK) {
-        const dim3 grid((unsigned)((n + LC3_WG_WAVES - 1) / LC3_WG_WAVES)), block(64 * LC3_WG_WAVES);
-        const int32_t *pl = d->d_planes;
-        if (mode == LC3_RECON_LATE) {
-            if (h.view == 1) hipLaunchKernelGGL((lc3_decode_vbr_kernel<lc3_cfg_48k10, 1>), grid, block, 0, stream, lc3_cfg_slot<lc3_cfg_48k10>{h.slot},
-                                                d->d_states, n, pl, d_pcm, d_nbytes, slot_bytes, n_frames, fresh);
-            else hipLaunchKernelGGL((lc3_decode_vbr_kernel<lc3_cfg_any, 1>), grid, block, 0, stream, lc3_cfg_slot<lc3_cfg_any>{h.slot}, d->d_states,
-                                    n, pl, d_pcm, d_nbytes, slot_bytes, n_frames, fresh);
-        } else {
-            if (h.view == 1) hipLaunchKernelGGL((lc3_decode_vbr_kernel<lc3_cfg_48k10, 0>), grid, block, lc3_lds_pad(2), stream,
-                                                lc3_cfg_slot<lc3_cfg_48k10>{h.slot}, d->d_states, n, pl, d_pcm, d_nbytes, slot_bytes, n_frames, fresh);
-            else hipLaunchKernelGGL((lc3_decode_vbr_kernel<lc3_cfg_any, 0>), grid, block, lc3_lds_pad(2), stream, lc3_cfg_slot<lc3_cfg_any>{h.slot},
-                                    d->d_states, n, pl, d_pcm, d_nbytes, slot_bytes, n_frames, fresh);
-        }
-        rc = launched();
-    }
-    if (rc == LC3GPU_OK) d->timer.mark(stream, 3, 0);
-    if (rc) {
-        d->timer.rollback(t0);
-        (void)d->order_end(stream);
-        if (fresh) (void)decoder_init_states(d);
-        return rc;
-    }
-    if (fresh) d->fresh_set_all(0);
-    return d->order_end(stream);
+    call.arm();
+    rc = decode_stages(
+        d, stream, 0, mode,
+        [&] {
+            const unsigned fpb = lc3_frame_block_fit(LC3_PARSE_LDS_FIXED, (size_t)(64 + slot_bytes));
+            const size_t lds = LC3_PARSE_LDS_FIXED + (size_t)fpb * (size_t)(64 + slot_bytes);
+            LC3_LAUNCH_HEADLINE(lc3_parse_vbr_kernel, h, dim3((unsigned)((frames + fpb - 1) / fpb)), dim3(fpb), lds, stream, d_in, d_bad, d_nbytes,
+                                slot_bytes, d->d_planes, (int)frames, mode);
+            return LC3GPU_OK;
+        },
+        [&] {
+            const size_t wgs = (frames + LC3_WG_WAVES - 1) / LC3_WG_WAVES;
+            LC3_LAUNCH_HEADLINE(lc3_recon_vbr_kernel, h, dim3((unsigned)(wgs < lc3_recon_grid() ? wgs : lc3_recon_grid())), dim3(64 * LC3_WG_WAVES), 0,
+                                stream, d->d_planes, d_nbytes, slot_bytes, (int)frames);
+            return LC3GPU_OK;
+        },
+        [&] { return tns_launch(h, d->d_planes, frames, stream); },
+        [&] {
+            LC3_LAUNCH_SYNTH(lc3_decode_vbr_kernel, h, mode == LC3_RECON_LATE, lc3_stream_grid(n), dim3(64 * LC3_WG_WAVES), stream, d->d_states, n,
+                             (const int32_t *)d->d_planes, d_pcm, d_nbytes, slot_bytes, n_frames, fresh);
+            return LC3GPU_OK;
+        });
+    if (rc == LC3GPU_OK && fresh) d->fresh_set_all(0);
+    const int rc_end = call.end(rc);
+    if (rc && fresh) (void)decoder_init_states(d);
+    return rc_end;
 }
 
 int lc3gpu_inspect(int frame_us, int fs_hz, const uint8_t *d_in, const uint16_t *d_nbytes, const uint8_t *d_bad, int slot_bytes, int n_frames,
@@ -4263,68 +4322,32 @@ int lc3gpu_decode_mixed(lc3gpu_decoder *d, const uint8_t *d_in, const uint8_t *d
     if (((uintptr_t)d_pcm & 3u) != 0) return LC3GPU_EINVAL;
     LC3_ON_DEVICE(d);
     hipStream_t stream = (hipStream_t)stream_;
+    const size_t frames = (size_t)d->num_channels * (size_t)n_frames;
+    BatchCall call(*d, stream);
     int rc = decoder_materialise(d);
-    if (rc == LC3GPU_OK) rc = d->order_begin(stream);
-    if (rc) return rc;
-    lc3_groups G;
-    unsigned wg_stream, wg_frame;
-    size_t frames;
-    int max_nbytes;
-    fill_groups(*d, n_frames, 256u, G, wg_stream, wg_frame, frames, max_nbytes);
-    const unsigned fpb = lc3_frame_block_fit(LC3_PARSE_LDS_FIXED, (size_t)(64 + max_nbytes));
-    fill_groups(*d, n_frames, fpb, G, wg_stream, wg_frame, frames, max_nbytes);
-    rc = decoder_reserve_planes(d, frames, stream);
+    if (rc == LC3GPU_OK) rc = call.begin();
+    if (rc == LC3GPU_OK) rc = decoder_reserve_planes(d, frames, stream);
     if (rc) return rc;
     lc3_io io = {0, d->d_tab};
-    const size_t lds = LC3_PARSE_LDS_FIXED + (size_t)fpb * (size_t)(64 + max_nbytes);
-    const int mode = lc3_recon_mode((size_t)d->num_channels * (size_t)n_frames, n_frames);
+    const int mode = lc3_recon_mode(frames, n_frames);
     if (mode == LC3_RECON_WAVE && (rc = lc3_tns_lds_optin()) != LC3GPU_OK) return rc;
-    const size_t t0 = d->timer.used;
-    d->timer.begin(stream);
-    if (mode == LC3_RECON_LANE && lc3_parse_pc_enabled()) {  // full batches: the producer / consumer pairs (as lc3gpu_decode does)
-        if ((rc = lc3_parse_pc_optin()) != LC3GPU_OK) {
-            d->timer.rollback(t0);
-            (void)d->order_end(stream);
-            return rc;
-        }
-        const unsigned pfpb = lc3_parse_pc_fpb(max_nbytes);
-        lc3_groups Gp;
-        unsigned a, b;
-        size_t f;
-        int m;
-        fill_groups(*d, n_frames, pfpb, Gp, a, b, f, m);
-        hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_parse_pc_mixed_kernel), dim3(b), dim3(2 * pfpb), lc3_parse_pc_lds(pfpb, max_nbytes), stream, Gp, d_in, d_bad, d->d_planes,
-                           n_frames, io, d->d_pc_timeouts);
-    } else
-        hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_parse_mixed_kernel), dim3(wg_frame), dim3(fpb), lds, stream, G, d_in, d_bad, d->d_planes, n_frames, io, mode);
-    LC3_LAUNCH_CHECK(d, stream, t0);
-    d->timer.mark(stream, 0);
-    lc3_groups Gx;  // the group table for other numbers of frames per workgroup
-    unsigned gx_a, gx_b;
-    size_t gx_f;
-    int gx_m;
-    if (mode == LC3_RECON_WAVE) {
-        fill_groups(*d, n_frames, (unsigned)LC3_WG_WAVES, Gx, gx_a, gx_b, gx_f, gx_m);
-        hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_recon_mixed_kernel), dim3(gx_b), dim3(64 * LC3_WG_WAVES), 0, stream, Gx, d->d_planes, n_frames);
-        LC3_LAUNCH_CHECK(d, stream, t0);
-        d->timer.mark(stream, 1);
-    }
-    if (mode == LC3_RECON_WAVE) {
-        fill_groups(*d, n_frames, (unsigned)LC3_TNS_FPB, Gx, gx_a, gx_b, gx_f, gx_m);
-        hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_tns_mixed_kernel), dim3(gx_b), dim3(LC3_TNS_FPB), LC3_TNS_LDS, stream, Gx, d->d_planes, n_frames);
-        LC3_LAUNCH_CHECK(d, stream, t0);
-        d->timer.mark(stream, 2);
-    }
-    LC3_STAGE_RECORD(d, LC3GPU_DEC_STAGE_PARSE, stream, t0);
-    if (mode == LC3_RECON_LATE)
-        hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_decode_mixed_late_kernel), dim3(wg_stream), dim3(64 * LC3_WG_WAVES), 0, stream, G, d->d_states,
-                           (const int32_t *)d->d_planes, d_pcm, n_frames, 0, io);
-    else
-        hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_decode_mixed_kernel), dim3(wg_stream), dim3(64 * LC3_WG_WAVES), 0, stream, G, d->d_states,
-                           (const int32_t *)d->d_planes, d_pcm, n_frames, 0, io);
-    LC3_LAUNCH_CHECK(d, stream, t0);
-    d->timer.mark(stream, 3);
-    return d->order_end(stream);
+    const HandleGroups groups{*d, n_frames};
+    GroupTable t;  // (the synthesis kernel's workgroups do not depend on the frames per workgroup of the others)
+    groups(256u, t);
+    call.arm();
+    rc = decode_stages(
+        d, stream, 0, mode, [&] { return parse_mixed_launch(d, groups, d->max_nbytes, d_in, d_bad, n_frames, io, mode, stream); },
+        [&] { return recon_mixed_launch(d, groups, n_frames, stream); }, [&] { return tns_mixed_launch(d, groups, n_frames, stream); },
+        [&] {
+            if (mode == LC3_RECON_LATE)
+                hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_decode_mixed_late_kernel), dim3(t.wg_stream), dim3(64 * LC3_WG_WAVES), 0, stream, t.G, d->d_states,
+                                   (const int32_t *)d->d_planes, d_pcm, n_frames, 0, io);
+            else
+                hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_decode_mixed_kernel), dim3(t.wg_stream), dim3(64 * LC3_WG_WAVES), 0, stream, t.G, d->d_states,
+                                   (const int32_t *)d->d_planes, d_pcm, n_frames, 0, io);
+            return LC3GPU_OK;
+        });
+    return call.end(rc);
 }
 
 // A list of a mixed handle's streams, as lc3gpu_encode_mixed_list: parser and reconstruction form as lc3gpu_decode_mixed picks them for a
@@ -4343,66 +4366,35 @@ int lc3gpu_decode_mixed_list(lc3gpu_decoder *d, const int32_t *channels, int n_l
     hipStream_t stream = (hipStream_t)stream_;
     const size_t frames = (size_t)n_list * (size_t)n_frames;
     const int mode = lc3_recon_mode(frames, n_frames);
-    uint8_t *slot = nullptr;
-    rc = d->order_begin(stream);
+    lc3_mlist_plan P;
+    BatchCall call(*d, stream);
+    rc = call.begin();
     if (rc == LC3GPU_OK) rc = decoder_reserve_planes(d, frames, stream);
     if (rc == LC3GPU_OK && mode == LC3_RECON_WAVE) rc = lc3_tns_lds_optin();
-    if (rc == LC3GPU_OK) rc = d->mlist_slot(&slot);
+    if (rc == LC3GPU_OK) rc = d->mlist_send(channels, n_list, d->fresh_mask.data(), stream, P);
     if (rc) return rc;
-    lc3_mlist_plan P;
-    lc3_mlist_build(d->mlist_groups.data(), (int)d->mlist_groups.size(), d->mlist_streams.data(), d->fresh_mask.data(), channels, n_list,
-                    (int32_t *)slot, (lc3_stream_io *)(slot + HandleCommon::mlist_tab_offset(n_list)), P);
-    if ((rc = d->mlist_upload(n_list, stream)) != LC3GPU_OK) return rc;
-    const int32_t *d_entries = (const int32_t *)d->d_mlist;
-    const lc3_io io = {0, (const lc3_stream_io *)(d->d_mlist + HandleCommon::mlist_tab_offset(n_list))};
-    const lc3_mlist_group *mg = d->mlist_groups.data();
-    const int ng = (int)d->mlist_groups.size();
-    const unsigned fpb = lc3_frame_block_fit(LC3_PARSE_LDS_FIXED, (size_t)(64 + P.max_nbytes));
-    const size_t lds = LC3_PARSE_LDS_FIXED + (size_t)fpb * (size_t)(64 + P.max_nbytes);
-    lc3_groups G;
-    unsigned wg_stream, wg_frame;
-    lc3_mlist_groups(mg, ng, P, n_frames, (unsigned)LC3_WG_WAVES, fpb, G, wg_stream, wg_frame);
-    const size_t t0 = d->timer.used;
-    d->timer.begin(stream);
-    if (mode == LC3_RECON_LANE && lc3_parse_pc_enabled()) {  // full batches: the producer / consumer pairs, as lc3gpu_decode_mixed
-        if ((rc = lc3_parse_pc_optin()) != LC3GPU_OK) {
-            d->timer.rollback(t0);
-            (void)d->order_end(stream);
-            return rc;
-        }
-        const unsigned pfpb = lc3_parse_pc_fpb(P.max_nbytes);
-        lc3_groups Gp;
-        unsigned a, b;
-        lc3_mlist_groups(mg, ng, P, n_frames, (unsigned)LC3_WG_WAVES, pfpb, Gp, a, b);
-        hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_parse_pc_mixed_kernel), dim3(b), dim3(2 * pfpb), lc3_parse_pc_lds(pfpb, P.max_nbytes), stream, Gp, d_in, d_bad,
-                           d->d_planes, n_frames, io, d->d_pc_timeouts);
-    } else
-        hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_parse_mixed_kernel), dim3(wg_frame), dim3(fpb), lds, stream, G, d_in, d_bad, d->d_planes, n_frames, io, mode);
-    LC3_LAUNCH_CHECK(d, stream, t0);
-    d->timer.mark(stream, 0);
-    if (mode == LC3_RECON_WAVE) {
-        lc3_groups Gx;
-        unsigned a, b;
-        lc3_mlist_groups(mg, ng, P, n_frames, (unsigned)LC3_WG_WAVES, (unsigned)LC3_WG_WAVES, Gx, a, b);
-        hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_recon_mixed_kernel), dim3(b), dim3(64 * LC3_WG_WAVES), 0, stream, Gx, d->d_planes, n_frames);
-        LC3_LAUNCH_CHECK(d, stream, t0);
-        d->timer.mark(stream, 1);
-        lc3_mlist_groups(mg, ng, P, n_frames, (unsigned)LC3_WG_WAVES, (unsigned)LC3_TNS_FPB, Gx, a, b);
-        hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_tns_mixed_kernel), dim3(b), dim3(LC3_TNS_FPB), LC3_TNS_LDS, stream, Gx, d->d_planes, n_frames);
-        LC3_LAUNCH_CHECK(d, stream, t0);
-        d->timer.mark(stream, 2);
-    }
-    LC3_STAGE_RECORD(d, LC3GPU_DEC_STAGE_PARSE, stream, t0);
-    if (mode == LC3_RECON_LATE)
-        hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_decode_mixed_list_late_kernel), dim3(wg_stream), dim3(64 * LC3_WG_WAVES), 0, stream, G, d->d_states, d_entries,
-                           (const int32_t *)d->d_planes, d_pcm, n_frames, io);
-    else
-        hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_decode_mixed_list_kernel), dim3(wg_stream), dim3(64 * LC3_WG_WAVES), 0, stream, G, d->d_states, d_entries,
-                           (const int32_t *)d->d_planes, d_pcm, n_frames, io);
-    LC3_LAUNCH_CHECK(d, stream, t0);  // (the channels noted fresh stay noted: whatever ran, their next call starts them from the constructed state)
-    d->timer.mark(stream, 3);
-    for (int i = 0; i < n_list; i++) d->fresh_clear(d->streams[(size_t)channels[i]].internal);
-    return d->order_end(stream);
+    const int32_t *d_entries = d->d_mlist_entries();
+    const lc3_io io = {0, d->d_mlist_tab(n_list)};
+    const ListGroups groups{*d, P, n_frames};
+    GroupTable t;  // (as in lc3gpu_decode_mixed: the wave-per-stream kernels read wg_stream only)
+    groups(256u, t);
+    call.arm();
+    rc = decode_stages(
+        d, stream, 0, mode, [&] { return parse_mixed_launch(d, groups, P.max_nbytes, d_in, d_bad, n_frames, io, mode, stream); },
+        [&] { return recon_mixed_launch(d, groups, n_frames, stream); }, [&] { return tns_mixed_launch(d, groups, n_frames, stream); },
+        [&] {
+            if (mode == LC3_RECON_LATE)
+                hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_decode_mixed_list_late_kernel), dim3(t.wg_stream), dim3(64 * LC3_WG_WAVES), 0, stream, t.G,
+                                   d->d_states, d_entries, (const int32_t *)d->d_planes, d_pcm, n_frames, io);
+            else
+                hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_decode_mixed_list_kernel), dim3(t.wg_stream), dim3(64 * LC3_WG_WAVES), 0, stream, t.G, d->d_states,
+                                   d_entries, (const int32_t *)d->d_planes, d_pcm, n_frames, io);
+            return LC3GPU_OK;
+        });
+    // (on failure the channels noted fresh stay noted: whatever ran, their next call starts them from the constructed state)
+    if (rc == LC3GPU_OK)
+        for (int i = 0; i < n_list; i++) d->fresh_clear(d->streams[(size_t)channels[i]].internal);
+    return call.end(rc);
 }
 
 int lc3gpu_decode_frame(lc3gpu_decoder *d, int num_bits_per_audio_sample, int channel_index, const uint8_t *buf_in,
