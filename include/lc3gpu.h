@@ -189,9 +189,59 @@ int lc3gpu_encode_mixed(lc3gpu_encoder *enc, const int16_t *d_pcm, uint8_t *d_ou
  * stream take no workgroups.  8 kHz streams: refused at encoder creation as ever, allowed on the decoder.  Asynchronous on hip_stream,
  * ordered after the handle's earlier work.
  * NOT provided by the mixed-list calls (out of scope): the interleaved layout, a frame size per frame (lc3gpu_*_vbr), the host-resident
- * calls (lc3gpu_*_host), the pipeline object, and a frame count per listed channel (n_frames holds for every item of a call). */
+ * calls (lc3gpu_*_host) and the pipeline object.  (n_frames holds for every item of a call and every stream is coded at its
+ * descriptor's size; a frame count per listed channel and a frame size per call are what lc3gpu_encode_mixed_items /
+ * lc3gpu_decode_mixed_items below provide.) */
 int lc3gpu_encode_mixed_list(lc3gpu_encoder *enc, const int32_t *channels, int n_list, const int16_t *d_pcm, uint8_t *d_out, int n_frames,
                              void *hip_stream);
+/* Batch over a list of ITEMS of a mixed handle: a frame count and a frame size per listed stream.  The reference's caller calls
+ * encode_frame / decode_frame once per (channel, frame) with a slice whose length selects the size (encoder/lc3_encoder.rs:65,175-191,
+ * decoder/lc3_decoder.rs:85,217-234); a 30 ms tick of a server -- four frames of every 7.5 ms stream, three of every 10 ms stream --, a
+ * decoder behind jitter buffers that owes one stream one frame and another three, a stream whose bitrate adapts: each is ONE call.
+ * The contract of lc3gpu_encode_mixed_list, with these differences:
+ *   items     HOST lc3gpu_item[n_items], any order, no channel twice; may be reused as soon as the call returns.  Item i: `channel` a
+ *             descriptor index, `n_frames` >= 1 the frames of this stream in this call, `nbytes` the frame size of ALL of them (0 = the
+ *             descriptor's; the state and the state blob do not depend on the size, so a stream may change it from call to call),
+ *             `reserved` 0
+ *   buffers   DEVICE, ragged and compact in list order.  With nf_j / nbytes_j the frame length / effective frame size of item j:
+ *               d_pcm  item i at element offset sum_{j<i} n_frames_j * nf_j,     int16[n_frames_i][nf_i]
+ *               d_out  item i at byte offset    sum_{j<i} n_frames_j * nbytes_j, uint8[n_frames_i][nbytes_i]
+ *               flags  (decoder) item i at      sum_{j<i} n_frames_j,            uint8[n_frames_i], one per frame
+ *             nf is even for every configuration, so a 4-byte aligned d_pcm base keeps every item aligned
+ *   checks    everything on the host before anything is queued; a refused call has launched nothing, written nothing, advanced no
+ *             channel and consumed no pending reset:
+ *               channel out of range or named twice                  LC3GPU_ECHANNEL
+ *               n_frames < 1                                         LC3GPU_ELENGTH
+ *               nbytes not 0 and outside 20..400 (encoder)           LC3GPU_ELENGTH
+ *               nbytes not 0 and outside 1..400 (decoder)            LC3GPU_ELENGTH
+ *               more than 2^31 - 1 frames in one call                LC3GPU_ELENGTH
+ *               reserved != 0, a null pointer, n_items < 0,
+ *               misaligned PCM, a UNIFORM handle, a bound handle
+ *               on another stream                                    LC3GPU_EINVAL
+ *               n_items == 0                                         LC3GPU_OK (nothing launched)
+ *             LC3GPU_EPAIR and LC3GPU_EUNSUPPORTED (a group without a compile-time view) as for lc3gpu_*_mixed_list
+ *   state     a listed channel advances by its own n_frames, exactly as that many reference calls at that size advance it; channels not
+ *             listed keep their blob (and their PLC count) byte for byte; channels reset by lc3gpu_*_reset_channels start fresh inside
+ *             the same launch
+ *   mixing    items, mixed-list, lc3gpu_*_mixed and *_frame calls may alternate on a handle; a call whose items all have n_frames = T
+ *             and nbytes = 0 gives the bytes and the PCM of lc3gpu_*_mixed_list with n_frames = T
+ *   launches  the items are bucketed by (configuration, effective nbytes, n_frames); ONE launch per kernel per 24 buckets (a call with
+ *             more buckets runs as consecutive launch sets on the same stream, with one upload and one host check for all of them)
+ * NOT provided (out of scope): a size per FRAME within an item, the interleaved layout, the host-resident calls, the pipeline object,
+ * uniform handles. */
+typedef struct lc3gpu_item {
+    int32_t channel;  /* descriptor index of the mixed handle */
+    int32_t n_frames; /* >= 1: frames of this stream in this call */
+    int32_t nbytes;   /* frame size for this call; 0 = the descriptor's */
+    int32_t reserved; /* 0 */
+} lc3gpu_item;
+#ifdef __cplusplus
+static_assert(sizeof(lc3gpu_item) == 16, "lc3gpu_item is 16 bytes");
+#else
+_Static_assert(sizeof(lc3gpu_item) == 16, "lc3gpu_item is 16 bytes");
+#endif
+int lc3gpu_encode_mixed_items(lc3gpu_encoder *enc, const lc3gpu_item *items, int n_items, const int16_t *d_pcm, uint8_t *d_out,
+                              void *hip_stream);
 
 /* per-channel state blobs (checkpoint / CPU cross-checks): size per channel, device->host copy, host->device.
  * nbytes must equal state_size * num_channels (LC3GPU_ELENGTH otherwise); both calls synchronise the device.  A channel's blob
@@ -307,6 +357,11 @@ int lc3gpu_decode_mixed(lc3gpu_decoder *dec, const uint8_t *d_in, const uint8_t 
  * synchronisation lc3gpu_decode_mixed spends on materialising them. */
 int lc3gpu_decode_mixed_list(lc3gpu_decoder *dec, const int32_t *channels, int n_list, const uint8_t *d_in, const uint8_t *d_bad_frame,
                              int16_t *d_pcm, int n_frames, void *hip_stream);
+/* Batch decode over a list of ITEMS of a mixed handle: the contract of lc3gpu_encode_mixed_items (which see) with d_in like that call's
+ * d_out, d_pcm like its d_pcm, d_bad_frame one flag per frame in item order or NULL, and frame sizes 1..400 (a frame too short to hold
+ * side information is concealed and counted, as everywhere). */
+int lc3gpu_decode_mixed_items(lc3gpu_decoder *dec, const lc3gpu_item *items, int n_items, const uint8_t *d_in, const uint8_t *d_bad_frame,
+                              int16_t *d_pcm, void *hip_stream);
 
 size_t lc3gpu_decoder_state_size(const lc3gpu_decoder *dec);
 int lc3gpu_decoder_state_save(lc3gpu_decoder *dec, void *host_dst, size_t nbytes);

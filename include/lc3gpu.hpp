@@ -79,6 +79,12 @@ public:
         int rc = lc3gpu_encode_mixed_list(h_, channels.data(), (int)channels.size(), d_pcm, d_out, n_frames, hip_stream);
         if (rc) throw Error(rc, "encode_mixed_list");
     }
+    // mixed handle: a list of items, each a stream with its own frame count and frame size for this call (lc3gpu_item; nbytes 0 = the
+    // descriptor's); ragged DEVICE buffers compact in list order, item i's PCM at element offset sum n_frames_j * nf_j
+    void encode_mixed_items(const std::vector<lc3gpu_item> &items, const int16_t *d_pcm, uint8_t *d_out, void *hip_stream = nullptr) {
+        int rc = lc3gpu_encode_mixed_items(h_, items.data(), (int)items.size(), d_pcm, d_out, hip_stream);
+        if (rc) throw Error(rc, "encode_mixed_items");
+    }
     // back to the freshly constructed state from the next call on: every channel, or the named ones (a new EncoderChannel); no wait
     void reset() {
         int rc = lc3gpu_encoder_reset(h_);
@@ -163,6 +169,12 @@ public:
                            const uint8_t *d_bad_frame = nullptr) {
         int rc = lc3gpu_decode_mixed_list(h_, channels.data(), (int)channels.size(), d_in, d_bad_frame, d_pcm, n_frames, hip_stream);
         if (rc) throw Error(rc, "decode_mixed_list");
+    }
+    // mixed handle: a list of items (see Encoder::encode_mixed_items); d_bad_frame one flag per frame in item order
+    void decode_mixed_items(const std::vector<lc3gpu_item> &items, const uint8_t *d_in, int16_t *d_pcm, void *hip_stream = nullptr,
+                            const uint8_t *d_bad_frame = nullptr) {
+        int rc = lc3gpu_decode_mixed_items(h_, items.data(), (int)items.size(), d_in, d_bad_frame, d_pcm, hip_stream);
+        if (rc) throw Error(rc, "decode_mixed_items");
     }
     // every channel, or the named ones (a new DecoderChannel; their PLC counts go to zero); no wait
     void reset() {

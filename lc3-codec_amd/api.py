@@ -252,6 +252,8 @@ def load_library():
     L.lc3gpu_decode_list.argtypes = [vp, vp, i, vp, vp, vp, i, i, vp]
     L.lc3gpu_encode_mixed_list.argtypes = [vp, vp, i, vp, vp, i, vp]
     L.lc3gpu_decode_mixed_list.argtypes = [vp, vp, i, vp, vp, vp, i, vp]
+    L.lc3gpu_encode_mixed_items.argtypes = [vp, vp, i, vp, vp, vp]
+    L.lc3gpu_decode_mixed_items.argtypes = [vp, vp, i, vp, vp, vp, vp]
     L.lc3gpu_encoder_reset_channels.argtypes = [vp, vp, i]
     L.lc3gpu_decoder_reset_channels.argtypes = [vp, vp, i]
     L.lc3gpu_encoder_state_save_channels.argtypes = [vp, vp, i, vp, ctypes.c_size_t]
@@ -343,6 +345,7 @@ ABI_SYMBOLS = [
     "lc3gpu_inspect", "lc3gpu_encode_list", "lc3gpu_decode_list", "lc3gpu_encoder_reset_channels", "lc3gpu_decoder_reset_channels",
     "lc3gpu_encoder_state_save_channels", "lc3gpu_encoder_state_load_channels", "lc3gpu_decoder_state_save_channels",
     "lc3gpu_decoder_state_load_channels", "lc3gpu_encode_mixed_list", "lc3gpu_decode_mixed_list",
+    "lc3gpu_encode_mixed_items", "lc3gpu_decode_mixed_items",
 ]
 
 # LC3GPU_SPEC_*: opt-in corrections of the reference's deviations from the LC3 specification (default 0 = reference behaviour)
@@ -478,6 +481,21 @@ def _channel_list(channels):
     if a.size and a.dtype.kind not in "iu":
         raise TypeError("channel indices must be integers")
     return np.ascontiguousarray(a.reshape(-1), dtype=np.int32)
+
+
+def _item_list(items):
+    """a sequence of (channel, n_frames[, nbytes]) or an integer array [n][2..4] -> contiguous HOST int32[n][4], the lc3gpu_item array of
+    the *_mixed_items calls (nbytes 0 = the descriptor's; the fourth word is reserved, 0 unless the caller's array sets it)"""
+    rows = [tuple(r) for r in items]
+    out = np.zeros((len(rows), 4), np.int32)
+    for i, r in enumerate(rows):
+        if not 2 <= len(r) <= 4:
+            raise TypeError("an item is (channel, n_frames[, nbytes])")
+        for v in r:
+            if not isinstance(v, (int, np.integer)):
+                raise TypeError("item fields must be integers")
+        out[i, : len(r)] = r
+    return out
 
 
 class Lc3Config:
@@ -621,6 +639,16 @@ class Lc3Encoder:
         rc = self._L.lc3gpu_encode_mixed_list(self._h, _ptr(ch), int(ch.size), _ptr(d_pcm), _ptr(d_out), int(n_frames), _ptr(stream))
         if rc:
             raise Lc3EncoderError(rc, "encode_mixed_list")
+
+    def encode_mixed_items(self, items, d_pcm, d_out, stream=None):
+        """a mixed handle's batch over a list of items `(channel, n_frames[, nbytes])` (HOST, any order, no channel twice): every listed
+        stream gets its own number of frames at its own frame size this call (nbytes 0 or left out: the descriptor's).  Ragged DEVICE
+        buffers compact in list order: item i's PCM at element offset sum n_frames_j * nf_j, its bytes at sum n_frames_j * nbytes_j.
+        One launch per kernel per 24 (configuration, size, count) buckets; asynchronous on `stream` (lc3gpu_encode_mixed_items)"""
+        it = _item_list(items)
+        rc = self._L.lc3gpu_encode_mixed_items(self._h, _ptr(it), int(it.shape[0]), _ptr(d_pcm), _ptr(d_out), _ptr(stream))
+        if rc:
+            raise Lc3EncoderError(rc, "encode_mixed_items")
 
     def reset(self, channels=None):
         """every channel (channels=None) or the named ones back to the freshly constructed state from their next call on; no wait"""
@@ -856,6 +884,14 @@ class Lc3Decoder:
                                               _ptr(stream))
         if rc:
             raise Lc3DecoderError(rc, "decode_mixed_list")
+
+    def decode_mixed_items(self, items, d_in, d_pcm, stream=None, d_bad_frame=None):
+        """a mixed handle's batch over a list of items `(channel, n_frames[, nbytes])`, as Lc3Encoder.encode_mixed_items: d_in like its
+        d_out, d_bad_frame one flag per frame in item order; frame sizes 1..400 (lc3gpu_decode_mixed_items)"""
+        it = _item_list(items)
+        rc = self._L.lc3gpu_decode_mixed_items(self._h, _ptr(it), int(it.shape[0]), _ptr(d_in), _ptr(d_bad_frame), _ptr(d_pcm), _ptr(stream))
+        if rc:
+            raise Lc3DecoderError(rc, "decode_mixed_items")
 
     def reset(self, channels=None):
         """every channel (channels=None) or the named ones back to the freshly constructed state (PLC count 0) from their next call on; no wait"""

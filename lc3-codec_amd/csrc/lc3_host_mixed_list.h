@@ -16,6 +16,8 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <algorithm>
+#include <vector>
 
 // How a launch finds a stream's PCM, frame bytes and bad-frame flags in the ragged layout of a mixed-configuration handle: stream i's PCM
 // at element T * tab[i].pcm_off1, its bytes at T * tab[i].byte_off1, its flags at tab[i].flag_idx * T
@@ -28,7 +30,8 @@ struct lc3_group {
     int slot, fixed;              // configuration slot; the compile-time view that applies (lc3_cfg_views.h: 1..4), 0 = the run-time view
     int first_stream, n_streams;  // [first_stream, first_stream + n_streams) in the handle's internal order (a list call: launch positions)
     int wg_stream, wg_frame;      // the group's first workgroup in a stream-kernel / frame-kernel launch
-    int nbytes, ne, nb, pad;
+    int nbytes, ne, nb;
+    int n_frames;                 // an items call (lc3_mitems_*): frames per stream of this row; every other call: 0, the launch's argument holds
     long long frame_base;         // first plane column of the group
 };
 struct lc3_groups {
@@ -96,9 +99,143 @@ static inline void lc3_mlist_groups(const lc3_mlist_group *groups, int n_groups,
         g.nbytes = groups[i].nbytes;
         g.ne = groups[i].ne;
         g.nb = groups[i].nb;
-        g.pad = 0;
+        g.n_frames = 0;
         g.frame_base = (long long)P.first[i] * (long long)T;
         wg_stream += ((unsigned)P.count[i] + wg_waves - 1) / wg_waves;
         wg_frame += (unsigned)(((size_t)P.count[i] * (size_t)T + fpb - 1) / fpb);
+    }
+}
+
+// ---- a frame count and a frame size per listed stream (lc3gpu_encode_mixed_items / lc3gpu_decode_mixed_items) -------------------------
+// An item names a channel, how many frames it gets in this call and at which size (0: the descriptor's).  The plan buckets the items by
+// (configuration, effective nbytes, n_frames) -- the frame count is part of the key because a workgroup of the wave-per-stream kernels
+// holds four streams of ONE bucket and these meet at workgroup barriers whose number depends on the frame count.  Buckets are ordered by
+// that key, the items inside a bucket keep the caller's order (stable), which fixes every item's LAUNCH POSITION as in a list call:
+//   entries[pos]   internal index | LC3_LIST_FRESH
+//   tab[pos]       ABSOLUTE offsets into the caller's ragged compact buffers: pcm_off1 in elements (sum of n_frames * nf over the items in
+//                  front), byte_off1 in bytes (sum of n_frames * nbytes), flag_idx in frames (sum of n_frames).  The kernels of the items
+//                  path reach them with a factor of one where the other calls' kernels multiply by the launch's frame count
+//   buckets[b]     first launch position, count, and frame_base = the running sum of count * n_frames: the bucket's first plane column
+// A bucket becomes one lc3_group row (n_frames in the row).  A launch takes at most LC3_MAX_GROUPS rows, so a call with more buckets runs
+// as consecutive launch sets (lc3_mitems_rows over [b0, b1)): one launch per kernel per 24 buckets, one upload, one host check.
+struct lc3_mitem {  // = lc3gpu_item (include/lc3gpu.h)
+    int32_t channel, n_frames, nbytes, reserved;
+};
+struct lc3_mitems_bucket {
+    int group;             // a group of the handle with the bucket's configuration (slot, view, ne, nb, nf are its)
+    int nbytes, n_frames;  // effective frame size, frames per stream
+    int first, count;      // launch positions [first, first + count)
+    int next;              // (chain of the buckets of one (slot, nbytes) cell while the plan is built)
+    long long frame_base;
+};
+struct lc3_mitems_plan {
+    std::vector<lc3_mitems_bucket> buckets;  // in launch order
+    std::vector<int> cell, bucket_of;        // scratch: head bucket per (slot, nbytes); bucket per item
+    int n_items = 0, max_frames = 0;         // max_frames: the largest per-item count
+    long long frames = 0;                    // of the whole call
+};
+#define LC3_MITEMS_SLOTS 12
+#define LC3_MITEMS_MAX_NBYTES 400
+
+// items: already checked (channel in range and not twice, n_frames >= 1, nbytes 0 or in range).  fresh: per INTERNAL index.
+static inline void lc3_mitems_build(const lc3_mlist_group *groups, const lc3_mlist_stream *streams, const uint8_t *fresh, const lc3_mitem *items,
+                                    int n_items, int32_t *entries, lc3_stream_io *tab, lc3_mitems_plan &P) {
+    P.buckets.clear();
+    P.cell.assign((size_t)LC3_MITEMS_SLOTS * (LC3_MITEMS_MAX_NBYTES + 1), -1);
+    P.bucket_of.resize((size_t)n_items);
+    P.n_items = n_items;
+    P.max_frames = 0;
+    P.frames = 0;
+    for (int i = 0; i < n_items; i++) {  // pass 1: the item's bucket, in order of first appearance
+        const int gi = streams[items[i].channel].group;
+        const int nbytes = items[i].nbytes ? items[i].nbytes : groups[gi].nbytes, T = items[i].n_frames;
+        int &head = P.cell[(size_t)groups[gi].slot * (LC3_MITEMS_MAX_NBYTES + 1) + (size_t)nbytes];
+        int b = head;
+        while (b >= 0 && P.buckets[(size_t)b].n_frames != T) b = P.buckets[(size_t)b].next;
+        if (b < 0) {
+            b = (int)P.buckets.size();
+            P.buckets.push_back({gi, nbytes, T, 0, 0, head, 0});
+            head = b;
+        }
+        P.buckets[(size_t)b].count += 1;
+        P.bucket_of[(size_t)i] = b;
+        if (T > P.max_frames) P.max_frames = T;
+    }
+    // the buckets in key order; rank[b]: where bucket b of pass 1 went
+    const int nb = (int)P.buckets.size();
+    std::vector<int> order((size_t)nb), rank((size_t)nb), next((size_t)nb);
+    for (int b = 0; b < nb; b++) order[(size_t)b] = b;
+    std::sort(order.begin(), order.end(), [&](int a, int b) {
+        const lc3_mitems_bucket &x = P.buckets[(size_t)a], &y = P.buckets[(size_t)b];
+        if (groups[x.group].slot != groups[y.group].slot) return groups[x.group].slot < groups[y.group].slot;
+        if (x.nbytes != y.nbytes) return x.nbytes < y.nbytes;
+        return x.n_frames < y.n_frames;
+    });
+    std::vector<lc3_mitems_bucket> sorted((size_t)nb);
+    int pos = 0;
+    for (int r = 0; r < nb; r++) {
+        lc3_mitems_bucket &b = sorted[(size_t)r];
+        b = P.buckets[(size_t)order[(size_t)r]];
+        rank[(size_t)order[(size_t)r]] = r;
+        b.first = next[(size_t)r] = pos;
+        b.next = -1;
+        b.frame_base = P.frames;
+        pos += b.count;
+        P.frames += (long long)b.count * (long long)b.n_frames;
+    }
+    P.buckets.swap(sorted);
+    long long po = 0, bo = 0, fo = 0;  // pass 2: absolute prefix sums in the caller's LIST order
+    for (int i = 0; i < n_items; i++) {
+        const lc3_mlist_stream &st = streams[items[i].channel];
+        const int r = rank[(size_t)P.bucket_of[(size_t)i]];
+        const lc3_mitems_bucket &b = P.buckets[(size_t)r];
+        const int p = next[(size_t)r]++;  // (stable: the list's order inside a bucket)
+        entries[p] = (int32_t)((uint32_t)st.internal | (fresh[st.internal] ? 0x80000000u : 0u));
+        tab[p].pcm_off1 = po;
+        tab[p].byte_off1 = bo;
+        tab[p].flag_idx = (int)fo;
+        tab[p].pad = 0;
+        po += (long long)b.n_frames * (long long)groups[b.group].nf;
+        bo += (long long)b.n_frames * (long long)b.nbytes;
+        fo += b.n_frames;
+    }
+}
+
+// launch sets: buckets [b0, b1) with b1 - b0 <= LC3_MAX_GROUPS; set k of the call is [k * LC3_MAX_GROUPS, ...)
+static inline int lc3_mitems_sets(const lc3_mitems_plan &P) { return ((int)P.buckets.size() + LC3_MAX_GROUPS - 1) / LC3_MAX_GROUPS; }
+static inline void lc3_mitems_set(const lc3_mitems_plan &P, int k, int &b0, int &b1) {
+    b0 = k * LC3_MAX_GROUPS;
+    b1 = std::min((int)P.buckets.size(), b0 + LC3_MAX_GROUPS);
+}
+// the largest frame size of a launch set: what sizes the LDS of its packer / parser launches
+static inline int lc3_mitems_max_nbytes(const lc3_mitems_plan &P, int b0, int b1) {
+    int m = 0;
+    for (int b = b0; b < b1; b++) m = std::max(m, P.buckets[(size_t)b].nbytes);
+    return m;
+}
+// The group table of one launch set (as lc3_mlist_groups): one row per bucket, its frame count in the row, frame_base the bucket's own --
+// the launch sets of a call use disjoint plane columns of the same planes
+static inline void lc3_mitems_rows(const lc3_mlist_group *groups, const lc3_mitems_plan &P, int b0, int b1, unsigned wg_waves, unsigned fpb,
+                                   lc3_groups &G, unsigned &wg_stream, unsigned &wg_frame) {
+    G.n = 0;
+    G.pad = 0;
+    wg_stream = wg_frame = 0;
+    for (int i = b0; i < b1; i++) {
+        const lc3_mitems_bucket &b = P.buckets[(size_t)i];
+        const lc3_mlist_group &cfg = groups[b.group];
+        lc3_group &g = G.g[G.n++];
+        g.slot = cfg.slot;
+        g.fixed = cfg.view;
+        g.first_stream = b.first;
+        g.n_streams = b.count;
+        g.wg_stream = (int)wg_stream;
+        g.wg_frame = (int)wg_frame;
+        g.nbytes = b.nbytes;
+        g.ne = cfg.ne;
+        g.nb = cfg.nb;
+        g.n_frames = b.n_frames;
+        g.frame_base = b.frame_base;
+        wg_stream += ((unsigned)b.count + wg_waves - 1) / wg_waves;
+        wg_frame += (unsigned)(((size_t)b.count * (size_t)b.n_frames + fpb - 1) / fpb);
     }
 }

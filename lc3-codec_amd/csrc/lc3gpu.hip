@@ -72,6 +72,12 @@
 // lc3_decode_mixed_late_kernel_all (6, 7) they moved the spill counts of those kernels' run-time-view body by one or two registers, and
 // an existing kernel is to compile as it did
 #define LC3_IN_MIXED_LIST_TU(k) (!LC3_MULTI_TU || (LC3_TU_KIND == 2 && LC3_TU_INDEX == (k)))
+// the twins of EVERY kernel of the mixed chain for a list of items with a frame count and a frame size each (lc3gpu_*_mixed_items): they
+// take the frame count from their group row.  Placed as the list twins are -- never in the main unit of a multi-unit library -- each
+// beside the kernel it is a twin of (front 0, back 1, parsers 2 / 3, reconstruction and TNS 4), the lane-per-frame encoder kernels -- whose
+// twins live in the main unit only -- with the back half (1), both synthesis forms in unit 4 beside the list synthesis twins, for the reason
+// given there ("Where the kernels live")
+#define LC3_IN_ITEMS_TU(k) LC3_IN_MIXED_LIST_TU(k)
 #define LC3_CAT_(a, b) a##b
 #define LC3_CAT(a, b) LC3_CAT_(a, b)
 
@@ -727,7 +733,7 @@ __device__ __forceinline__ long long lc3_mlist_off(const long long *field) {  //
     const int lo = lc3_list_entry((const int32_t *)field, 0), hi = lc3_list_entry((const int32_t *)field, 1);
     return (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned long long)(unsigned)lo);
 }
-template <class CV>
+template <class CV, int IOABS = 0>  // IOABS: tab holds absolute offsets (an items call), not offsets per frame of the launch
 __device__ __forceinline__ void lc3_enc_front_body_mixed_list(lc3_cfg_slot<CV> cfg, unsigned wg, lc3_enc_state *states, const int32_t *entries,
                                                               int first_pos, int n_streams, const int16_t *pcm, float *mid, int32_t *planes,
                                                               int nbytes, int n_frames, const lc3_stream_io *tab, int spec_flags) {
@@ -739,7 +745,7 @@ __device__ __forceinline__ void lc3_enc_front_body_mixed_list(lc3_cfg_slot<CV> c
     typename CV::bind_t c0 = CV::bind(lc3_cfg_table[cfg.id]);
     const int entry = lc3_list_entry(entries, first_pos + s);
     lc3_enc_state *gst = states + (size_t)lc3_list_channel(entry);
-    const int16_t *pcm_s = pcm + (size_t)n_frames * (size_t)lc3_mlist_off(&tab[first_pos + s].pcm_off1);
+    const int16_t *pcm_s = pcm + (size_t)(IOABS ? 1 : n_frames) * (size_t)lc3_mlist_off(&tab[first_pos + s].pcm_off1);
 #ifndef LC3_TABLES_IN_GLOBAL
     lc3_front_tables_stage_image(c0.stage_image);
     lc3_fft_tables_stage_image(c0.stage_image);  // ends with the workgroup barrier
@@ -762,6 +768,34 @@ __global__ __launch_bounds__(64 * LC3_WG_WAVES, LC3_FRONT_WAVES) void LC3_MIXED_
 __global__ __launch_bounds__(64 * LC3_WG_WAVES, LC3_FRONT_WAVES) void lc3_enc_front_mixed_list_kernel_all(
     lc3_groups G, lc3_enc_state *states, const int32_t *entries, const int16_t *pcm, float *mid, int32_t *planes, int n_frames, lc3_io io,
     int spec_flags);
+#endif
+
+// ---- items: a frame count and a frame size per listed stream (lc3gpu_encode_mixed_items / lc3gpu_decode_mixed_items) ---------------------
+// Every kernel of the mixed chain once more, reading the frame count from its group ROW (g.n_frames) instead of a launch-wide argument: a
+// row is one bucket of the call's items -- equal configuration, frame size and frame count (lc3_host_mixed_list.h) -- and the per-call
+// table holds ABSOLUTE offsets (IOABS).  Plane columns of launch position p of a row: [frame_base + (p - first_stream) * n_frames, ...).
+// Barrier rule: the gathered LTPF blocks of the front half and its phase (t % LC3_WG_WAVES) + (t + 2 < n_frames ? ...) are workgroup-
+// uniform only because the four streams of a workgroup belong to one row and therefore share n_frames; a shadow wave repeats a stream
+// of its OWN row.  No per-stream branch on the frame count encloses a workgroup barrier: the count is read once per workgroup, from the row.
+template <class CV>
+__device__ __forceinline__ void lc3_enc_front_body_items(lc3_cfg_slot<CV> cfg, unsigned wg, lc3_enc_state *states, const int32_t *entries,
+                                                         int first_pos, int n_streams, const int16_t *pcm, float *mid, int32_t *planes,
+                                                         int nbytes, int n_frames, const lc3_stream_io *tab, int spec_flags) {
+    lc3_enc_front_body_mixed_list<CV, 1>(cfg, wg, states, entries, first_pos, n_streams, pcm, mid, planes, nbytes, n_frames, tab, spec_flags);
+}
+#if LC3_IN_ITEMS_TU(0)
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, LC3_FRONT_WAVES) void LC3_MIXED_KERNEL(lc3_enc_front_items_kernel)(
+    lc3_groups G, lc3_enc_state *states, const int32_t *entries, const int16_t *pcm, float *mid, int32_t *planes, lc3_io io, int spec_flags) {
+    const lc3_group &g = G.g[lc3_find_group(G, blockIdx.x, 0)];
+    float *m = mid + (size_t)g.frame_base * (size_t)MP_WORDS;
+    int32_t *p = planes + (size_t)g.frame_base * (size_t)EP_WORDS;
+    LC3_GROUP_VIEW_LIST(lc3_enc_front_body_items, g, blockIdx.x - g.wg_stream, states, entries, g.first_stream, g.n_streams, pcm, m, p, g.nbytes,
+                        g.n_frames, io.tab, spec_flags);
+}
+#endif
+#if LC3_MULTI_TU && LC3_TU_KIND == 0
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, LC3_FRONT_WAVES) void lc3_enc_front_items_kernel_all(
+    lc3_groups G, lc3_enc_state *states, const int32_t *entries, const int16_t *pcm, float *mid, int32_t *planes, lc3_io io, int spec_flags);
 #endif
 
 // SNS vector quantiser, one LANE per frame (lc3_dev_enc_vq.h): 16 targets -> indices (packer plane) + 64 band gains.
@@ -794,6 +828,17 @@ __global__ __launch_bounds__(256) void lc3_sns_vq_mixed_kernel(lc3_groups G, flo
     lc3_sns_vq_body(blockIdx.x - g.wg_frame, g.nb, mid + (size_t)g.frame_base * (size_t)MP_WORDS,
                     planes + (size_t)g.frame_base * (size_t)EP_WORDS, g.n_streams * n_frames, spec_flags);
 }
+#endif
+
+#if LC3_IN_ITEMS_TU(1)
+__global__ __launch_bounds__(256) void LC3_MIXED_KERNEL(lc3_sns_vq_items_kernel)(lc3_groups G, float *mid, int32_t *planes, int spec_flags) {
+    const lc3_group &g = G.g[lc3_find_group(G, blockIdx.x, 1)];
+    lc3_sns_vq_body(blockIdx.x - g.wg_frame, g.nb, mid + (size_t)g.frame_base * (size_t)MP_WORDS,
+                    planes + (size_t)g.frame_base * (size_t)EP_WORDS, g.n_streams * g.n_frames, spec_flags);
+}
+#endif
+#if LC3_MULTI_TU && LC3_TU_KIND == 0
+__global__ __launch_bounds__(256) void lc3_sns_vq_items_kernel_all(lc3_groups G, float *mid, int32_t *planes, int spec_flags);
 #endif
 
 // Analysis, back half: one wave per stream: spectral shaping with the quantised gains, TNS, quantiser (stateful),
@@ -887,12 +932,28 @@ __global__ __launch_bounds__(64 * LC3_WG_WAVES, LC3_BACK_WAVES) void LC3_MIXED_K
 __global__ __launch_bounds__(64 * LC3_WG_WAVES, LC3_BACK_WAVES) void lc3_enc_back_mixed_list_kernel_all(
     lc3_groups G, lc3_enc_state *states, const int32_t *entries, const float *mid, int32_t *planes, int n_frames, int spec_flags);
 #endif
+// ... and over a list of items: the row's frame count (see lc3_enc_front_items_kernel)
+#if LC3_IN_ITEMS_TU(1)
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, LC3_BACK_WAVES) void LC3_MIXED_KERNEL(lc3_enc_back_items_kernel)(
+    lc3_groups G, lc3_enc_state *states, const int32_t *entries, const float *mid, int32_t *planes, int spec_flags) {
+    const lc3_group &g = G.g[lc3_find_group(G, blockIdx.x, 0)];
+    const float *m = mid + (size_t)g.frame_base * (size_t)MP_WORDS;
+    int32_t *p = planes + (size_t)g.frame_base * (size_t)EP_WORDS;
+    LC3_GROUP_VIEW_LIST(lc3_enc_back_body_mixed_list, g, blockIdx.x - g.wg_stream, states, entries, g.first_stream, g.n_streams, m, p, g.nbytes,
+                        g.n_frames, spec_flags);
+}
+#endif
+#if LC3_MULTI_TU && LC3_TU_KIND == 0
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, LC3_BACK_WAVES) void lc3_enc_back_items_kernel_all(
+    lc3_groups G, lc3_enc_state *states, const int32_t *entries, const float *mid, int32_t *planes, int spec_flags);
+#endif
 
 // Bitstream packer, one LANE per frame (lc3_dev_enc_pack.h).  blockDim.x frames per workgroup; context lookup and the
 // packed spectral model in LDS, every lane builds its frame in an LDS staging slot, then the workgroup copies the
 // frames out with coalesced stores (planar layout: one contiguous run; other layouts: frame by frame).
 // Dynamic LDS: 4096 + 64*17*4 + 152*4 (TNS models) + blockDim.x * nbytes (rounded up to 4) + 4 (sink).
 #define LC3_PACK_LDS_FIXED (4096 + 64 * 17 * 4 + LC3_TNS_MODEL_WORDS * 4)
+template <int IOABS = 0>  // IOABS: the table's offsets are absolute (an items call: lc3_host_mixed_list.h), not per frame of the launch
 __device__ __forceinline__ void lc3_pack_body(unsigned wg, int ne, const int32_t *planes, uint8_t *out, int nbytes, int n_frames,
                                               int T, int first_channel, lc3_io io) {
     LC3_LANE_KERNEL_BEGIN();
@@ -951,7 +1012,7 @@ __device__ __forceinline__ void lc3_pack_body(unsigned wg, int ne, const int32_t
     if (io.ilv || io.tab) {  // frame f = s * T + t has its own place: one frame after the other, its bytes spread over the threads
         for (int j = 0; j < nfr; j++) {
             const size_t fj = f0 + (size_t)j, s = fj / (size_t)T, t = fj - s * (size_t)T;
-            uint8_t *d = out + lc3_io_byte_off(io, nbytes, first_channel, s, t, T);
+            uint8_t *d = out + lc3_io_byte_off(io, nbytes, first_channel, s, t, IOABS ? 1 : T);
             for (int b = tid; b < nbytes; b += fpb) d[b] = s_bytes[j * nbytes + b];
         }
     } else {
@@ -987,6 +1048,17 @@ __global__ __launch_bounds__(256) void lc3_pack_mixed_kernel(lc3_groups G, const
     lc3_pack_body(blockIdx.x - g.wg_frame, g.ne, planes + (size_t)g.frame_base * (size_t)EP_WORDS, out, g.nbytes, g.n_streams * T, T,
                   g.first_stream, io);
 }
+#endif
+
+#if LC3_IN_ITEMS_TU(1)
+__global__ __launch_bounds__(256) void LC3_MIXED_KERNEL(lc3_pack_items_kernel)(lc3_groups G, const int32_t *planes, uint8_t *out, lc3_io io) {
+    const lc3_group &g = G.g[lc3_find_group(G, blockIdx.x, 1)];
+    lc3_pack_body<1>(blockIdx.x - g.wg_frame, g.ne, planes + (size_t)g.frame_base * (size_t)EP_WORDS, out, g.nbytes, g.n_streams * g.n_frames,
+                     g.n_frames, g.first_stream, io);
+}
+#endif
+#if LC3_MULTI_TU && LC3_TU_KIND == 0
+__global__ __launch_bounds__(256) void lc3_pack_items_kernel_all(lc3_groups G, const int32_t *planes, uint8_t *out, lc3_io io);
 #endif
 
 // ---- a frame size per frame (lc3gpu_encode_vbr; lc3_dev_enc_vbr.h) ----------------------------------------------------------------------
@@ -1183,6 +1255,7 @@ __device__ __forceinline__ void lc3_pc_gave_up(unsigned *pc) {
     }
 }
 // pc_timeouts: the handle's sticky count of pair halves that gave up on their partner (lc3gpu_encoder_pair_timeouts)
+template <int IOABS = 0>
 __device__ __forceinline__ void lc3_pack_pc_body(unsigned wg, int ne, const int32_t *planes, uint8_t *out, int nbytes, int n_frames, int T,
                                                  int first_channel, lc3_io io, unsigned *pc_timeouts) {
     LC3_LANE_KERNEL_BEGIN();
@@ -1246,7 +1319,7 @@ __device__ __forceinline__ void lc3_pack_pc_body(unsigned wg, int ne, const int3
     if (io.ilv || io.tab) {  // frame f = s * T + t has its own place: one frame after the other, its bytes spread over the threads
         for (int j = 0; j < nfr; j++) {
             const size_t fj = f0 + (size_t)j, s = fj / (size_t)T, t = fj - s * (size_t)T;
-            uint8_t *d = out + lc3_io_byte_off(io, nbytes, first_channel, s, t, T);
+            uint8_t *d = out + lc3_io_byte_off(io, nbytes, first_channel, s, t, IOABS ? 1 : T);
             for (int b = tid; b < nbytes; b += nt) d[b] = s_bytes[j * nbytes + b];
         }
     } else {
@@ -1276,6 +1349,19 @@ __global__ __launch_bounds__(512) void lc3_pack_pc_mixed_kernel(lc3_groups G, co
 }
 #endif
 
+#if LC3_IN_ITEMS_TU(1)
+__global__ __launch_bounds__(512) void LC3_MIXED_KERNEL(lc3_pack_pc_items_kernel)(lc3_groups G, const int32_t *planes, uint8_t *out, lc3_io io,
+                                                                                  unsigned *pc_timeouts) {
+    const lc3_group &g = G.g[lc3_find_group(G, blockIdx.x, 1)];
+    lc3_pack_pc_body<1>(blockIdx.x - g.wg_frame, g.ne, planes + (size_t)g.frame_base * (size_t)EP_WORDS, out, g.nbytes, g.n_streams * g.n_frames,
+                        g.n_frames, g.first_stream, io, pc_timeouts);
+}
+#endif
+#if LC3_MULTI_TU && LC3_TU_KIND == 0
+__global__ __launch_bounds__(512) void lc3_pack_pc_items_kernel_all(lc3_groups G, const int32_t *planes, uint8_t *out, lc3_io io,
+                                                                    unsigned *pc_timeouts);
+#endif
+
 // The packer's symbols as a stage of its own (lc3_enc_symbols_frame, lc3_dev_enc.h): one WAVE per frame.  A workgroup stages the
 // context lookup table once (lc3_spec_tab) and walks frames wg * 4 + wave, + 4 * gridDim.x, ...; eight waves per SIMD.  Selectable
 // (LC3GPU_PREP_SYMBOLS=2); measured against the two other forms in DESIGN.md section 6.
@@ -1299,7 +1385,7 @@ __global__ __launch_bounds__(64 * LC3_WG_WAVES, 8) void lc3_symbols_kernel(lc3_c
 // Dynamic LDS: 4096 (context lookup) + 64*20*4 (spectral model, lc3_dcf_word) + 16*11*4 (MPVQ offsets) + 152*4 (TNS models) + 144 (band index table) + 16*4*blockDim.x (scale
 // factors, [n][lane]) + blockDim.x * nbytes (frame bytes).
 #define LC3_PARSE_LDS_FIXED (4096 + 64 * LC3_DCF_ROW_WORDS * 4 + 16 * 11 * 4 + 4 * 152 + 144)
-template <class CV>
+template <class CV, int IOABS = 0>  // IOABS: as lc3_pack_body
 __device__ __forceinline__ void lc3_parse_body(lc3_cfg_slot<CV> cfg, unsigned wg, const uint8_t *in, const uint8_t *bad,
                                                int32_t *planes, int nbytes, int n_frames, int T, int first_channel, lc3_io io, int late,
                                                float *dbg = nullptr) {
@@ -1331,7 +1417,7 @@ __device__ __forceinline__ void lc3_parse_body(lc3_cfg_slot<CV> cfg, unsigned wg
         if (io.ilv || io.tab) {  // frame f = s * T + t is fetched from its own place (examples/decode.rs:86-92 for the file order)
             for (int j = 0; j < nfr; j++) {
                 const size_t fj = f0 + (size_t)j, s = fj / (size_t)T, t = fj - s * (size_t)T;
-                const uint8_t *q = in + lc3_io_byte_off(io, nbytes, first_channel, s, t, T);
+                const uint8_t *q = in + lc3_io_byte_off(io, nbytes, first_channel, s, t, IOABS ? 1 : T);
                 for (int b = tid; b < nbytes; b += fpb) s_bytes[j * nbytes + b] = q[b];
             }
         } else if ((((uintptr_t)src) & 3u) == 0) {
@@ -1361,7 +1447,7 @@ __device__ __forceinline__ void lc3_parse_body(lc3_cfg_slot<CV> cfg, unsigned wg
         for (int i = 0; i < 8; i++) c.pt[i] = 0;
         c.plast = clock64();
 #endif
-        const size_t fb = lc3_io_flag_idx(io, first_channel, f / (size_t)T, f % (size_t)T, T);  // the flag array follows the frame layout
+        const size_t fb = lc3_io_flag_idx(io, first_channel, f / (size_t)T, f % (size_t)T, IOABS ? 1 : T);  // the flag array follows the frame layout
         int rc;
         if (late == 2) rc = (bad && bad[fb]) ? -100 : lc3_parse_frame<0>(c, ne, fs_ind, n_ms_10);  // (late is launch-uniform)
         else rc = (bad && bad[fb]) ? -100 : lc3_parse_frame<1>(c, ne, fs_ind, n_ms_10);
@@ -1416,6 +1502,31 @@ __global__ __launch_bounds__(256) void lc3_parse_mixed_kernel_all(lc3_groups G, 
                                                               int T, lc3_io io, int late);
 #endif
 
+// ... over a list of items: the row's frame count, absolute table offsets (see lc3_enc_front_items_kernel).  The switch over the views
+// names lc3_parse_body<view, 1> itself: through a forwarding function template (what LC3_GROUP_VIEW needs for a second template argument)
+// the very same body was allocated 158 vector registers instead of the 112 of lc3_parse_mixed_kernel
+#if LC3_IN_ITEMS_TU(2)
+__global__ __launch_bounds__(256) void LC3_MIXED_KERNEL(lc3_parse_items_kernel)(lc3_groups G, const uint8_t *in, const uint8_t *bad, int32_t *planes,
+                                                                                lc3_io io, int late) {
+    const lc3_group &g = G.g[lc3_find_group(G, blockIdx.x, 1)];
+    int32_t *p = planes + (size_t)g.frame_base * (size_t)LC3_PLANE_WORDS;
+    const int T = LC3_UNIFORM_I32(g.n_frames), nfr = LC3_UNIFORM_I32(g.n_streams) * T;  // (the row's words are workgroup-uniform)
+    switch (g.fixed) {
+#define LC3_X(i, V) \
+    case i: lc3_parse_body<V, 1>(lc3_cfg_slot<V>{g.slot}, blockIdx.x - g.wg_frame, in, bad, p, g.nbytes, nfr, T, g.first_stream, io, late); break;
+        LC3_FOR_EACH_VIEW(LC3_X)
+#undef LC3_X
+    default:  // (the run-time view's body, as the twin carries it; the host refuses a group without a view in a multi-unit library)
+        lc3_parse_body<lc3_cfg_any, 1>(lc3_cfg_slot<lc3_cfg_any>{g.slot}, blockIdx.x - g.wg_frame, in, bad, p, g.nbytes, nfr, T, g.first_stream, io, late);
+        break;
+    }
+}
+#endif
+#if LC3_MULTI_TU && LC3_TU_KIND == 0
+__global__ __launch_bounds__(256) void lc3_parse_items_kernel_all(lc3_groups G, const uint8_t *in, const uint8_t *bad, int32_t *planes, lc3_io io,
+                                                                  int late);
+#endif
+
 // The parser of a full batch as PRODUCER / CONSUMER wave pairs (lc3_pc_produce / lc3_pc_consume, lc3_dev_dec_parse.h): a workgroup of
 // 2 x fpb threads parses fpb frames; wave w of its first half runs the range decoder's recurrence for 64 frames, wave w of the second half
 // (the same SIMD where the hardware deals a workgroup's waves round the SIMDs) everything else of those frames, the spectrum
@@ -1427,7 +1538,7 @@ static __host__ __device__ inline size_t lc3_parse_pc_lds(unsigned fpb, int nbyt
     const size_t base = (LC3_PARSE_LDS_FIXED + (size_t)fpb * (size_t)(64 + nbytes) + 15) & ~(size_t)15;
     return base + (size_t)(fpb / 64) * (4 * 64 * 4) + 64;
 }
-template <class CV>
+template <class CV, int IOABS = 0>
 __device__ __forceinline__ void lc3_parse_pc_body(lc3_cfg_slot<CV> cfg, unsigned wg, const uint8_t *in, const uint8_t *bad, int32_t *planes,
                                                   int nbytes, int n_frames, int T, int first_channel, lc3_io io, unsigned *pc_timeouts) {
     LC3_LANE_KERNEL_BEGIN();
@@ -1467,7 +1578,7 @@ __device__ __forceinline__ void lc3_parse_pc_body(lc3_cfg_slot<CV> cfg, unsigned
         if (io.ilv || io.tab) {  // frame f = s * T + t is fetched from its own place (examples/decode.rs:86-92 for the file order)
             for (int j = 0; j < nfr; j++) {
                 const size_t fj = f0 + (size_t)j, s = fj / (size_t)T, t = fj - s * (size_t)T;
-                const uint8_t *q = in + lc3_io_byte_off(io, nbytes, first_channel, s, t, T);
+                const uint8_t *q = in + lc3_io_byte_off(io, nbytes, first_channel, s, t, IOABS ? 1 : T);
                 for (int b = tid; b < nbytes; b += nt) s_bytes[j * nbytes + b] = q[b];
             }
         } else if ((((uintptr_t)src) & 3u) == 0) {
@@ -1504,7 +1615,7 @@ __device__ __forceinline__ void lc3_parse_pc_body(lc3_cfg_slot<CV> cfg, unsigned
     k.fin = s_fin + pair * (4 * 64) + lane;
     int rc_in = -100;
     if (valid) {
-        const size_t fb = lc3_io_flag_idx(io, first_channel, f / (size_t)T, f % (size_t)T, T);  // the flag array follows the frame layout
+        const size_t fb = lc3_io_flag_idx(io, first_channel, f / (size_t)T, f % (size_t)T, IOABS ? 1 : T);  // the flag array follows the frame layout
         rc_in = (bad && bad[fb]) ? -100 : 0;
     }
     if (role == 0) {  // pc_timeouts: the handle's sticky count of pair halves that gave up on their partner (lc3gpu_decoder_pair_timeouts)
@@ -1539,6 +1650,25 @@ __global__ __launch_bounds__(512) void LC3_MIXED_KERNEL(lc3_parse_pc_mixed_kerne
 #if LC3_MULTI_TU && LC3_TU_KIND == 0
 __global__ __launch_bounds__(512) void lc3_parse_pc_mixed_kernel_all(lc3_groups G, const uint8_t *in, const uint8_t *bad, int32_t *planes, int T,
                                                                  lc3_io io, unsigned *pc_timeouts);
+#endif
+
+template <class CV>
+__device__ __forceinline__ void lc3_parse_pc_body_items(lc3_cfg_slot<CV> cfg, unsigned wg, const uint8_t *in, const uint8_t *bad, int32_t *planes,
+                                                        int nbytes, int n_frames, int T, int first_pos, lc3_io io, unsigned *pc_timeouts) {
+    lc3_parse_pc_body<CV, 1>(cfg, wg, in, bad, planes, nbytes, n_frames, T, first_pos, io, pc_timeouts);
+}
+#if LC3_IN_ITEMS_TU(3)
+__global__ __launch_bounds__(512) void LC3_MIXED_KERNEL(lc3_parse_pc_items_kernel)(lc3_groups G, const uint8_t *in, const uint8_t *bad, int32_t *planes,
+                                                                                   lc3_io io, unsigned *pc_timeouts) {
+    const lc3_group &g = G.g[lc3_find_group(G, blockIdx.x, 1)];
+    int32_t *p = planes + (size_t)g.frame_base * (size_t)LC3_PLANE_WORDS;
+    LC3_GROUP_VIEW_LIST(lc3_parse_pc_body_items, g, blockIdx.x - g.wg_frame, in, bad, p, g.nbytes, g.n_streams * g.n_frames, g.n_frames, g.first_stream,
+                        io, pc_timeouts);
+}
+#endif
+#if LC3_MULTI_TU && LC3_TU_KIND == 0
+__global__ __launch_bounds__(512) void lc3_parse_pc_items_kernel_all(lc3_groups G, const uint8_t *in, const uint8_t *bad, int32_t *planes, lc3_io io,
+                                                                     unsigned *pc_timeouts);
 #endif
 
 // Spectrum reconstruction D4-D8 of a full batch (lc3_dev_dec_recon.h), between the parser and the synthesis kernel:
@@ -1576,6 +1706,19 @@ __global__ __launch_bounds__(64 * LC3_WG_WAVES, LC3_RECON_WAVES) void LC3_MIXED_
 #endif
 #if LC3_MULTI_TU && LC3_TU_KIND == 0
 __global__ __launch_bounds__(64 * LC3_WG_WAVES, LC3_RECON_WAVES) void lc3_recon_mixed_kernel_all(lc3_groups G, int32_t *planes, int T);
+#endif
+#if LC3_IN_ITEMS_TU(4)
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, LC3_RECON_WAVES) void LC3_MIXED_KERNEL(lc3_recon_items_kernel)(lc3_groups G, int32_t *planes) {
+    const lc3_group &g = G.g[lc3_find_group(G, blockIdx.x, 1)];
+    int32_t *p = planes + (size_t)g.frame_base * (size_t)LC3_PLANE_WORDS;
+    const unsigned wg = blockIdx.x - g.wg_frame;
+    const size_t nfr = (size_t)g.n_streams * (size_t)g.n_frames, left = nfr - (size_t)wg * LC3_WG_WAVES;  // this workgroup's four frames only
+    LC3_GROUP_VIEW_LIST(lc3_recon_body, g, 0u, 1u, p + (size_t)wg * LC3_WG_WAVES * (size_t)LC3_PLANE_WORDS, g.nbytes,
+                        left < LC3_WG_WAVES ? left : (size_t)LC3_WG_WAVES);
+}
+#endif
+#if LC3_MULTI_TU && LC3_TU_KIND == 0
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, LC3_RECON_WAVES) void lc3_recon_items_kernel_all(lc3_groups G, int32_t *planes);
 #endif
 // LC3_TNS_FPB frames per workgroup, one wave per 64 of them: 16 KB of (dynamic) LDS per wave for its frames' band gains, band-major.
 // Four waves per workgroup so that the 1 024 waves of a full batch land one per SIMD (single-wave workgroups are packed several to a CU).
@@ -1616,6 +1759,16 @@ __global__ __launch_bounds__(LC3_TNS_FPB) void LC3_MIXED_KERNEL(lc3_tns_mixed_ke
 #endif
 #if LC3_MULTI_TU && LC3_TU_KIND == 0
 __global__ __launch_bounds__(LC3_TNS_FPB) void lc3_tns_mixed_kernel_all(lc3_groups G, int32_t *planes, int T);
+#endif
+#if LC3_IN_ITEMS_TU(4)
+__global__ __launch_bounds__(LC3_TNS_FPB) void LC3_MIXED_KERNEL(lc3_tns_items_kernel)(lc3_groups G, int32_t *planes) {
+    const lc3_group &g = G.g[lc3_find_group(G, blockIdx.x, 1)];
+    int32_t *p = planes + (size_t)g.frame_base * (size_t)LC3_PLANE_WORDS;
+    LC3_GROUP_VIEW_LIST(lc3_tns_body, g, blockIdx.x - g.wg_frame, p, (size_t)g.n_streams * (size_t)g.n_frames);
+}
+#endif
+#if LC3_MULTI_TU && LC3_TU_KIND == 0
+__global__ __launch_bounds__(LC3_TNS_FPB) void lc3_tns_items_kernel_all(lc3_groups G, int32_t *planes);
 #endif
 
 // LATE: the launch reconstructs the spectrum here (lc3_dec_reconstruct_wave) -- a compile-time switch, so that the kernels of full
@@ -1723,7 +1876,7 @@ __global__ __launch_bounds__(64 * LC3_WG_WAVES, 4) void lc3_decode_mixed_late_ke
 #endif
 
 // the synthesis over a list of a mixed handle's streams, in its lane and late reconstruction forms (see lc3_enc_front_mixed_list_kernel)
-template <class CV, int LATE>
+template <class CV, int LATE, int IOABS = 0>  // IOABS: as lc3_enc_front_body_mixed_list
 __device__ __forceinline__ void lc3_decode_body_mixed_list(lc3_cfg_slot<CV> cfg, unsigned wg, lc3_dec_state *states, const int32_t *entries,
                                                            int first_pos, int n_streams, const int32_t *planes, int16_t *pcm, int nbytes,
                                                            int n_frames, const lc3_stream_io *tab) {
@@ -1735,7 +1888,7 @@ __device__ __forceinline__ void lc3_decode_body_mixed_list(lc3_cfg_slot<CV> cfg,
     typename CV::bind_t c0 = CV::bind(lc3_cfg_table[cfg.id]);
     const int entry = lc3_list_entry(entries, first_pos + s);
     lc3_dec_state *gst = states + (size_t)lc3_list_channel(entry);
-    int16_t *pcm_s = pcm + (size_t)n_frames * (size_t)lc3_mlist_off(&tab[first_pos + s].pcm_off1);
+    int16_t *pcm_s = pcm + (size_t)(IOABS ? 1 : n_frames) * (size_t)lc3_mlist_off(&tab[first_pos + s].pcm_off1);
 #ifndef LC3_TABLES_IN_GLOBAL
     const lc3_fft_image_regs tab_regs = lc3_fft_tables_image_issue(c0.stage_image);
 #endif
@@ -1776,6 +1929,43 @@ __global__ __launch_bounds__(64 * LC3_WG_WAVES, 4) void LC3_MIXED_KERNEL(lc3_dec
     LC3_GROUP_VIEW_LIST(lc3_decode_body_mixed_list_late, g, blockIdx.x - g.wg_stream, states, entries, g.first_stream, g.n_streams, p, pcm, g.nbytes,
                         n_frames, io.tab);
 }
+#endif
+// ... over a list of items: the row's frame count, absolute table offsets (see lc3_enc_front_items_kernel)
+template <class CV>
+__device__ __forceinline__ void lc3_decode_body_items_now(lc3_cfg_slot<CV> cfg, unsigned wg, lc3_dec_state *states, const int32_t *entries,
+                                                          int first_pos, int n_streams, const int32_t *planes, int16_t *pcm, int nbytes,
+                                                          int n_frames, const lc3_stream_io *tab) {
+    lc3_decode_body_mixed_list<CV, 0, 1>(cfg, wg, states, entries, first_pos, n_streams, planes, pcm, nbytes, n_frames, tab);
+}
+template <class CV>
+__device__ __forceinline__ void lc3_decode_body_items_late(lc3_cfg_slot<CV> cfg, unsigned wg, lc3_dec_state *states, const int32_t *entries,
+                                                           int first_pos, int n_streams, const int32_t *planes, int16_t *pcm, int nbytes,
+                                                           int n_frames, const lc3_stream_io *tab) {
+    lc3_decode_body_mixed_list<CV, 1, 1>(cfg, wg, states, entries, first_pos, n_streams, planes, pcm, nbytes, n_frames, tab);
+}
+#if LC3_IN_ITEMS_TU(4)
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, 4) void LC3_MIXED_KERNEL(lc3_decode_items_kernel)(lc3_groups G, lc3_dec_state *states,
+                                                                                const int32_t *entries, const int32_t *planes,
+                                                                                int16_t *pcm, lc3_io io) {
+    const lc3_group &g = G.g[lc3_find_group(G, blockIdx.x, 0)];
+    const int32_t *p = planes + (size_t)g.frame_base * (size_t)LC3_PLANE_WORDS;
+    LC3_GROUP_VIEW_LIST(lc3_decode_body_items_now, g, blockIdx.x - g.wg_stream, states, entries, g.first_stream, g.n_streams, p, pcm, g.nbytes,
+                        g.n_frames, io.tab);
+}
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, 4) void LC3_MIXED_KERNEL(lc3_decode_items_late_kernel)(lc3_groups G, lc3_dec_state *states,
+                                                                                     const int32_t *entries, const int32_t *planes,
+                                                                                     int16_t *pcm, lc3_io io) {
+    const lc3_group &g = G.g[lc3_find_group(G, blockIdx.x, 0)];
+    const int32_t *p = planes + (size_t)g.frame_base * (size_t)LC3_PLANE_WORDS;
+    LC3_GROUP_VIEW_LIST(lc3_decode_body_items_late, g, blockIdx.x - g.wg_stream, states, entries, g.first_stream, g.n_streams, p, pcm, g.nbytes,
+                        g.n_frames, io.tab);
+}
+#endif
+#if LC3_MULTI_TU && LC3_TU_KIND == 0
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, 4) void lc3_decode_items_kernel_all(lc3_groups G, lc3_dec_state *states, const int32_t *entries,
+                                                                                const int32_t *planes, int16_t *pcm, lc3_io io);
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, 4) void lc3_decode_items_late_kernel_all(lc3_groups G, lc3_dec_state *states, const int32_t *entries,
+                                                                                     const int32_t *planes, int16_t *pcm, lc3_io io);
 #endif
 #if LC3_MULTI_TU && LC3_TU_KIND == 0
 __global__ __launch_bounds__(64 * LC3_WG_WAVES, 4) void lc3_decode_mixed_list_kernel_all(lc3_groups G, lc3_dec_state *states, const int32_t *entries,
@@ -2645,19 +2835,59 @@ struct HandleCommon {
     static size_t mlist_bytes(int n) { return mlist_tab_offset(n) + sizeof(lc3_stream_io) * (size_t)n; }
     // builds the plan P of a call over channels[n] (already checked; fresh: per internal index) in a free pinned slot and sends it, in
     // stream order on `s`; the handle's description in the plan's terms is written down at the first call
+    void mlist_describe() {
+        if (!mlist_groups.empty()) return;
+        mlist_groups.resize(groups.size());
+        for (size_t g = 0; g < groups.size(); g++)
+            mlist_groups[g] = {groups[g].h.slot, groups[g].h.view, groups[g].nbytes, groups[g].h.c.ne, groups[g].h.c.nb, groups[g].h.c.nf};
+        mlist_streams.resize(streams.size());
+        for (size_t i = 0; i < streams.size(); i++) mlist_streams[i] = {streams[i].group, streams[i].internal};
+    }
     int mlist_send(const int32_t *channels, int n, const uint8_t *fresh, hipStream_t s, lc3_mlist_plan &P) {
-        if (mlist_groups.empty()) {
-            mlist_groups.resize(groups.size());
-            for (size_t g = 0; g < groups.size(); g++)
-                mlist_groups[g] = {groups[g].h.slot, groups[g].h.view, groups[g].nbytes, groups[g].h.c.ne, groups[g].h.c.nb, groups[g].h.c.nf};
-            mlist_streams.resize(streams.size());
-            for (size_t i = 0; i < streams.size(); i++) mlist_streams[i] = {streams[i].group, streams[i].internal};
-        }
+        mlist_describe();
         uint8_t *slot = nullptr;
         const int rc = mlist_ring.acquire(mlist_bytes(num_channels), &slot);
         if (rc) return rc;
         lc3_mlist_build(mlist_groups.data(), (int)mlist_groups.size(), mlist_streams.data(), fresh, channels, n, (int32_t *)slot,
                         (lc3_stream_io *)(slot + mlist_tab_offset(n)), P);
+        return mlist_ring.upload(mlist_bytes(n), s);
+    }
+    // The items of an items call (lc3gpu_*_mixed_items), checked on the host: LC3GPU_OK, or the code of the first item that is refused;
+    // nothing is queued or changed.  min_bytes: 20 for encoders, 1 for decoders.  frames / max_frames: the call's total and its largest
+    // per-item count (what the kernel forms are chosen by)
+    int items_check(const lc3gpu_item *items, int n, int min_bytes, size_t *frames, int *max_frames) {
+        if (list_seen.size() != (size_t)num_channels) list_seen.assign((size_t)num_channels, 0u);
+        if (++list_call == 0u) {
+            std::fill(list_seen.begin(), list_seen.end(), 0u);
+            list_call = 1u;
+        }
+        size_t total = 0;
+        int most = 0;
+        for (int i = 0; i < n; i++) {
+            const lc3gpu_item &it = items[i];
+            if (it.channel < 0 || it.channel >= num_channels || list_seen[(size_t)it.channel] == list_call) return LC3GPU_ECHANNEL;
+            list_seen[(size_t)it.channel] = list_call;
+            if (it.n_frames < 1) return LC3GPU_ELENGTH;
+            if (it.nbytes != 0 && (it.nbytes < min_bytes || it.nbytes > LC3_MAX_NE)) return LC3GPU_ELENGTH;
+            if (it.reserved != 0) return LC3GPU_EINVAL;
+            total += (size_t)it.n_frames;
+            most = std::max(most, it.n_frames);
+        }
+        if (total > (size_t)0x7fffffff) return LC3GPU_ELENGTH;  // (frame counts and flag offsets are 32-bit on the device)
+        *frames = total;
+        *max_frames = most;
+        return LC3GPU_OK;
+    }
+    // the plan of an items call (lc3_mitems_build), built into a pinned slot and sent as mlist_send sends a list's: the same 28 bytes per item
+    lc3_mitems_plan mitems_plan;
+    int mitems_send(const lc3gpu_item *items, int n, const uint8_t *fresh, hipStream_t s) {
+        static_assert(sizeof(lc3gpu_item) == sizeof(lc3_mitem), "lc3gpu_item is the plan's item");
+        mlist_describe();
+        uint8_t *slot = nullptr;
+        const int rc = mlist_ring.acquire(mlist_bytes(num_channels), &slot);
+        if (rc) return rc;
+        lc3_mitems_build(mlist_groups.data(), mlist_streams.data(), fresh, (const lc3_mitem *)items, n, (int32_t *)slot,
+                         (lc3_stream_io *)(slot + mlist_tab_offset(n)), mitems_plan);
         return mlist_ring.upload(mlist_bytes(n), s);
     }
     const int32_t *d_mlist_entries() const { return (const int32_t *)mlist_ring.d; }
@@ -2849,7 +3079,7 @@ struct HandleGroups {
             g.nbytes = gh.nbytes;
             g.ne = gh.h.c.ne;
             g.nb = gh.h.c.nb;
-            g.pad = 0;
+            g.n_frames = 0;  // (the launch's argument holds: lc3_host_mixed_list.h)
             g.frame_base = (long long)frames;
             t.wg_stream += (unsigned)((gh.n_streams + LC3_WG_WAVES - 1) / LC3_WG_WAVES);
             t.wg_frame += (unsigned)(((size_t)gh.n_streams * (size_t)T + fpb - 1) / fpb);
@@ -2866,6 +3096,27 @@ struct ListGroups {
         lc3_mlist_groups(hc.mlist_groups.data(), (int)hc.mlist_groups.size(), P, T, (unsigned)LC3_WG_WAVES, fpb, t.G, t.wg_stream, t.wg_frame);
     }
 };
+
+// launch set [b0, b1) of the buckets of an items plan (lc3_host_mixed_list.h): a row per bucket, the frame count in the row
+struct ItemsGroups {
+    const HandleCommon &hc;
+    const lc3_mitems_plan &P;
+    int b0, b1;
+    void operator()(unsigned fpb, GroupTable &t) const {
+        lc3_mitems_rows(hc.mlist_groups.data(), P, b0, b1, (unsigned)LC3_WG_WAVES, fpb, t.G, t.wg_stream, t.wg_frame);
+    }
+};
+// one stage of an items call: launch(groups, max_nbytes of the set) for every launch set of the plan, in order, on the call's stream
+template <class Launch>
+int items_stage(const HandleCommon &hc, const lc3_mitems_plan &P, Launch launch) {
+    for (int k = 0; k < lc3_mitems_sets(P); k++) {
+        int b0, b1;
+        lc3_mitems_set(P, k, b0, b1);
+        const int rc = launch(ItemsGroups{hc, P, b0, b1}, lc3_mitems_max_nbytes(P, b0, b1));
+        if (rc) return rc;
+    }
+    return LC3GPU_OK;
+}
 
 }  // namespace
 
@@ -3814,6 +4065,86 @@ int lc3gpu_encode_mixed_list(lc3gpu_encoder *e, const int32_t *channels, int n_l
     return call.end(rc);
 }
 
+// A list of items of a mixed handle: a frame count and a frame size per listed stream.  As lc3gpu_encode_mixed_list -- host check, plan into
+// a pinned slot, one upload -- with the items bucketed by (configuration, frame size, frame count) and the items twins of every kernel,
+// which read the frame count from their group row: one launch per kernel per LC3_MAX_GROUPS buckets.  The kernel forms are chosen once
+// per call, by its total number of frames.
+int lc3gpu_encode_mixed_items(lc3gpu_encoder *e, const lc3gpu_item *items, int n_items, const int16_t *d_pcm, uint8_t *d_out, void *stream_) {
+    if (!e || !e->mixed || n_items < 0) return LC3GPU_EINVAL;
+    if (n_items == 0) return LC3GPU_OK;
+    if (!items || !d_pcm || !d_out || ((uintptr_t)d_pcm & 3u) != 0) return LC3GPU_EINVAL;
+    if (!e->mixed_list_views_ok()) return LC3GPU_EUNSUPPORTED;
+    size_t frames = 0;
+    int max_frames = 0;
+    int rc = e->items_check(items, n_items, 20, &frames, &max_frames);
+    if (rc) return rc;
+    LC3_ON_DEVICE(e);
+    hipStream_t stream = (hipStream_t)stream_;
+    BatchCall call(*e, stream);
+    rc = call.begin();
+    if (rc == LC3GPU_OK) rc = encoder_reserve_planes(e, frames, stream);
+    if (rc == LC3GPU_OK) rc = e->mitems_send(items, n_items, e->fresh_mask.data(), stream);
+    if (rc) return rc;
+    const lc3_mitems_plan &P = e->mitems_plan;
+    const int32_t *d_entries = e->d_mlist_entries();
+    const lc3_io io = {0, e->d_mlist_tab(n_items)};
+    const dim3 wg_block(64 * LC3_WG_WAVES);
+    const bool pairs = lc3_prep_symbols_mode(frames) == 0 && lc3_pack_pc_enabled();
+    if (pairs && (rc = pc_optin_once(*e, lc3_pack_pc_optin)) != LC3GPU_OK) return rc;
+    call.arm();
+    rc = encode_stages(
+        e, stream, 0, nullptr,
+        [&] {
+            return items_stage(*e, P, [&](ItemsGroups groups, int) {
+                GroupTable t;
+                groups(256u, t);
+                hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_enc_front_items_kernel), dim3(t.wg_stream), wg_block, 0, stream, t.G, e->d_states, d_entries, d_pcm,
+                                   e->d_mid, e->d_planes, io, e->spec_flags);
+                return LC3GPU_OK;
+            });
+        },
+        [&] {
+            return items_stage(*e, P, [&](ItemsGroups groups, int) {
+                GroupTable t;
+                groups(256u, t);
+                hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_sns_vq_items_kernel), dim3(t.wg_frame), dim3(256), 0, stream, t.G, e->d_mid, e->d_planes,
+                                   e->spec_flags);
+                return LC3GPU_OK;
+            });
+        },
+        [&] {
+            return items_stage(*e, P, [&](ItemsGroups groups, int) {
+                GroupTable t;
+                groups(256u, t);
+                hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_enc_back_items_kernel), dim3(t.wg_stream), wg_block, 0, stream, t.G, e->d_states, d_entries,
+                                   (const float *)e->d_mid, e->d_planes, e->spec_flags | lc3_prep_symbols_flag(frames, true));
+                return LC3GPU_OK;
+            });
+        },
+        [] { return LC3GPU_OK; },
+        [&] {
+            return items_stage(*e, P, [&](ItemsGroups groups, int max_nbytes) {
+                GroupTable t;  // (the LDS of a launch set is sized by ITS largest frame)
+                if (pairs) {
+                    const unsigned pfpb = lc3_pack_pc_fpb(max_nbytes);
+                    groups(pfpb, t);
+                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_pack_pc_items_kernel), dim3(t.wg_frame), dim3(2 * pfpb), lc3_pack_pc_lds(pfpb, max_nbytes),
+                                       stream, t.G, (const int32_t *)e->d_planes, d_out, io, e->d_pc_timeouts);
+                } else {
+                    const unsigned fpb = lc3_frame_block_fit(LC3_PACK_LDS_FIXED, (size_t)max_nbytes);
+                    const size_t lds = LC3_PACK_LDS_FIXED + (((size_t)fpb * (size_t)max_nbytes + 3) & ~(size_t)3) + 4;
+                    groups(fpb, t);
+                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_pack_items_kernel), dim3(t.wg_frame), dim3(fpb), lds, stream, t.G, (const int32_t *)e->d_planes,
+                                       d_out, io);
+                }
+                return LC3GPU_OK;
+            });
+        });
+    if (rc == LC3GPU_OK)
+        for (int i = 0; i < n_items; i++) e->fresh_mask[(size_t)e->streams[(size_t)items[i].channel].internal] = 0;
+    return call.end(rc);
+}
+
 static int encode_frame_host(lc3gpu_encoder *e, int channel_index, const int16_t *samples_in, int n_samples,
                              uint8_t *buf_out, int nbytes, float *dbg) {
     if (!e || !samples_in || !buf_out) return LC3GPU_EINVAL;
@@ -4394,6 +4725,87 @@ int lc3gpu_decode_mixed_list(lc3gpu_decoder *d, const int32_t *channels, int n_l
     // (on failure the channels noted fresh stay noted: whatever ran, their next call starts them from the constructed state)
     if (rc == LC3GPU_OK)
         for (int i = 0; i < n_list; i++) d->fresh_clear(d->streams[(size_t)channels[i]].internal);
+    return call.end(rc);
+}
+
+// A list of items of a mixed handle, as lc3gpu_encode_mixed_items: the parser and reconstruction form are chosen once per call, by its
+// total number of frames and its largest per-item count
+int lc3gpu_decode_mixed_items(lc3gpu_decoder *d, const lc3gpu_item *items, int n_items, const uint8_t *d_in, const uint8_t *d_bad, int16_t *d_pcm,
+                              void *stream_) {
+    if (!d || !d->mixed || n_items < 0) return LC3GPU_EINVAL;
+    if (n_items == 0) return LC3GPU_OK;
+    if (!items || !d_in || !d_pcm || ((uintptr_t)d_pcm & 3u) != 0) return LC3GPU_EINVAL;
+    if (!d->mixed_list_views_ok()) return LC3GPU_EUNSUPPORTED;
+    size_t frames = 0;
+    int max_frames = 0;
+    int rc = d->items_check(items, n_items, 1, &frames, &max_frames);
+    if (rc) return rc;
+    LC3_ON_DEVICE(d);
+    hipStream_t stream = (hipStream_t)stream_;
+    const int mode = lc3_recon_mode(frames, max_frames);
+    const bool pairs = mode == LC3_RECON_LANE && lc3_parse_pc_enabled();
+    BatchCall call(*d, stream);
+    rc = call.begin();
+    if (rc == LC3GPU_OK) rc = decoder_reserve_planes(d, frames, stream);
+    if (rc == LC3GPU_OK && mode == LC3_RECON_WAVE) rc = lc3_tns_lds_optin();
+    if (rc == LC3GPU_OK && pairs) rc = pc_optin_once(*d, lc3_parse_pc_optin);
+    if (rc == LC3GPU_OK) rc = d->mitems_send(items, n_items, d->fresh_mask.data(), stream);
+    if (rc) return rc;
+    const lc3_mitems_plan &P = d->mitems_plan;
+    const int32_t *d_entries = d->d_mlist_entries();
+    const lc3_io io = {0, d->d_mlist_tab(n_items)};
+    call.arm();
+    rc = decode_stages(
+        d, stream, 0, mode,
+        [&] {
+            return items_stage(*d, P, [&](ItemsGroups groups, int max_nbytes) {
+                GroupTable t;
+                if (pairs) {
+                    const unsigned pfpb = lc3_parse_pc_fpb(max_nbytes);
+                    groups(pfpb, t);
+                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_parse_pc_items_kernel), dim3(t.wg_frame), dim3(2 * pfpb), lc3_parse_pc_lds(pfpb, max_nbytes),
+                                       stream, t.G, d_in, d_bad, d->d_planes, io, d->d_pc_timeouts);
+                } else {
+                    const unsigned fpb = lc3_frame_block_fit(LC3_PARSE_LDS_FIXED, (size_t)(64 + max_nbytes));
+                    const size_t lds = LC3_PARSE_LDS_FIXED + (size_t)fpb * (size_t)(64 + max_nbytes);
+                    groups(fpb, t);
+                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_parse_items_kernel), dim3(t.wg_frame), dim3(fpb), lds, stream, t.G, d_in, d_bad, d->d_planes, io,
+                                       mode);
+                }
+                return LC3GPU_OK;
+            });
+        },
+        [&] {
+            return items_stage(*d, P, [&](ItemsGroups groups, int) {
+                GroupTable t;
+                groups((unsigned)LC3_WG_WAVES, t);
+                hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_recon_items_kernel), dim3(t.wg_frame), dim3(64 * LC3_WG_WAVES), 0, stream, t.G, d->d_planes);
+                return LC3GPU_OK;
+            });
+        },
+        [&] {
+            return items_stage(*d, P, [&](ItemsGroups groups, int) {
+                GroupTable t;
+                groups((unsigned)LC3_TNS_FPB, t);
+                hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_tns_items_kernel), dim3(t.wg_frame), dim3(LC3_TNS_FPB), LC3_TNS_LDS, stream, t.G, d->d_planes);
+                return LC3GPU_OK;
+            });
+        },
+        [&] {
+            return items_stage(*d, P, [&](ItemsGroups groups, int) {
+                GroupTable t;
+                groups(256u, t);
+                if (mode == LC3_RECON_LATE)
+                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_decode_items_late_kernel), dim3(t.wg_stream), dim3(64 * LC3_WG_WAVES), 0, stream, t.G, d->d_states,
+                                       d_entries, (const int32_t *)d->d_planes, d_pcm, io);
+                else
+                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_decode_items_kernel), dim3(t.wg_stream), dim3(64 * LC3_WG_WAVES), 0, stream, t.G, d->d_states,
+                                       d_entries, (const int32_t *)d->d_planes, d_pcm, io);
+                return LC3GPU_OK;
+            });
+        });
+    if (rc == LC3GPU_OK)
+        for (int i = 0; i < n_items; i++) d->fresh_clear(d->streams[(size_t)items[i].channel].internal);
     return call.end(rc);
 }
 

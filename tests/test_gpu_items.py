@@ -1,0 +1,378 @@
+"""lc3gpu_encode_mixed_items / lc3gpu_decode_mixed_items on the GPU: any subset of a mixed handle's streams, each with its own number of
+frames and its own frame size this call.  The yardstick is one oracle encoder / decoder per channel LIFE, called frame by frame at that
+frame's size (a reset channel gets a new oracle object): identical bytes, identical PCM; and lc3gpu_*_mixed_list on twin handles where a
+call's items share one frame count and the descriptors' sizes."""
+import ctypes
+import importlib
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import oracle_lib as O
+import test_gpu_mixed_list as ML
+
+pytestmark = pytest.mark.gpu
+pkg = importlib.import_module("lc3-codec_amd")
+synth = importlib.import_module("lc3-codec_amd.synth")
+ROOT = ML.ROOT
+MIXED = ML.MIXED
+EINVAL, ECHANNEL, ELENGTH = -1, -2, -3
+torch_mod, dev, cur_stream, _cat = ML.torch_mod, ML.dev, ML.cur_stream, ML._cat
+
+
+class ItemsServer(ML.MixedServer):
+    """MixedServer driven by the items calls.  The encoder's frames of a channel queue up for its decoder, which may take fewer per tick
+    (a jitter buffer).  Items are (channel, n_frames, nbytes) with the DECODER's channel index; nbytes 0 = the descriptor's."""
+
+    def __init__(self, S, total_frames, seed, configs=MIXED):
+        super().__init__(S, total_frames, seed, configs)
+        self.queue = {c: [] for c in range(self.n_ch)}
+        for c, fr in self.frames8k.items():
+            self.queue[c] = [f for f in fr]
+
+    def size(self, c, nb):
+        return nb or self.descs[c][2]
+
+    def encode(self, items, what=""):
+        torch = torch_mod()
+        items = [(int(c), int(T), int(nb)) for c, T, nb in items if self.encodable[c]]
+        if not items:
+            return
+        pcm = [self.material[c][self.cursor[c]:self.cursor[c] + T] for c, T, _ in items]
+        ref = [np.stack([self.enc_or[c].encode_frame(pcm[i][j], self.size(c, nb)) for j in range(T)]) for i, (c, T, nb) in enumerate(items)]
+        d_out = torch.full((sum(r.size for r in ref),), 0xA5, dtype=torch.uint8, device="cuda")
+        self.enc.encode_mixed_items([(self.enc_index[c], T, nb) for c, T, nb in items], dev(_cat(pcm, np.int16)), d_out, stream=cur_stream())
+        torch.cuda.synchronize()
+        got, off = d_out.cpu().numpy(), 0
+        for i, (c, T, nb) in enumerate(items):
+            assert np.array_equal(got[off:off + ref[i].size].reshape(T, -1), ref[i]), "%s encode: item %d, channel %d %s, %d frames at %d bytes differs from the oracle" % (
+                what, i, c, self.descs[c], T, self.size(c, nb))
+            off += ref[i].size
+            self.cursor[c] += T
+            self.queue[c] += [f for f in ref[i]]
+
+    def decode(self, items, what="", raw=()):
+        """raw: channels whose frames of this call are random bytes of the item's size, not the encoder's (sizes no encoder produces)"""
+        torch = torch_mod()
+        rng = self.rng
+        items = [(int(c), int(T), int(nb)) for c, T, nb in items]
+        data, want, flags = [], [], []
+        for c, T, nb in items:
+            n = self.size(c, nb)
+            if c in raw:
+                fr = rng.integers(0, 256, (T, n)).astype(np.uint8)
+            else:
+                fr = np.stack(self.queue[c][:T])
+                del self.queue[c][:T]
+            assert fr.shape == (T, n), "the test's own queue: %s frames of %d bytes for channel %d" % (fr.shape, n, c)
+            xor = np.zeros((T, n), np.uint8)
+            for j in np.flatnonzero(rng.random(T) < 0.12):
+                xor[j, rng.integers(0, n, 3)] = rng.integers(1, 256, 3)
+            fr = fr ^ xor
+            fl = (rng.random(T) < 0.1).astype(np.uint8)
+            w = np.zeros((T, self.nf[c]), np.int16)
+            for j in range(T):
+                buf = fr[j].copy()
+                if fl[j]:
+                    buf[-2:] = 0xFF  # (the oracle has no external flag: unparsable side information at the frame's own size)
+                _, w[j] = self.dec_or[c].decode_frame(buf)
+                assert not fl[j] or self.dec_or[c].last_was_plc()
+                self.plc[c] += int(self.dec_or[c].last_was_plc())
+            data.append(fr)
+            want.append(w)
+            flags.append(fl)
+        d_pcm = torch.full((sum(w.size for w in want),), 12345, dtype=torch.int16, device="cuda")
+        self.dec.decode_mixed_items(items, dev(_cat(data, np.uint8)), d_pcm, stream=cur_stream(), d_bad_frame=dev(_cat(flags, np.uint8)))
+        torch.cuda.synchronize()
+        got, off = d_pcm.cpu().numpy(), 0
+        for i, (c, T, nb) in enumerate(items):
+            assert np.array_equal(got[off:off + want[i].size].reshape(T, -1), want[i]), "%s decode: item %d, channel %d %s, %d frames at %d bytes differs from the oracle" % (
+                what, i, c, self.descs[c], T, self.size(c, nb))
+            off += want[i].size
+
+    def tick(self, items, what="", raw=()):
+        self.encode(items, what)
+        self.decode(items, what, raw)
+
+
+def test_30_ms_ticks():
+    """ten encodable configurations on the encoder, twelve on the decoder, two streams each; four 30 ms ticks: a 10 ms stream takes 3 frames,
+    a 7.5 ms stream 4; a random fifth is dropped per tick; resets between ticks; a third of the decoder's items take 1..3 frames only"""
+    sv = ItemsServer(2, 4 * 4 + 2, seed=11)
+    rng = np.random.default_rng(30)
+    jitter = 0
+    for k in range(4):
+        if k:
+            sv.reset_enc([int(c) for c in rng.choice(sv.n_ch, 3, replace=False)])
+            sv.reset_dec([int(c) for c in rng.choice(sv.n_ch, 3, replace=False)])  # (a new decoder object takes the frames still queued)
+        due = [int(c) for c in rng.permutation(sv.n_ch) if rng.random() >= 0.2]
+        owed = lambda c: 4 if sv.descs[c][1] == 7500 else 3
+        sv.encode([(c, owed(c), 0) for c in due], "tick %d" % k)
+        dec_items = []
+        for c in [int(c) for c in rng.permutation(due)]:
+            T = min(owed(c), len(sv.queue[c]))
+            if rng.random() < 1 / 3:
+                T = min(T, int(rng.integers(1, 4)))
+                jitter += 1
+            dec_items.append((c, T, 0))
+        assert len(set(T for _, T, _ in dec_items)) >= 3
+        sv.decode(dec_items, "tick %d" % k)
+    assert jitter >= 4
+    assert sv.dec.plc_events() == sum(sv.plc) > 0, "PLC count over the channels' current lives"
+    assert sv.enc.pair_timeouts() == 0 and sv.dec.pair_timeouts() == 0
+
+
+def test_sizes_per_item_and_a_channel_walking_through_sizes():
+    sv = ItemsServer(2, 16, seed=13, configs=MIXED[:10])  # twenty channels, every one encodable; channels c and c + 10 share a configuration
+    a, b, w = 4, 14, 9  # 48 kHz / 10 ms twice; the walking channel: 48 kHz / 7.5 ms
+    own = sv.descs[w][2]
+    for k, nb in enumerate((0, 20, 400, own, 0)):
+        others = [(int(c), 1 + (c % 2), 0) for c in np.random.default_rng(k).choice([c for c in range(sv.n_ch) if c not in (a, b, w)], 6, replace=False)]
+        items = others[:3] + [(a, 2, 90)] + others[3:5] + [(w, 2, nb), (b, 2, 200)] + others[5:]  # a and b: one configuration, two sizes, one tick
+        sv.tick(items, "tick %d" % k)
+    # the decoder alone: frames of one byte cannot hold side information -- concealed and counted
+    plc0 = sv.plc[w]
+    sv.decode([(w, 2, 1), (a, 1, 1), (3, 1, 0)] if sv.queue[3] else [(w, 2, 1), (a, 1, 1)], "1-byte frames", raw=(w, a))
+    assert sv.plc[w] == plc0 + 2
+    assert sv.dec.plc_events() == sum(sv.plc)
+    # the handle's mixed-list call still codes every stream at its descriptor's size
+    for c in range(sv.n_ch):
+        sv.queue[c] = []
+    sv.step([w, a, 2, b, 17], 2, "list", "mixed_list after the items calls")
+
+
+def _items_vs_list(S, sizes, seed=3, tile=None):
+    """items with one common T and nbytes = 0 against lc3gpu_*_mixed_list on twin handles: the list in order and a permutation"""
+    torch = torch_mod()
+    descs, pcm = ML._twin_setup(S, sum(sizes), seed, tile)
+    n = len(descs)
+    nf = [pkg.Lc3Config(d[0], d[1]).nf for d in descs]
+    rng = np.random.default_rng(seed)
+    perm = [int(c) for c in rng.permutation(n)]
+    encs = [pkg.Lc3Encoder.mixed(descs) for _ in range(4)]  # list / items, in order; list / items, permuted
+    decs = [pkg.Lc3Decoder.mixed(descs) for _ in range(4)]
+    st, t0 = cur_stream(), 0
+    for T in sizes:
+        boff = np.concatenate([[0], np.cumsum([T * d[2] for d in descs])]).astype(np.int64)
+        poff = np.concatenate([[0], np.cumsum([T * f for f in nf])]).astype(np.int64)
+        gather_b = dev(np.concatenate([np.arange(boff[c], boff[c + 1]) for c in perm]))
+        gather_p = dev(np.concatenate([np.arange(poff[c], poff[c + 1]) for c in perm]))
+        d_pcm = dev(_cat([pcm[c][t0:t0 + T] for c in range(n)], np.int16))
+        d_pcm_p = d_pcm[gather_p].contiguous()
+        outs = [torch.zeros(int(boff[-1]), dtype=torch.uint8, device="cuda") for _ in range(4)]
+        encs[0].encode_mixed_list(np.arange(n), d_pcm, outs[0], T, stream=st)
+        encs[1].encode_mixed_items([(c, T) for c in range(n)], d_pcm, outs[1], stream=st)
+        encs[2].encode_mixed_list(perm, d_pcm_p, outs[2], T, stream=st)
+        encs[3].encode_mixed_items([(c, T, 0) for c in perm], d_pcm_p, outs[3], stream=st)
+        torch.cuda.synchronize()
+        assert torch.equal(outs[1], outs[0]), "encode_mixed_items (in order) differs from encode_mixed_list (T = %d)" % T
+        assert torch.equal(outs[3], outs[2]), "encode_mixed_items (permuted) differs from encode_mixed_list (T = %d)" % T
+        flags = (rng.random((n, T)) < 0.03).astype(np.uint8)
+        pcms = [torch.zeros(int(poff[-1]), dtype=torch.int16, device="cuda") for _ in range(4)]
+        in_p = outs[0][gather_b].contiguous()
+        decs[0].decode_mixed_list(np.arange(n), outs[0], pcms[0], T, stream=st, d_bad_frame=dev(flags))
+        decs[1].decode_mixed_items([(c, T) for c in range(n)], outs[0], pcms[1], stream=st, d_bad_frame=dev(flags))
+        decs[2].decode_mixed_list(perm, in_p, pcms[2], T, stream=st, d_bad_frame=dev(flags[perm]))
+        decs[3].decode_mixed_items([(c, T, 0) for c in perm], in_p, pcms[3], stream=st, d_bad_frame=dev(flags[perm]))
+        torch.cuda.synchronize()
+        assert torch.equal(pcms[1], pcms[0]), "decode_mixed_items (in order) differs from decode_mixed_list (T = %d)" % T
+        assert torch.equal(pcms[3], pcms[2]), "decode_mixed_items (permuted) differs from decode_mixed_list (T = %d)" % T
+        t0 += T
+    assert decs[0].plc_events() == decs[1].plc_events() == decs[2].plc_events() == decs[3].plc_events() > 0
+    for h in encs + decs:
+        assert h.pair_timeouts() == 0
+    assert np.array_equal(encs[1].state_save(), encs[0].state_save()) and np.array_equal(encs[3].state_save(), encs[2].state_save())
+    assert np.array_equal(decs[1].state_save(), decs[0].state_save()) and np.array_equal(decs[3].state_save(), decs[2].state_save())
+
+
+def test_items_of_one_count_equal_the_mixed_list_call():
+    _items_vs_list(7, (1, 2, 5))
+
+
+def test_more_than_24_buckets():
+    """ten configurations x three sizes, one or two streams each, n_frames 1 and 2: more buckets than a launch's group table has rows"""
+    sv = ItemsServer(5, 8, seed=17, configs=MIXED[:10])  # channel c: configuration c % 10, stream c // 10
+    rng = np.random.default_rng(24)
+    for k in range(2):
+        items, keys = [], set()
+        for c in range(sv.n_ch):
+            cfg, i = c % 10, c // 10
+            nb = (0, 0, 24 + 3 * cfg, 24 + 3 * cfg, 300 - 7 * cfg)[i]  # streams 0, 1: the descriptor's; 2, 3: a small size; 4: a large one
+            T = 1 + ((i + cfg + k) % 2)
+            items.append((c, T, nb))
+            keys.add((cfg, sv.size(c, nb), T))
+        assert len(keys) > 24, len(keys)
+        sv.tick([items[i] for i in rng.permutation(len(items))], "tick %d" % k)
+        sv.reset_enc([3, 27])
+        sv.reset_dec([14, 41])
+    assert sv.enc.pair_timeouts() == 0 and sv.dec.pair_timeouts() == 0
+
+
+def test_untouched_means_untouched():
+    torch = torch_mod()
+    sv = ItemsServer(4, 14, seed=23)
+    sv.tick([(c, 2, 0) for c in range(sv.n_ch)], "warm-up")
+    rng = np.random.default_rng(77)
+    listed = [int(c) for c in rng.permutation(rng.choice(sv.n_ch, sv.n_ch // 2, replace=False))]
+    rest = [c for c in range(sv.n_ch) if c not in listed]
+    enc_rest = [sv.enc_index[c] for c in rest if sv.encodable[c]]
+    enc_before, dec_before = sv.enc.state_save(enc_rest), sv.dec.state_save(rest)
+    enc_listed_before = sv.enc.state_save([sv.enc_index[c] for c in listed if sv.encodable[c]])
+    sv.reset_enc(listed[:2])
+    sv.reset_dec(listed[1:3])
+    plc_rest = sum(sv.plc[c] for c in rest)
+    sv.tick([(c, 1 + i % 3, 0 if (i % 4 or not sv.encodable[c]) else 64) for i, c in enumerate(listed)], "half of the channels")
+    torch.cuda.synchronize()
+    assert np.array_equal(sv.enc.state_save(enc_rest), enc_before), "encoder channels that were not listed changed"
+    assert np.array_equal(sv.dec.state_save(rest), dec_before), "decoder channels that were not listed changed"
+    assert not np.array_equal(sv.enc.state_save([sv.enc_index[c] for c in listed if sv.encodable[c]]), enc_listed_before)
+    assert sum(sv.plc[c] for c in rest) == plc_rest and sv.dec.plc_events() == sum(sv.plc)
+
+
+def test_argument_errors_launch_nothing_and_advance_nothing():
+    torch = torch_mod()
+    L = pkg.load_library()
+    sv = ItemsServer(1, 10, seed=51, configs=MIXED[:10])  # ten channels, every one encodable: decoder index = encoder index
+    sv.tick([(5, 1, 0), (1, 2, 0), (6, 1, 0), (2, 1, 0)], "before")
+    sv.reset_enc([3])  # a pending reset that the refused calls must not consume
+    sv.reset_dec([3])
+    ok = [(3, 1, 0), (1, 2, 0), (2, 1, 64), (6, 1, 0)]
+    arr = lambda it: np.array([tuple(r) + (0,) * (4 - len(r)) for r in it], np.int32)
+    d_pcm = dev(_cat([sv.material[c][sv.cursor[c]:sv.cursor[c] + T] for c, T, _ in ok], np.int16))
+    d_out = torch.full((sum(T * sv.size(c, nb) for c, T, nb in ok),), 0xA5, dtype=torch.uint8, device="cuda")
+    d_pcm_out = torch.full((sum(T * sv.nf[c] for c, T, _ in ok),), 12345, dtype=torch.int16, device="cuda")
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    cp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    st = ctypes.c_void_p(cur_stream())
+    E = lambda it, n, a, b, h=None: L.lc3gpu_encode_mixed_items(h or sv.enc._h, it, n, a, b, st)
+    D = lambda it, n, a, b, h=None: L.lc3gpu_decode_mixed_items(h or sv.dec._h, it, n, a, None, b, st)
+
+    def with_(i, field, v):
+        a = arr(ok)
+        a[i, field] = v
+        return a
+
+    for side, (call, a, b) in enumerate(((E, p(d_pcm), p(d_out)), (D, p(d_out), p(d_pcm_out)))):
+        for bad in (with_(2, 0, 10), with_(1, 0, -1), with_(2, 0, 3)):  # out of range; a channel named twice
+            assert call(cp(bad), 4, a, b) == ECHANNEL
+        for bad in (with_(1, 1, 0), with_(3, 1, -2), with_(0, 2, 401), with_(0, 2, -5)):
+            assert call(cp(bad), 4, a, b) == ELENGTH
+        if side == 0:  # 1..19 bytes: the encoder refuses them, the decoder takes them (test_sizes_per_item_...: 1-byte frames)
+            assert call(cp(with_(0, 2, 19)), 4, a, b) == ELENGTH
+        assert call(cp(with_(3, 3, 1)), 4, a, b) == EINVAL  # reserved
+        assert call(None, 4, a, b) == EINVAL
+        assert call(cp(arr(ok)), 4, None, b) == EINVAL
+        assert call(cp(arr(ok)), 4, a, None) == EINVAL
+        assert call(cp(arr(ok)), -1, a, b) == EINVAL
+        assert call(cp(arr(ok)), 0, a, b) == 0  # no items: nothing launched
+    assert E(cp(arr(ok)), 4, ctypes.c_void_p(d_pcm.data_ptr() + 2), p(d_out)) == EINVAL  # misaligned PCM
+    assert D(cp(arr(ok)), 4, p(d_out), ctypes.c_void_p(d_pcm_out.data_ptr() + 2)) == EINVAL
+    uenc = pkg.Lc3Encoder(8, pkg.FrameDuration.TenMs, pkg.SamplingFrequency.Hz48000)
+    udec = pkg.Lc3Decoder(8, pkg.FrameDuration.TenMs, pkg.SamplingFrequency.Hz48000)
+    assert E(cp(arr(ok)), 4, p(d_pcm), p(d_out), h=uenc._h) == EINVAL  # uniform handles are refused
+    assert D(cp(arr(ok)), 4, p(d_out), p(d_pcm_out), h=udec._h) == EINVAL
+    with pytest.raises(pkg.Lc3EncoderError) as ei:
+        uenc.encode_mixed_items([(0, 1)], d_pcm, d_out)
+    assert ei.value.code == EINVAL
+    with pytest.raises(pkg.Lc3DecoderError) as ei:
+        udec.decode_mixed_items([(0, 1)], d_out, d_pcm_out)
+    assert ei.value.code == EINVAL
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()  # a bound handle takes the call on its bound stream only
+    torch.cuda.synchronize()
+    sv.enc.bind_stream(s1.cuda_stream)
+    sv.dec.bind_stream(s1.cuda_stream)
+    s2p = ctypes.c_void_p(s2.cuda_stream)
+    assert L.lc3gpu_encode_mixed_items(sv.enc._h, cp(arr(ok)), 4, p(d_pcm), p(d_out), s2p) == EINVAL
+    assert L.lc3gpu_decode_mixed_items(sv.dec._h, cp(arr(ok)), 4, p(d_out), None, p(d_pcm_out), s2p) == EINVAL
+    sv.enc.bind_stream(s1.cuda_stream, bind=False)
+    sv.dec.bind_stream(s1.cuda_stream, bind=False)
+    torch.cuda.synchronize()
+    assert bool((d_out == 0xA5).all()) and bool((d_pcm_out == 12345).all()), "a refused call wrote to its output"
+    # nothing was launched, advanced or reset: the next valid calls give the oracle's bytes, on channels the refused calls named too
+    sv.tick(ok + [(0, 3, 0)], "after the refused calls")
+    sv.tick([(c, 1 + c % 2, 0) for c in (9, 8, 7, 6, 5, 4, 3, 2, 1, 0)], "after the refused calls")
+
+
+_FORMS_CHILD = r"""
+import sys
+import numpy as np
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
+import test_gpu_items as m
+torch = m.torch_mod()
+sv = m.ItemsServer(2, 24, seed=3)
+rng = np.random.default_rng(8)
+for k in range(4):
+    if k:
+        sv.reset_enc([int(c) for c in rng.choice(sv.n_ch, 3, replace=False)])
+        sv.reset_dec([int(c) for c in rng.choice(sv.n_ch, 3, replace=False)])
+        for c in range(sv.n_ch):
+            if c not in sv.frames8k:
+                sv.queue[c] = []
+    chosen = [int(c) for c in rng.choice(sv.n_ch, int(rng.integers(1, sv.n_ch + 1)), replace=False)]
+    sv.tick([(c, int(rng.integers(1, 6)), 0 if (rng.random() < 0.6 or not sv.encodable[c]) else int(rng.integers(20, 401))) for c in chosen], "tick %d" % k)
+assert sv.dec.plc_events() == sum(sv.plc)
+# one tick large enough for the packer / parser forms of full batches, counts 1 and 2 mixed, against two mixed-list calls on twin handles:
+# every item for one frame, then the count-2 items for a second
+S = int(sys.argv[2]) // 10 + 1
+descs, pcm = m.ML._twin_setup(S, 2, 5, 48)
+n = len(descs)
+nf = [m.pkg.Lc3Config(d[0], d[1]).nf for d in descs]
+order = [int(c) for c in rng.permutation(n)]
+count = {c: 1 + int(rng.random() < 0.5) for c in order}
+two = [c for c in order if count[c] == 2]
+assert sum(count.values()) > int(sys.argv[2]) and two and len(two) < n
+st = m.cur_stream()
+enc_i, enc_l, dec_i, dec_l = m.pkg.Lc3Encoder.mixed(descs), m.pkg.Lc3Encoder.mixed(descs), m.pkg.Lc3Decoder.mixed(descs), m.pkg.Lc3Decoder.mixed(descs)
+items = [(c, count[c]) for c in order]
+out_i = torch.zeros(sum(count[c] * descs[c][2] for c in order), dtype=torch.uint8, device="cuda")
+enc_i.encode_mixed_items(items, m.dev(m._cat([pcm[c][:count[c]] for c in order], np.int16)), out_i, stream=st)
+out_1 = torch.zeros(sum(descs[c][2] for c in order), dtype=torch.uint8, device="cuda")
+out_2 = torch.zeros(sum(descs[c][2] for c in two), dtype=torch.uint8, device="cuda")
+enc_l.encode_mixed_list(order, m.dev(m._cat([pcm[c][:1] for c in order], np.int16)), out_1, 1, stream=st)
+enc_l.encode_mixed_list(two, m.dev(m._cat([pcm[c][1:2] for c in two], np.int16)), out_2, 1, stream=st)
+torch.cuda.synchronize()
+gi, g1, g2 = out_i.cpu().numpy(), out_1.cpu().numpy(), out_2.cpu().numpy()
+oi = o1 = o2 = 0
+for c in order:
+    nb = descs[c][2]
+    assert np.array_equal(gi[oi:oi + nb], g1[o1:o1 + nb]), ("encode, first frame", c)
+    oi += nb; o1 += nb
+    if count[c] == 2:
+        assert np.array_equal(gi[oi:oi + nb], g2[o2:o2 + nb]), ("encode, second frame", c)
+        oi += nb; o2 += nb
+flags = [(rng.random(count[c]) < 0.03).astype(np.uint8) for c in order]
+pcm_i = torch.zeros(sum(count[c] * nf[c] for c in order), dtype=torch.int16, device="cuda")
+dec_i.decode_mixed_items(items, out_i, pcm_i, stream=st, d_bad_frame=m.dev(m._cat(flags, np.uint8)))
+pcm_1 = torch.zeros(sum(nf[c] for c in order), dtype=torch.int16, device="cuda")
+pcm_2 = torch.zeros(sum(nf[c] for c in two), dtype=torch.int16, device="cuda")
+dec_l.decode_mixed_list(order, out_1, pcm_1, 1, stream=st, d_bad_frame=m.dev(np.array([f[0] for f in flags], np.uint8)))
+dec_l.decode_mixed_list(two, out_2, pcm_2, 1, stream=st, d_bad_frame=m.dev(np.array([f[1] for f, c in zip(flags, order) if count[c] == 2], np.uint8)))
+torch.cuda.synchronize()
+gi, g1, g2 = pcm_i.cpu().numpy(), pcm_1.cpu().numpy(), pcm_2.cpu().numpy()
+oi = o1 = o2 = 0
+for c in order:
+    assert np.array_equal(gi[oi:oi + nf[c]], g1[o1:o1 + nf[c]]), ("decode, first frame", c)
+    oi += nf[c]; o1 += nf[c]
+    if count[c] == 2:
+        assert np.array_equal(gi[oi:oi + nf[c]], g2[o2:o2 + nf[c]]), ("decode, second frame", c)
+        oi += nf[c]; o2 += nf[c]
+assert np.array_equal(enc_i.state_save(), enc_l.state_save()) and np.array_equal(dec_i.state_save(), dec_l.state_save())
+assert dec_i.plc_events() == dec_l.plc_events() > 0
+for h in (enc_i, dec_i):
+    assert h.pair_timeouts() == 0
+print("forms ok")
+"""
+
+
+def test_items_every_kernel_form_in_a_fresh_process():
+    """a short oracle-checked tick sequence and one tick above the full-batch threshold (counts 1 and 2 mixed) against two mixed-list calls
+    on twin handles, per kernel form, each child under its own time limit; stops at the first child that fails"""
+    threshold = ML._pc_threshold()
+    for env in ML.FORMS:
+        e = dict(os.environ)
+        e.update(env)
+        r = subprocess.run([sys.executable, "-c", _FORMS_CHILD, ROOT, str(threshold)], env=e, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0 and "forms ok" in r.stdout, (env, r.returncode, r.stdout[-1000:], r.stderr[-3000:])

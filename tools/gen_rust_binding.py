@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "lc3gpu.h")
 
 OPAQUE = {"lc3gpu_encoder": "Lc3GpuEncoder", "lc3gpu_decoder": "Lc3GpuDecoder", "lc3gpu_pipeline": "Lc3GpuPipeline",
-          "lc3gpu_stream_desc": "Lc3GpuStreamDesc", "lc3gpu_frame_info": "Lc3GpuFrameInfo"}
+          "lc3gpu_stream_desc": "Lc3GpuStreamDesc", "lc3gpu_frame_info": "Lc3GpuFrameInfo", "lc3gpu_item": "Lc3GpuItem"}
 SCALAR = {"int": "i32", "unsigned": "u32", "unsigned int": "u32", "float": "f32", "double": "f64", "size_t": "usize",
           "int16_t": "i16", "uint16_t": "u16", "uint8_t": "u8", "int32_t": "i32", "uint32_t": "u32", "int64_t": "i64", "uint64_t": "u64",
           "unsigned long long": "u64", "char": "c_char", "void": "c_void"}
@@ -198,6 +198,15 @@ impl Lc3EncoderGpu {
                                            hip_stream: *mut c_void) -> i32 {
         lc3gpu_encode_mixed_list(self.h, channels.as_ptr(), channels.len() as i32, d_pcm, d_out, n_frames as i32, hip_stream)
     }
+    /// A frame count and a frame size per listed stream of a mixed-configuration handle: the reference's caller calls `encode_frame` once
+    /// per (channel, frame) with a slice whose length selects the size (encoder/lc3_encoder.rs:175-191).
+    ///
+    /// # Safety
+    /// `d_pcm` / `d_out` must be device allocations laid out as include/lc3gpu.h states for lc3gpu_encode_mixed_items that outlive the
+    /// call's work; `items` is host memory and free again when the call returns.
+    pub unsafe fn encode_mixed_items_device(&mut self, items: &[Lc3GpuItem], d_pcm: *const i16, d_out: *mut u8, hip_stream: *mut c_void) -> i32 {
+        lc3gpu_encode_mixed_items(self.h, items.as_ptr(), items.len() as i32, d_pcm, d_out, hip_stream)
+    }
     /// a new `EncoderChannel` for each named channel (from its next call on; no wait); the others are untouched
     pub fn reset_channels(&mut self, channels: &[i32]) -> Result<(), i32> {
         let rc = unsafe { lc3gpu_encoder_reset_channels(self.h, channels.as_ptr(), channels.len() as i32) };
@@ -281,6 +290,15 @@ impl Lc3DecoderGpu {
                                            n_frames: usize, hip_stream: *mut c_void) -> i32 {
         lc3gpu_decode_mixed_list(self.h, channels.as_ptr(), channels.len() as i32, d_in, d_bad_frame, d_pcm, n_frames as i32, hip_stream)
     }
+    /// A frame count and a frame size per listed stream (decoder/lc3_decoder.rs:217-234 once per (channel, frame)).
+    ///
+    /// # Safety
+    /// device allocations laid out as include/lc3gpu.h states for lc3gpu_decode_mixed_items that outlive the call's work; `items` is host
+    /// memory and free again when the call returns.
+    pub unsafe fn decode_mixed_items_device(&mut self, items: &[Lc3GpuItem], d_in: *const u8, d_bad_frame: *const u8, d_pcm: *mut i16,
+                                            hip_stream: *mut c_void) -> i32 {
+        lc3gpu_decode_mixed_items(self.h, items.as_ptr(), items.len() as i32, d_in, d_bad_frame, d_pcm, hip_stream)
+    }
     /// a new `DecoderChannel` for each named channel (from its next call on; no wait; its PLC count goes to zero)
     pub fn reset_channels(&mut self, channels: &[i32]) -> Result<(), i32> {
         let rc = unsafe { lc3gpu_decoder_reset_channels(self.h, channels.as_ptr(), channels.len() as i32) };
@@ -355,11 +373,15 @@ def generate():
         "",
     ]
     for c, r in sorted(OPAQUE.items()):
-        if c in ("lc3gpu_stream_desc", "lc3gpu_frame_info"):
+        if c in ("lc3gpu_stream_desc", "lc3gpu_frame_info", "lc3gpu_item"):
             continue
         lines += ["#[repr(C)]", "pub struct %s {" % r, "    _private: [u8; 0],", "}"]
     lines += ["/// one stream of a mixed-configuration handle (lc3gpu_stream_desc)", "#[repr(C)]", "#[derive(Clone, Copy, Debug)]",
               "pub struct Lc3GpuStreamDesc {", "    pub fs_hz: i32,", "    pub frame_us: i32,", "    pub nbytes: i32,", "}"]
+    lines += ["/// one item of the *_mixed_items calls (lc3gpu_item, 16 bytes): a stream, its frames in this call and their size (0 = the",
+              "/// descriptor's)", "#[repr(C)]", "#[derive(Clone, Copy, Debug, Default)]", "pub struct Lc3GpuItem {", "    pub channel: i32,",
+              "    pub n_frames: i32,", "    pub nbytes: i32,", "    pub reserved: i32,", "}",
+              "const _: () = assert!(core::mem::size_of::<Lc3GpuItem>() == 16);"]
     lines += ["/// one frame's record of lc3gpu_inspect (lc3gpu_frame_info, 128 bytes): status LC3GPU_FRAME_*, the side information",
               "/// (decoder/side_info.rs:20-31) and the arithmetic data (decoder/arithmetic_codec.rs:99-107)", "#[repr(C)]",
               "#[derive(Clone, Copy, Debug, Default)]", "pub struct Lc3GpuFrameInfo {"]
