@@ -191,7 +191,8 @@ int lc3gpu_encode_mixed(lc3gpu_encoder *enc, const int16_t *d_pcm, uint8_t *d_ou
  * NOT provided by the mixed-list calls (out of scope): the interleaved layout, a frame size per frame (lc3gpu_*_vbr), the host-resident
  * calls (lc3gpu_*_host) and the pipeline object.  (n_frames holds for every item of a call and every stream is coded at its
  * descriptor's size; a frame count per listed channel and a frame size per call are what lc3gpu_encode_mixed_items /
- * lc3gpu_decode_mixed_items below provide.) */
+ * lc3gpu_decode_mixed_items below provide.)  The interleaved layout is what lc3gpu_encode_mixed_mc_items / lc3gpu_decode_mixed_mc_items
+ * provide. */
 int lc3gpu_encode_mixed_list(lc3gpu_encoder *enc, const int32_t *channels, int n_list, const int16_t *d_pcm, uint8_t *d_out, int n_frames,
                              void *hip_stream);
 /* Batch over a list of ITEMS of a mixed handle: a frame count and a frame size per listed stream.  The reference's caller calls
@@ -228,7 +229,7 @@ int lc3gpu_encode_mixed_list(lc3gpu_encoder *enc, const int32_t *channels, int n
  *   launches  the items are bucketed by (configuration, effective nbytes, n_frames); ONE launch per kernel per 24 buckets (a call with
  *             more buckets runs as consecutive launch sets on the same stream, with one upload and one host check for all of them)
  * NOT provided (out of scope): a size per FRAME within an item, the interleaved layout, the host-resident calls, the pipeline object,
- * uniform handles. */
+ * uniform handles.  The interleaved layout is what lc3gpu_encode_mixed_mc_items / lc3gpu_decode_mixed_mc_items below provide. */
 typedef struct lc3gpu_item {
     int32_t channel;  /* descriptor index of the mixed handle */
     int32_t n_frames; /* >= 1: frames of this stream in this call */
@@ -242,6 +243,61 @@ _Static_assert(sizeof(lc3gpu_item) == 16, "lc3gpu_item is 16 bytes");
 #endif
 int lc3gpu_encode_mixed_items(lc3gpu_encoder *enc, const lc3gpu_item *items, int n_items, const int16_t *d_pcm, uint8_t *d_out,
                               void *hip_stream);
+/* Batch over a list of MULTI-CHANNEL items of a mixed handle: WAV sample order in, frame order out.  A stereo or multi-channel stream's
+ * PCM arrives as L R L R and its frames leave as the channels' frames back to back -- the order the reference's file drivers read and
+ * write (examples/encode.rs:96-115, examples/decode.rs:93-118) and the order of a multi-channel LC3 SDU.  An mc item names the C
+ * descriptors of one such stream; the kernels read and write the interleaved buffers themselves, so a tick needs no de-interleave or
+ * multiplex pass around the call.  The contract of lc3gpu_encode_mixed_items (which see), with these differences:
+ *   items     HOST lc3gpu_mc_item[n_items], any order, no channel in two items; may be reused as soon as the call returns.  Item i:
+ *             descriptors `first_channel` .. `first_channel + n_channels - 1` are the stream's channels 0 .. C-1, `n_channels` 1..8,
+ *             `n_frames` >= 1 the frames of EVERY channel of the stream in this call, `nbytes` the frame size of every channel for this
+ *             call (0 = the descriptors', which must then be equal)
+ *   buffers   DEVICE, compact in list order, each item in the layout of LC3GPU_LAYOUT_INTERLEAVED.  With C_j, T_j, nf_j, nb_j the
+ *             channel count, frame count, frame length and effective frame size of item j:
+ *               d_pcm  item i at element sum_{j<i} T_j * nf_j * C_j,  int16[T_i][nf_i][C_i]
+ *               d_out  item i at byte    sum_{j<i} T_j * C_j * nb_j,  uint8[T_i][C_i][nb_i]
+ *               flags  (decoder) item i at sum_{j<i} T_j * C_j,       uint8[T_i][C_i]
+ *             nf is even, so a 4-byte aligned d_pcm base keeps every item's base 4-byte aligned; a single channel of an item with
+ *             C > 1 is only 2-byte aligned and is read and written with 16-bit accesses, as in lc3gpu_*_layout
+ *   checks    on the host before anything is queued; a refused call has launched nothing, written nothing, advanced no channel and
+ *             consumed no pending reset:
+ *               a channel range outside [0, n_streams), a channel
+ *               named by two items                                   LC3GPU_ECHANNEL
+ *               n_channels outside 1..8                              LC3GPU_EINVAL
+ *               channels of one item that differ in fs_hz or
+ *               frame_us (lc3_encoder.rs:117-124: one configuration) LC3GPU_EINVAL
+ *               nbytes == 0 while the item's descriptors differ in
+ *               nbytes (one num_bytes_per_channel)                   LC3GPU_ELENGTH
+ *               n_frames < 1                                         LC3GPU_ELENGTH
+ *               nbytes not 0 and outside 20..400 (encoder)           LC3GPU_ELENGTH
+ *               nbytes not 0 and outside 1..400 (decoder)            LC3GPU_ELENGTH
+ *               more than 2^31 - 1 channel-frames in one call        LC3GPU_ELENGTH
+ *               a null pointer, n_items < 0, misaligned PCM, a
+ *               UNIFORM handle, a bound handle on another stream     LC3GPU_EINVAL
+ *               n_items == 0                                         LC3GPU_OK (nothing launched)
+ *             LC3GPU_EPAIR and LC3GPU_EUNSUPPORTED as for lc3gpu_*_mixed_items
+ *   state     every channel of an item advances exactly as under an items call that lists it alone with the same n_frames and nbytes:
+ *             an mc call gives the bytes, the PCM and the per-channel blobs of lc3gpu_*_mixed_items on the de-interleaved buffers, and
+ *             the results of the items call itself when every n_channels is 1.  Channels not listed keep their blob and their PLC
+ *             count byte for byte; channels noted by lc3gpu_*_reset_channels start fresh inside the same launch
+ *   mixing    mc-items, items, mixed-list, lc3gpu_*_mixed and *_frame calls may alternate on a handle
+ *   launches  as for the items calls: the items' CHANNELS are bucketed by (configuration, effective nbytes, n_frames), ONE launch per
+ *             kernel per 24 buckets; the channel count is not part of the key
+ * NOT provided (out of scope): a size per frame, the host-resident calls, the pipeline object, uniform handles (their interleaved
+ * layout is lc3gpu_encode_layout / lc3gpu_decode_layout). */
+typedef struct lc3gpu_mc_item {
+    int32_t first_channel; /* descriptor index of the stream's channel 0 */
+    int32_t n_channels;    /* 1..8: descriptors first_channel .. first_channel + n_channels - 1 */
+    int32_t n_frames;      /* >= 1: frames of EVERY channel of the stream in this call */
+    int32_t nbytes;        /* frame size of every channel for this call; 0 = the descriptors' (then all equal) */
+} lc3gpu_mc_item;
+#ifdef __cplusplus
+static_assert(sizeof(lc3gpu_mc_item) == 16, "lc3gpu_mc_item is 16 bytes");
+#else
+_Static_assert(sizeof(lc3gpu_mc_item) == 16, "lc3gpu_mc_item is 16 bytes");
+#endif
+int lc3gpu_encode_mixed_mc_items(lc3gpu_encoder *enc, const lc3gpu_mc_item *items, int n_items, const int16_t *d_pcm, uint8_t *d_out,
+                                 void *hip_stream);
 
 /* per-channel state blobs (checkpoint / CPU cross-checks): size per channel, device->host copy, host->device.
  * nbytes must equal state_size * num_channels (LC3GPU_ELENGTH otherwise); both calls synchronise the device.  A channel's blob
@@ -362,6 +418,11 @@ int lc3gpu_decode_mixed_list(lc3gpu_decoder *dec, const int32_t *channels, int n
  * side information is concealed and counted, as everywhere). */
 int lc3gpu_decode_mixed_items(lc3gpu_decoder *dec, const lc3gpu_item *items, int n_items, const uint8_t *d_in, const uint8_t *d_bad_frame,
                               int16_t *d_pcm, void *hip_stream);
+/* Batch decode over a list of MULTI-CHANNEL items of a mixed handle: the contract of lc3gpu_encode_mixed_mc_items (which see) with d_in
+ * like that call's d_out (uint8[T][C][nbytes] per item), d_pcm like its d_pcm (int16[T][nf][C] per item), d_bad_frame uint8[T][C] per
+ * item or NULL, and frame sizes 1..400. */
+int lc3gpu_decode_mixed_mc_items(lc3gpu_decoder *dec, const lc3gpu_mc_item *items, int n_items, const uint8_t *d_in,
+                                 const uint8_t *d_bad_frame, int16_t *d_pcm, void *hip_stream);
 
 size_t lc3gpu_decoder_state_size(const lc3gpu_decoder *dec);
 int lc3gpu_decoder_state_save(lc3gpu_decoder *dec, void *host_dst, size_t nbytes);

@@ -85,6 +85,12 @@ public:
         int rc = lc3gpu_encode_mixed_items(h_, items.data(), (int)items.size(), d_pcm, d_out, hip_stream);
         if (rc) throw Error(rc, "encode_mixed_items");
     }
+    // mixed handle: multi-channel items (lc3gpu_mc_item: the C descriptors of one stream), PCM int16[T][nf][C], bytes uint8[T][C][nbytes]
+    // per item (lc3gpu_encode_mixed_mc_items)
+    void encode_mixed_mc_items(const std::vector<lc3gpu_mc_item> &items, const int16_t *d_pcm, uint8_t *d_out, void *hip_stream = nullptr) {
+        int rc = lc3gpu_encode_mixed_mc_items(h_, items.data(), (int)items.size(), d_pcm, d_out, hip_stream);
+        if (rc) throw Error(rc, "encode_mixed_mc_items");
+    }
     // back to the freshly constructed state from the next call on: every channel, or the named ones (a new EncoderChannel); no wait
     void reset() {
         int rc = lc3gpu_encoder_reset(h_);
@@ -175,6 +181,12 @@ public:
                             const uint8_t *d_bad_frame = nullptr) {
         int rc = lc3gpu_decode_mixed_items(h_, items.data(), (int)items.size(), d_in, d_bad_frame, d_pcm, hip_stream);
         if (rc) throw Error(rc, "decode_mixed_items");
+    }
+    // mixed handle: multi-channel items (see Encoder::encode_mixed_mc_items); d_bad_frame uint8[T][C] per item
+    void decode_mixed_mc_items(const std::vector<lc3gpu_mc_item> &items, const uint8_t *d_in, int16_t *d_pcm, void *hip_stream = nullptr,
+                               const uint8_t *d_bad_frame = nullptr) {
+        int rc = lc3gpu_decode_mixed_mc_items(h_, items.data(), (int)items.size(), d_in, d_bad_frame, d_pcm, hip_stream);
+        if (rc) throw Error(rc, "decode_mixed_mc_items");
     }
     // every channel, or the named ones (a new DecoderChannel; their PLC counts go to zero); no wait
     void reset() {

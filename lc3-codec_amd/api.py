@@ -254,6 +254,8 @@ def load_library():
     L.lc3gpu_decode_mixed_list.argtypes = [vp, vp, i, vp, vp, vp, i, vp]
     L.lc3gpu_encode_mixed_items.argtypes = [vp, vp, i, vp, vp, vp]
     L.lc3gpu_decode_mixed_items.argtypes = [vp, vp, i, vp, vp, vp, vp]
+    L.lc3gpu_encode_mixed_mc_items.argtypes = [vp, vp, i, vp, vp, vp]
+    L.lc3gpu_decode_mixed_mc_items.argtypes = [vp, vp, i, vp, vp, vp, vp]
     L.lc3gpu_encoder_reset_channels.argtypes = [vp, vp, i]
     L.lc3gpu_decoder_reset_channels.argtypes = [vp, vp, i]
     L.lc3gpu_encoder_state_save_channels.argtypes = [vp, vp, i, vp, ctypes.c_size_t]
@@ -346,6 +348,7 @@ ABI_SYMBOLS = [
     "lc3gpu_encoder_state_save_channels", "lc3gpu_encoder_state_load_channels", "lc3gpu_decoder_state_save_channels",
     "lc3gpu_decoder_state_load_channels", "lc3gpu_encode_mixed_list", "lc3gpu_decode_mixed_list",
     "lc3gpu_encode_mixed_items", "lc3gpu_decode_mixed_items",
+    "lc3gpu_encode_mixed_mc_items", "lc3gpu_decode_mixed_mc_items",
 ]
 
 # LC3GPU_SPEC_*: opt-in corrections of the reference's deviations from the LC3 specification (default 0 = reference behaviour)
@@ -491,6 +494,21 @@ def _item_list(items):
     for i, r in enumerate(rows):
         if not 2 <= len(r) <= 4:
             raise TypeError("an item is (channel, n_frames[, nbytes])")
+        for v in r:
+            if not isinstance(v, (int, np.integer)):
+                raise TypeError("item fields must be integers")
+        out[i, : len(r)] = r
+    return out
+
+
+def _mc_item_list(items):
+    """a sequence of (first_channel, n_channels, n_frames[, nbytes]) or an integer array [n][3..4] -> contiguous HOST int32[n][4], the
+    lc3gpu_mc_item array of the *_mixed_mc_items calls (nbytes 0 = the descriptors')"""
+    rows = [tuple(r) for r in items]
+    out = np.zeros((len(rows), 4), np.int32)
+    for i, r in enumerate(rows):
+        if not 3 <= len(r) <= 4:
+            raise TypeError("an mc item is (first_channel, n_channels, n_frames[, nbytes])")
         for v in r:
             if not isinstance(v, (int, np.integer)):
                 raise TypeError("item fields must be integers")
@@ -649,6 +667,17 @@ class Lc3Encoder:
         rc = self._L.lc3gpu_encode_mixed_items(self._h, _ptr(it), int(it.shape[0]), _ptr(d_pcm), _ptr(d_out), _ptr(stream))
         if rc:
             raise Lc3EncoderError(rc, "encode_mixed_items")
+
+    def encode_mixed_mc_items(self, items, d_pcm, d_out, stream=None):
+        """a mixed handle's batch over multi-channel items `(first_channel, n_channels, n_frames[, nbytes])` (HOST; descriptors
+        first_channel .. first_channel + n_channels - 1 are one stream's channels, 1..8 of one configuration): WAV sample order in,
+        frame order out.  DEVICE buffers compact in list order, item i's PCM int16[T_i][nf_i][C_i] at element sum T_j * nf_j * C_j, its
+        bytes uint8[T_i][C_i][nbytes_i] at byte sum T_j * C_j * nbytes_j.  Every channel advances as under encode_mixed_items; launches
+        as there; asynchronous on `stream` (lc3gpu_encode_mixed_mc_items)"""
+        it = _mc_item_list(items)
+        rc = self._L.lc3gpu_encode_mixed_mc_items(self._h, _ptr(it), int(it.shape[0]), _ptr(d_pcm), _ptr(d_out), _ptr(stream))
+        if rc:
+            raise Lc3EncoderError(rc, "encode_mixed_mc_items")
 
     def reset(self, channels=None):
         """every channel (channels=None) or the named ones back to the freshly constructed state from their next call on; no wait"""
@@ -892,6 +921,15 @@ class Lc3Decoder:
         rc = self._L.lc3gpu_decode_mixed_items(self._h, _ptr(it), int(it.shape[0]), _ptr(d_in), _ptr(d_bad_frame), _ptr(d_pcm), _ptr(stream))
         if rc:
             raise Lc3DecoderError(rc, "decode_mixed_items")
+
+    def decode_mixed_mc_items(self, items, d_in, d_pcm, stream=None, d_bad_frame=None):
+        """a mixed handle's batch over multi-channel items `(first_channel, n_channels, n_frames[, nbytes])`, as
+        Lc3Encoder.encode_mixed_mc_items: d_in like its d_out, d_pcm int16[T][nf][C] per item, d_bad_frame uint8[T][C] per item; frame
+        sizes 1..400 (lc3gpu_decode_mixed_mc_items)"""
+        it = _mc_item_list(items)
+        rc = self._L.lc3gpu_decode_mixed_mc_items(self._h, _ptr(it), int(it.shape[0]), _ptr(d_in), _ptr(d_bad_frame), _ptr(d_pcm), _ptr(stream))
+        if rc:
+            raise Lc3DecoderError(rc, "decode_mixed_mc_items")
 
     def reset(self, channels=None):
         """every channel (channels=None) or the named ones back to the freshly constructed state (PLC count 0) from their next call on; no wait"""

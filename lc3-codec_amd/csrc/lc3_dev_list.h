@@ -87,4 +87,52 @@ __device__ __forceinline__ void lc3_list_synth_stream(LC3_CFG_PARAM, lc3_dec_lds
     if (valid) lc3_dec_state_store(c, L, lane, gst);
 }
 
+// ---- a stream that is one channel of C in WAV sample order (lc3gpu_*_mixed_mc_items) -----------------------------------------------------
+// pcm_s = the channel's first sample; sample n of frame t is pcm_s[(t * nf + n) * stride], stride = C, the item's channel count, per-
+// stream data read with the list entry.  stride == 1 is the planar stream above, on its 32-bit loads and stores; stride >= 2 takes the
+// 16-bit path of lc3_enc_mdct / lc3_enc_state_store / lc3_dec_store_strided (a channel of several is 2-byte aligned only).
+// Barrier rule: the four streams of a workgroup may differ in stride.  The stride selects between two load (store) sequences inside
+// lc3_enc_mdct, lc3_enc_state_store and lc3_decode_frame_wave, none of which holds a workgroup barrier, and is otherwise an address
+// factor: no gathered block, no table staging and no prologue hook depends on it.
+LC3_CFG_TEMPLATE __device__ __forceinline__ void lc3_list_front_stream_mc(LC3_CFG_PARAM, lc3_enc_lds &L, int lane, lc3_enc_state *gst, int fresh,
+                                                                         int valid, const int16_t *pcm_s, int stride, float *mid, int32_t *planes,
+                                                                         size_t fbase, int nbytes, int n_frames, int spec_flags,
+                                                                         int outline_ltpf) {
+    LC3_CFG_BIND;
+    const int nf = c.nf, z = c.z;
+    if (lane == 0) L.spec_flags = spec_flags;
+    if (LC3_UNIFORM_I32(fresh)) lc3_enc_state_init(L, lane, gst, valid);  // (wave-level fences only: see the barrier rule)
+    else lc3_enc_state_load(L, lane, gst);
+    for (int t = 0; t < n_frames; t++) {
+        const size_t f = fbase + (size_t)t;
+        int32_t *plane = valid ? LC3_PLANE_COL(planes, f, EP_WORDS) : nullptr;
+        float *mcol = valid ? mid + f * (size_t)MP_WORDS : nullptr;
+        const int16_t *frame = pcm_s + (size_t)t * (size_t)nf * (size_t)stride;
+        // the history inside the call is the previous frame's tail at the channel's stride; the state blob's copy is planar
+        const int16_t *hist = t > 0 ? frame - (size_t)(nf - z) * (size_t)stride : (fresh ? nullptr : gst->hist);
+        lc3_encode_front_wave(LC3_CFG_PASS, L, lane, frame, hist, gst, mcol, plane, LC3_PLANE_STRIDE, nbytes, nullptr, stride, t > 0 ? stride : 1,
+                              (t % LC3_WG_WAVES) + (t + 2 < n_frames ? 0x100 : 0), outline_ltpf);
+    }
+    if (valid)
+        lc3_enc_state_store(c, L, lane, gst, n_frames > 0 ? pcm_s + (size_t)(n_frames - 1) * (size_t)nf * (size_t)stride : nullptr, stride);
+}
+
+LC3_CFG_TEMPLATE_AND(class TABLES = lc3_no_prologue)
+__device__ __forceinline__ void lc3_list_synth_stream_mc(LC3_CFG_PARAM, lc3_dec_lds &L, int lane, lc3_dec_state *gst, int fresh, int valid,
+                                                         int nbytes, const int32_t *planes, size_t fbase, int n_frames, int16_t *pcm_s, int stride,
+                                                         int late, TABLES tables = TABLES()) {
+    LC3_CFG_BIND;
+    lc3_i4 st_regs = {0, 0, 0, 0};
+    if (!LC3_UNIFORM_I32(fresh)) st_regs = lc3_dec_state_issue(lane, gst);
+    lc3_decode_stream_wave(LC3_CFG_PASS, L, lane, nbytes, planes, fbase, n_frames, gst, valid, pcm_s, (size_t)c.nf * (size_t)stride, stride, late,
+                           nullptr, 0,
+                           [&]() {
+                               tables();
+                               if (LC3_UNIFORM_I32(fresh)) lc3_dec_state_init(L, lane, gst, valid);  // (see the ring rule)
+                               else lc3_dec_state_commit(L, lane, st_regs);
+                           },
+                           fresh);
+    if (valid) lc3_dec_state_store(c, L, lane, gst);
+}
+
 #endif  // LC3_DEV_LIST_H_

@@ -23,7 +23,7 @@
 // at element T * tab[i].pcm_off1, its bytes at T * tab[i].byte_off1, its flags at tab[i].flag_idx * T
 struct lc3_stream_io {
     long long pcm_off1, byte_off1;  // per frame of the batch: sum of nf / of nbytes over the caller's earlier streams
-    int flag_idx, pad;              // the stream's index in the caller's order
+    int flag_idx, pad;              // the stream's index in the caller's order; pad: 0 (an mc-items call: the sample stride, lc3_mcitems_build)
 };
 #define LC3_MAX_GROUPS 24
 struct lc3_group {
@@ -131,6 +131,8 @@ struct lc3_mitems_bucket {
 struct lc3_mitems_plan {
     std::vector<lc3_mitems_bucket> buckets;  // in launch order
     std::vector<int> cell, bucket_of;        // scratch: head bucket per (slot, nbytes); bucket per item
+    std::vector<lc3_mitem> flat;             // scratch of lc3_mcitems_build: the items' channels as items of one channel each,
+    std::vector<int> pos_of;                 // and their launch positions (kept here so that a tick allocates nothing once they have grown)
     int n_items = 0, max_frames = 0;         // max_frames: the largest per-item count
     long long frames = 0;                    // of the whole call
 };
@@ -138,8 +140,9 @@ struct lc3_mitems_plan {
 #define LC3_MITEMS_MAX_NBYTES 400
 
 // items: already checked (channel in range and not twice, n_frames >= 1, nbytes 0 or in range).  fresh: per INTERNAL index.
+// pos_of: when given, item i's launch position.
 static inline void lc3_mitems_build(const lc3_mlist_group *groups, const lc3_mlist_stream *streams, const uint8_t *fresh, const lc3_mitem *items,
-                                    int n_items, int32_t *entries, lc3_stream_io *tab, lc3_mitems_plan &P) {
+                                    int n_items, int32_t *entries, lc3_stream_io *tab, lc3_mitems_plan &P, int *pos_of = nullptr) {
     P.buckets.clear();
     P.cell.assign((size_t)LC3_MITEMS_SLOTS * (LC3_MITEMS_MAX_NBYTES + 1), -1);
     P.bucket_of.resize((size_t)n_items);
@@ -195,9 +198,61 @@ static inline void lc3_mitems_build(const lc3_mlist_group *groups, const lc3_mli
         tab[p].byte_off1 = bo;
         tab[p].flag_idx = (int)fo;
         tab[p].pad = 0;
+        if (pos_of) pos_of[i] = p;  // (lc3_mcitems_build: the item's launch position)
         po += (long long)b.n_frames * (long long)groups[b.group].nf;
         bo += (long long)b.n_frames * (long long)b.nbytes;
         fo += b.n_frames;
+    }
+}
+
+// ---- items of several channels in WAV sample order (lc3gpu_encode_mixed_mc_items / lc3gpu_decode_mixed_mc_items) ------------------------
+// An mc item names C consecutive descriptors -- one stream's channels -- with one frame count and one frame size for all of them; its PCM
+// is int16[T][nf][C] (L R L R), its bytes uint8[T][C][nbytes], its flags uint8[T][C], the items compact in list order.  The plan expands
+// every item into its C channels and buckets THOSE exactly as lc3_mitems_build does (the channel count is no part of the key: a workgroup
+// may hold channels of items with C = 1, 2 and 3 side by side).  Channel c of an item whose running bases are po, bo, fo gets
+//   tab[pos] = { pcm_off1 = po + c, byte_off1 = bo + c * nbytes, flag_idx = fo + c, pad = C }
+// -- absolute, as an items call's -- and pad, 0 in every other call's table, carries the sample stride: frame t of the channel has its
+// samples at pcm_off1 + (t * nf + n) * C, its bytes at byte_off1 + t * C * nbytes, its flag at flag_idx + t * C.  Buckets, launch sets and
+// rows (lc3_mitems_rows) are those of an items call over the expanded list.
+struct lc3_mcitem {  // = lc3gpu_mc_item (include/lc3gpu.h)
+    int32_t first_channel, n_channels, n_frames, nbytes;
+};
+#define LC3_MCITEMS_MAX_CHANNELS 8
+// the expanded list's length
+static inline size_t lc3_mcitems_channels(const lc3_mcitem *items, int n_items) {
+    size_t n = 0;
+    for (int i = 0; i < n_items; i++) n += (size_t)items[i].n_channels;
+    return n;
+}
+// items: already checked (channel ranges inside the handle and disjoint, n_channels 1..8, one configuration per item, n_frames >= 1, nbytes
+// in range or 0 with equal descriptors).  entries / tab: one per CHANNEL (lc3_mcitems_channels).  fresh: per INTERNAL index.
+static inline void lc3_mcitems_build(const lc3_mlist_group *groups, const lc3_mlist_stream *streams, const uint8_t *fresh, const lc3_mcitem *items,
+                                     int n_items, int32_t *entries, lc3_stream_io *tab, lc3_mitems_plan &P) {
+    std::vector<lc3_mitem> &flat = P.flat;
+    flat.clear();
+    for (int i = 0; i < n_items; i++)
+        for (int c = 0; c < items[i].n_channels; c++) flat.push_back({items[i].first_channel + c, items[i].n_frames, items[i].nbytes, 0});
+    // buckets and launch positions are the items plan's over the expanded list; its offsets are replaced below
+    std::vector<int> &pos_of = P.pos_of;
+    pos_of.resize(flat.size());
+    lc3_mitems_build(groups, streams, fresh, flat.data(), (int)flat.size(), entries, tab, P, pos_of.data());
+    long long po = 0, bo = 0, fo = 0;
+    size_t k = 0;
+    for (int i = 0; i < n_items; i++) {
+        const int C = items[i].n_channels, T = items[i].n_frames;
+        int nb = 0, nf = 0;
+        for (int c = 0; c < C; c++, k++) {
+            const int p = pos_of[k], gi = streams[flat[k].channel].group;
+            nb = flat[k].nbytes ? flat[k].nbytes : groups[gi].nbytes;  // (equal over the item's channels: checked)
+            nf = groups[gi].nf;
+            tab[p].pcm_off1 = po + c;
+            tab[p].byte_off1 = bo + (long long)c * (long long)nb;
+            tab[p].flag_idx = (int)(fo + c);
+            tab[p].pad = C;
+        }
+        po += (long long)T * (long long)nf * (long long)C;
+        bo += (long long)T * (long long)C * (long long)nb;
+        fo += (long long)T * (long long)C;
     }
 }
 

@@ -78,6 +78,8 @@
 // twins live in the main unit only -- with the back half (1), both synthesis forms in unit 4 beside the list synthesis twins, for the reason
 // given there ("Where the kernels live")
 #define LC3_IN_ITEMS_TU(k) LC3_IN_MIXED_LIST_TU(k)
+// the seven mc twins (lc3gpu_*_mixed_mc_items: front half, packers, parsers, synthesis forms), each beside the items kernel it is a twin of
+#define LC3_IN_MC_ITEMS_TU(k) LC3_IN_MIXED_LIST_TU(k)
 #define LC3_CAT_(a, b) a##b
 #define LC3_CAT(a, b) LC3_CAT_(a, b)
 
@@ -592,6 +594,26 @@ __device__ __forceinline__ size_t lc3_io_flag_idx(const lc3_io &io, int first, s
     return s * (size_t)T + t;
 }
 
+// The lane-per-frame bodies' compile-time IOABS switch: 0 = the table's offsets count per frame of the launch (times T), 1 = absolute (an
+// items call), 2 = absolute with the stream's channel count C in the row's spare word (an mc-items call): frame t of the stream has its
+// bytes at byte_off1 + t * C * nbytes and its flag at flag_idx + t * C
+template <int IOABS>
+__device__ __forceinline__ size_t lc3_io_byte_off_abs(const lc3_io &io, int nbytes, int first, size_t s, size_t t, int T) {
+    if (IOABS == 2) {
+        const lc3_stream_io &r = io.tab[(size_t)first + s];
+        return (size_t)r.byte_off1 + t * (size_t)r.pad * (size_t)nbytes;
+    }
+    return lc3_io_byte_off(io, nbytes, first, s, t, IOABS ? 1 : T);
+}
+template <int IOABS>
+__device__ __forceinline__ size_t lc3_io_flag_idx_abs(const lc3_io &io, int first, size_t s, size_t t, int T) {
+    if (IOABS == 2) {
+        const lc3_stream_io &r = io.tab[(size_t)first + s];
+        return (size_t)r.flag_idx + t * (size_t)r.pad;
+    }
+    return lc3_io_flag_idx(io, first, s, t, IOABS ? 1 : T);
+}
+
 // runs BODY<view>(slot{g.slot}, args...) with the group's configuration view (a mixed batch is BASELINE config 4's whole point: its
 // 48 kHz / 7.5 ms, 32 kHz and 16 kHz groups get the compile-time views the uniform handles of those configurations get)
 #define LC3_GROUP_VIEW(BODY, g, ...)                                                         \
@@ -795,6 +817,50 @@ __global__ __launch_bounds__(64 * LC3_WG_WAVES, LC3_FRONT_WAVES) void LC3_MIXED_
 #endif
 #if LC3_MULTI_TU && LC3_TU_KIND == 0
 __global__ __launch_bounds__(64 * LC3_WG_WAVES, LC3_FRONT_WAVES) void lc3_enc_front_items_kernel_all(
+    lc3_groups G, lc3_enc_state *states, const int32_t *entries, const int16_t *pcm, float *mid, int32_t *planes, lc3_io io, int spec_flags);
+#endif
+
+// ---- mc items: a listed stream is one channel of C in WAV sample order (lc3gpu_*_mixed_mc_items; lc3_mcitems_build) -----------------------
+// Twins of the items kernels that touch PCM, frame bytes or flags -- front half, both packers, both parsers, both synthesis forms; the
+// vector quantiser, the back half, the wave-per-frame reconstruction and the TNS kernel see plane columns only and are the items call's.
+// The table row of launch position p holds the channel's first sample / first frame / first flag and, in its spare word, the stream's
+// channel count C: samples C elements apart, frames C * nf elements, C * nbytes bytes and C flags apart.  C is per-stream data, read as
+// the list entry is (a scalar load through the constant address space, bound by v_readfirstlane); the four streams of a workgroup may have
+// C = 1, 2 and 3 side by side.  Barrier rule: C picks the load / store sequence of a stream's PCM and is an address factor, nothing else
+// (lc3_dev_list.h); rows, buckets and frame counts -- what the workgroup barriers depend on -- are the items call's.
+template <class CV>
+__device__ __forceinline__ void lc3_enc_front_body_mc_items(lc3_cfg_slot<CV> cfg, unsigned wg, lc3_enc_state *states, const int32_t *entries,
+                                                            int first_pos, int n_streams, const int16_t *pcm, float *mid, int32_t *planes,
+                                                            int nbytes, int n_frames, const lc3_stream_io *tab, int spec_flags) {
+    const int lane = threadIdx.x & 63, wave = LC3_WAVE_ID();
+    lc3_enc_lds &L = lc3_enc_wg[wave];
+    const int s_raw = (int)wg * LC3_WG_WAVES + wave;
+    const int valid = s_raw < n_streams;
+    const int s = valid ? s_raw : n_streams - 1;  // (a shadow wave stays inside its own row)
+    typename CV::bind_t c0 = CV::bind(lc3_cfg_table[cfg.id]);
+    const int entry = lc3_list_entry(entries, first_pos + s);
+    lc3_enc_state *gst = states + (size_t)lc3_list_channel(entry);
+    const int16_t *pcm_s = pcm + (size_t)lc3_mlist_off(&tab[first_pos + s].pcm_off1);
+    const int stride = lc3_list_entry(&tab[first_pos + s].pad, 0);
+#ifndef LC3_TABLES_IN_GLOBAL
+    lc3_front_tables_stage_image(c0.stage_image);
+    lc3_fft_tables_stage_image(c0.stage_image);  // ends with the workgroup barrier
+#endif
+    lc3_list_front_stream_mc(cfg, L, lane, gst, lc3_list_fresh(entry), valid, pcm_s, stride, mid, planes, (size_t)s * (size_t)n_frames, nbytes,
+                             n_frames, spec_flags, 1);
+}
+#if LC3_IN_MC_ITEMS_TU(0)
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, LC3_FRONT_WAVES) void LC3_MIXED_KERNEL(lc3_enc_front_mc_items_kernel)(
+    lc3_groups G, lc3_enc_state *states, const int32_t *entries, const int16_t *pcm, float *mid, int32_t *planes, lc3_io io, int spec_flags) {
+    const lc3_group &g = G.g[lc3_find_group(G, blockIdx.x, 0)];
+    float *m = mid + (size_t)g.frame_base * (size_t)MP_WORDS;
+    int32_t *p = planes + (size_t)g.frame_base * (size_t)EP_WORDS;
+    LC3_GROUP_VIEW_LIST(lc3_enc_front_body_mc_items, g, blockIdx.x - g.wg_stream, states, entries, g.first_stream, g.n_streams, pcm, m, p, g.nbytes,
+                        g.n_frames, io.tab, spec_flags);
+}
+#endif
+#if LC3_MULTI_TU && LC3_TU_KIND == 0
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, LC3_FRONT_WAVES) void lc3_enc_front_mc_items_kernel_all(
     lc3_groups G, lc3_enc_state *states, const int32_t *entries, const int16_t *pcm, float *mid, int32_t *planes, lc3_io io, int spec_flags);
 #endif
 
@@ -1012,7 +1078,7 @@ __device__ __forceinline__ void lc3_pack_body(unsigned wg, int ne, const int32_t
     if (io.ilv || io.tab) {  // frame f = s * T + t has its own place: one frame after the other, its bytes spread over the threads
         for (int j = 0; j < nfr; j++) {
             const size_t fj = f0 + (size_t)j, s = fj / (size_t)T, t = fj - s * (size_t)T;
-            uint8_t *d = out + lc3_io_byte_off(io, nbytes, first_channel, s, t, IOABS ? 1 : T);
+            uint8_t *d = out + lc3_io_byte_off_abs<IOABS>(io, nbytes, first_channel, s, t, T);
             for (int b = tid; b < nbytes; b += fpb) d[b] = s_bytes[j * nbytes + b];
         }
     } else {
@@ -1059,6 +1125,17 @@ __global__ __launch_bounds__(256) void LC3_MIXED_KERNEL(lc3_pack_items_kernel)(l
 #endif
 #if LC3_MULTI_TU && LC3_TU_KIND == 0
 __global__ __launch_bounds__(256) void lc3_pack_items_kernel_all(lc3_groups G, const int32_t *planes, uint8_t *out, lc3_io io);
+#endif
+// ... of an mc-items call: frame (s, t) goes to byte_off1 + t * C * nbytes (IOABS 2; see lc3_enc_front_mc_items_kernel)
+#if LC3_IN_MC_ITEMS_TU(1)
+__global__ __launch_bounds__(256) void LC3_MIXED_KERNEL(lc3_pack_mc_items_kernel)(lc3_groups G, const int32_t *planes, uint8_t *out, lc3_io io) {
+    const lc3_group &g = G.g[lc3_find_group(G, blockIdx.x, 1)];
+    lc3_pack_body<2>(blockIdx.x - g.wg_frame, g.ne, planes + (size_t)g.frame_base * (size_t)EP_WORDS, out, g.nbytes, g.n_streams * g.n_frames,
+                     g.n_frames, g.first_stream, io);
+}
+#endif
+#if LC3_MULTI_TU && LC3_TU_KIND == 0
+__global__ __launch_bounds__(256) void lc3_pack_mc_items_kernel_all(lc3_groups G, const int32_t *planes, uint8_t *out, lc3_io io);
 #endif
 
 // ---- a frame size per frame (lc3gpu_encode_vbr; lc3_dev_enc_vbr.h) ----------------------------------------------------------------------
@@ -1319,7 +1396,7 @@ __device__ __forceinline__ void lc3_pack_pc_body(unsigned wg, int ne, const int3
     if (io.ilv || io.tab) {  // frame f = s * T + t has its own place: one frame after the other, its bytes spread over the threads
         for (int j = 0; j < nfr; j++) {
             const size_t fj = f0 + (size_t)j, s = fj / (size_t)T, t = fj - s * (size_t)T;
-            uint8_t *d = out + lc3_io_byte_off(io, nbytes, first_channel, s, t, IOABS ? 1 : T);
+            uint8_t *d = out + lc3_io_byte_off_abs<IOABS>(io, nbytes, first_channel, s, t, T);
             for (int b = tid; b < nbytes; b += nt) d[b] = s_bytes[j * nbytes + b];
         }
     } else {
@@ -1360,6 +1437,18 @@ __global__ __launch_bounds__(512) void LC3_MIXED_KERNEL(lc3_pack_pc_items_kernel
 #if LC3_MULTI_TU && LC3_TU_KIND == 0
 __global__ __launch_bounds__(512) void lc3_pack_pc_items_kernel_all(lc3_groups G, const int32_t *planes, uint8_t *out, lc3_io io,
                                                                     unsigned *pc_timeouts);
+#endif
+#if LC3_IN_MC_ITEMS_TU(1)
+__global__ __launch_bounds__(512) void LC3_MIXED_KERNEL(lc3_pack_pc_mc_items_kernel)(lc3_groups G, const int32_t *planes, uint8_t *out, lc3_io io,
+                                                                                     unsigned *pc_timeouts) {
+    const lc3_group &g = G.g[lc3_find_group(G, blockIdx.x, 1)];
+    lc3_pack_pc_body<2>(blockIdx.x - g.wg_frame, g.ne, planes + (size_t)g.frame_base * (size_t)EP_WORDS, out, g.nbytes, g.n_streams * g.n_frames,
+                        g.n_frames, g.first_stream, io, pc_timeouts);
+}
+#endif
+#if LC3_MULTI_TU && LC3_TU_KIND == 0
+__global__ __launch_bounds__(512) void lc3_pack_pc_mc_items_kernel_all(lc3_groups G, const int32_t *planes, uint8_t *out, lc3_io io,
+                                                                       unsigned *pc_timeouts);
 #endif
 
 // The packer's symbols as a stage of its own (lc3_enc_symbols_frame, lc3_dev_enc.h): one WAVE per frame.  A workgroup stages the
@@ -1417,7 +1506,7 @@ __device__ __forceinline__ void lc3_parse_body(lc3_cfg_slot<CV> cfg, unsigned wg
         if (io.ilv || io.tab) {  // frame f = s * T + t is fetched from its own place (examples/decode.rs:86-92 for the file order)
             for (int j = 0; j < nfr; j++) {
                 const size_t fj = f0 + (size_t)j, s = fj / (size_t)T, t = fj - s * (size_t)T;
-                const uint8_t *q = in + lc3_io_byte_off(io, nbytes, first_channel, s, t, IOABS ? 1 : T);
+                const uint8_t *q = in + lc3_io_byte_off_abs<IOABS>(io, nbytes, first_channel, s, t, T);
                 for (int b = tid; b < nbytes; b += fpb) s_bytes[j * nbytes + b] = q[b];
             }
         } else if ((((uintptr_t)src) & 3u) == 0) {
@@ -1447,7 +1536,7 @@ __device__ __forceinline__ void lc3_parse_body(lc3_cfg_slot<CV> cfg, unsigned wg
         for (int i = 0; i < 8; i++) c.pt[i] = 0;
         c.plast = clock64();
 #endif
-        const size_t fb = lc3_io_flag_idx(io, first_channel, f / (size_t)T, f % (size_t)T, IOABS ? 1 : T);  // the flag array follows the frame layout
+        const size_t fb = lc3_io_flag_idx_abs<IOABS>(io, first_channel, f / (size_t)T, f % (size_t)T, T);  // the flag array follows the frame layout
         int rc;
         if (late == 2) rc = (bad && bad[fb]) ? -100 : lc3_parse_frame<0>(c, ne, fs_ind, n_ms_10);  // (late is launch-uniform)
         else rc = (bad && bad[fb]) ? -100 : lc3_parse_frame<1>(c, ne, fs_ind, n_ms_10);
@@ -1526,6 +1615,29 @@ __global__ __launch_bounds__(256) void LC3_MIXED_KERNEL(lc3_parse_items_kernel)(
 __global__ __launch_bounds__(256) void lc3_parse_items_kernel_all(lc3_groups G, const uint8_t *in, const uint8_t *bad, int32_t *planes, lc3_io io,
                                                                   int late);
 #endif
+// ... of an mc-items call: frame (s, t) comes from byte_off1 + t * C * nbytes, its flag from flag_idx + t * C (IOABS 2).  The switch names
+// the body itself, as in lc3_parse_items_kernel
+#if LC3_IN_MC_ITEMS_TU(2)
+__global__ __launch_bounds__(256) void LC3_MIXED_KERNEL(lc3_parse_mc_items_kernel)(lc3_groups G, const uint8_t *in, const uint8_t *bad, int32_t *planes,
+                                                                                   lc3_io io, int late) {
+    const lc3_group &g = G.g[lc3_find_group(G, blockIdx.x, 1)];
+    int32_t *p = planes + (size_t)g.frame_base * (size_t)LC3_PLANE_WORDS;
+    const int T = LC3_UNIFORM_I32(g.n_frames), nfr = LC3_UNIFORM_I32(g.n_streams) * T;  // (the row's words are workgroup-uniform)
+    switch (g.fixed) {
+#define LC3_X(i, V) \
+    case i: lc3_parse_body<V, 2>(lc3_cfg_slot<V>{g.slot}, blockIdx.x - g.wg_frame, in, bad, p, g.nbytes, nfr, T, g.first_stream, io, late); break;
+        LC3_FOR_EACH_VIEW(LC3_X)
+#undef LC3_X
+    default:
+        lc3_parse_body<lc3_cfg_any, 2>(lc3_cfg_slot<lc3_cfg_any>{g.slot}, blockIdx.x - g.wg_frame, in, bad, p, g.nbytes, nfr, T, g.first_stream, io, late);
+        break;
+    }
+}
+#endif
+#if LC3_MULTI_TU && LC3_TU_KIND == 0
+__global__ __launch_bounds__(256) void lc3_parse_mc_items_kernel_all(lc3_groups G, const uint8_t *in, const uint8_t *bad, int32_t *planes, lc3_io io,
+                                                                     int late);
+#endif
 
 // The parser of a full batch as PRODUCER / CONSUMER wave pairs (lc3_pc_produce / lc3_pc_consume, lc3_dev_dec_parse.h): a workgroup of
 // 2 x fpb threads parses fpb frames; wave w of its first half runs the range decoder's recurrence for 64 frames, wave w of the second half
@@ -1578,7 +1690,7 @@ __device__ __forceinline__ void lc3_parse_pc_body(lc3_cfg_slot<CV> cfg, unsigned
         if (io.ilv || io.tab) {  // frame f = s * T + t is fetched from its own place (examples/decode.rs:86-92 for the file order)
             for (int j = 0; j < nfr; j++) {
                 const size_t fj = f0 + (size_t)j, s = fj / (size_t)T, t = fj - s * (size_t)T;
-                const uint8_t *q = in + lc3_io_byte_off(io, nbytes, first_channel, s, t, IOABS ? 1 : T);
+                const uint8_t *q = in + lc3_io_byte_off_abs<IOABS>(io, nbytes, first_channel, s, t, T);
                 for (int b = tid; b < nbytes; b += nt) s_bytes[j * nbytes + b] = q[b];
             }
         } else if ((((uintptr_t)src) & 3u) == 0) {
@@ -1615,7 +1727,7 @@ __device__ __forceinline__ void lc3_parse_pc_body(lc3_cfg_slot<CV> cfg, unsigned
     k.fin = s_fin + pair * (4 * 64) + lane;
     int rc_in = -100;
     if (valid) {
-        const size_t fb = lc3_io_flag_idx(io, first_channel, f / (size_t)T, f % (size_t)T, IOABS ? 1 : T);  // the flag array follows the frame layout
+        const size_t fb = lc3_io_flag_idx_abs<IOABS>(io, first_channel, f / (size_t)T, f % (size_t)T, T);  // the flag array follows the frame layout
         rc_in = (bad && bad[fb]) ? -100 : 0;
     }
     if (role == 0) {  // pc_timeouts: the handle's sticky count of pair halves that gave up on their partner (lc3gpu_decoder_pair_timeouts)
@@ -1669,6 +1781,24 @@ __global__ __launch_bounds__(512) void LC3_MIXED_KERNEL(lc3_parse_pc_items_kerne
 #if LC3_MULTI_TU && LC3_TU_KIND == 0
 __global__ __launch_bounds__(512) void lc3_parse_pc_items_kernel_all(lc3_groups G, const uint8_t *in, const uint8_t *bad, int32_t *planes, lc3_io io,
                                                                      unsigned *pc_timeouts);
+#endif
+template <class CV>
+__device__ __forceinline__ void lc3_parse_pc_body_mc_items(lc3_cfg_slot<CV> cfg, unsigned wg, const uint8_t *in, const uint8_t *bad, int32_t *planes,
+                                                           int nbytes, int n_frames, int T, int first_pos, lc3_io io, unsigned *pc_timeouts) {
+    lc3_parse_pc_body<CV, 2>(cfg, wg, in, bad, planes, nbytes, n_frames, T, first_pos, io, pc_timeouts);
+}
+#if LC3_IN_MC_ITEMS_TU(3)
+__global__ __launch_bounds__(512) void LC3_MIXED_KERNEL(lc3_parse_pc_mc_items_kernel)(lc3_groups G, const uint8_t *in, const uint8_t *bad,
+                                                                                      int32_t *planes, lc3_io io, unsigned *pc_timeouts) {
+    const lc3_group &g = G.g[lc3_find_group(G, blockIdx.x, 1)];
+    int32_t *p = planes + (size_t)g.frame_base * (size_t)LC3_PLANE_WORDS;
+    LC3_GROUP_VIEW_LIST(lc3_parse_pc_body_mc_items, g, blockIdx.x - g.wg_frame, in, bad, p, g.nbytes, g.n_streams * g.n_frames, g.n_frames,
+                        g.first_stream, io, pc_timeouts);
+}
+#endif
+#if LC3_MULTI_TU && LC3_TU_KIND == 0
+__global__ __launch_bounds__(512) void lc3_parse_pc_mc_items_kernel_all(lc3_groups G, const uint8_t *in, const uint8_t *bad, int32_t *planes, lc3_io io,
+                                                                        unsigned *pc_timeouts);
 #endif
 
 // Spectrum reconstruction D4-D8 of a full batch (lc3_dev_dec_recon.h), between the parser and the synthesis kernel:
@@ -1966,6 +2096,74 @@ __global__ __launch_bounds__(64 * LC3_WG_WAVES, 4) void lc3_decode_items_kernel_
                                                                                 const int32_t *planes, int16_t *pcm, lc3_io io);
 __global__ __launch_bounds__(64 * LC3_WG_WAVES, 4) void lc3_decode_items_late_kernel_all(lc3_groups G, lc3_dec_state *states, const int32_t *entries,
                                                                                      const int32_t *planes, int16_t *pcm, lc3_io io);
+#endif
+// ... of an mc-items call: the stream's samples C elements apart, its frames C * nf (see lc3_enc_front_mc_items_kernel)
+template <class CV, int LATE>
+__device__ __forceinline__ void lc3_decode_body_mc_items(lc3_cfg_slot<CV> cfg, unsigned wg, lc3_dec_state *states, const int32_t *entries,
+                                                         int first_pos, int n_streams, const int32_t *planes, int16_t *pcm, int nbytes,
+                                                         int n_frames, const lc3_stream_io *tab) {
+    const int lane = threadIdx.x & 63, wave = LC3_WAVE_ID();
+    lc3_dec_lds &L = lc3_dec_wg[wave];
+    const int s_raw = (int)wg * LC3_WG_WAVES + wave;
+    const int valid = s_raw < n_streams;
+    const int s = valid ? s_raw : n_streams - 1;  // (a shadow wave stays inside its own row)
+    typename CV::bind_t c0 = CV::bind(lc3_cfg_table[cfg.id]);
+    const int entry = lc3_list_entry(entries, first_pos + s);
+    lc3_dec_state *gst = states + (size_t)lc3_list_channel(entry);
+    int16_t *pcm_s = pcm + (size_t)lc3_mlist_off(&tab[first_pos + s].pcm_off1);
+    const int stride = lc3_list_entry(&tab[first_pos + s].pad, 0);
+#ifndef LC3_TABLES_IN_GLOBAL
+    const lc3_fft_image_regs tab_regs = lc3_fft_tables_image_issue(c0.stage_image);
+#endif
+    lc3_list_synth_stream_mc(cfg, L, lane, gst, lc3_list_fresh(entry), valid, nbytes, planes, (size_t)s * (size_t)n_frames, n_frames, pcm_s, stride,
+                             LATE, [&]() {
+#ifndef LC3_TABLES_IN_GLOBAL
+                                 lc3_fft_tables_image_commit(tab_regs);
+#endif
+                             });
+}
+template <class CV>
+__device__ __forceinline__ void lc3_decode_body_mc_items_now(lc3_cfg_slot<CV> cfg, unsigned wg, lc3_dec_state *states, const int32_t *entries,
+                                                             int first_pos, int n_streams, const int32_t *planes, int16_t *pcm, int nbytes,
+                                                             int n_frames, const lc3_stream_io *tab) {
+    lc3_decode_body_mc_items<CV, 0>(cfg, wg, states, entries, first_pos, n_streams, planes, pcm, nbytes, n_frames, tab);
+}
+template <class CV>
+__device__ __forceinline__ void lc3_decode_body_mc_items_late(lc3_cfg_slot<CV> cfg, unsigned wg, lc3_dec_state *states, const int32_t *entries,
+                                                              int first_pos, int n_streams, const int32_t *planes, int16_t *pcm, int nbytes,
+                                                              int n_frames, const lc3_stream_io *tab) {
+    lc3_decode_body_mc_items<CV, 1>(cfg, wg, states, entries, first_pos, n_streams, planes, pcm, nbytes, n_frames, tab);
+}
+#if LC3_IN_MC_ITEMS_TU(4)
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, 4) void LC3_MIXED_KERNEL(lc3_decode_mc_items_kernel)(lc3_groups G, lc3_dec_state *states,
+                                                                                   const int32_t *entries, const int32_t *planes,
+                                                                                   int16_t *pcm, lc3_io io) {
+    const lc3_group &g = G.g[lc3_find_group(G, blockIdx.x, 0)];
+    const int32_t *p = planes + (size_t)g.frame_base * (size_t)LC3_PLANE_WORDS;
+    LC3_GROUP_VIEW_LIST(lc3_decode_body_mc_items_now, g, blockIdx.x - g.wg_stream, states, entries, g.first_stream, g.n_streams, p, pcm, g.nbytes,
+                        g.n_frames, io.tab);
+}
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, 4) void LC3_MIXED_KERNEL(lc3_decode_mc_items_late_kernel)(lc3_groups G, lc3_dec_state *states,
+                                                                                        const int32_t *entries, const int32_t *planes,
+                                                                                        int16_t *pcm, lc3_io io) {
+    // The four pointers arrive as ONE eight-dword scalar load from the kernel arguments.  Under this body's register pressure (the late
+    // reconstruction's calls plus the strided store's) the allocator "spills" that tuple by rematerialising the load in every view's body
+    // and leaves the spill slot behind: 48 bytes of scratch that nothing reads or writes, where the items twin has none.  Opaque
+    // scalar values cannot be rematerialised: they go to spare lanes of a vector register like every other scalar spill, and the
+    // kernel needs no scratch
+    asm volatile("" : "+s"(states), "+s"(entries), "+s"(planes), "+s"(pcm));
+    const lc3_group &g = G.g[lc3_find_group(G, blockIdx.x, 0)];
+    const int32_t *p = planes + (size_t)g.frame_base * (size_t)LC3_PLANE_WORDS;
+    LC3_GROUP_VIEW_LIST(lc3_decode_body_mc_items_late, g, blockIdx.x - g.wg_stream, states, entries, g.first_stream, g.n_streams, p, pcm, g.nbytes,
+                        g.n_frames, io.tab);
+}
+#endif
+#if LC3_MULTI_TU && LC3_TU_KIND == 0
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, 4) void lc3_decode_mc_items_kernel_all(lc3_groups G, lc3_dec_state *states, const int32_t *entries,
+                                                                                   const int32_t *planes, int16_t *pcm, lc3_io io);
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, 4) void lc3_decode_mc_items_late_kernel_all(lc3_groups G, lc3_dec_state *states,
+                                                                                        const int32_t *entries, const int32_t *planes,
+                                                                                        int16_t *pcm, lc3_io io);
 #endif
 #if LC3_MULTI_TU && LC3_TU_KIND == 0
 __global__ __launch_bounds__(64 * LC3_WG_WAVES, 4) void lc3_decode_mixed_list_kernel_all(lc3_groups G, lc3_dec_state *states, const int32_t *entries,
@@ -2890,6 +3088,57 @@ struct HandleCommon {
                          (lc3_stream_io *)(slot + mlist_tab_offset(n)), mitems_plan);
         return mlist_ring.upload(mlist_bytes(n), s);
     }
+    // The items of an mc-items call (lc3gpu_*_mixed_mc_items), checked as items_check checks: an item is the channels [first_channel,
+    // first_channel + n_channels) of one stream -- one configuration, one frame size, one frame count.  channels: the expanded list's length;
+    // frames: the call's channel-frames
+    int mc_items_check(const lc3gpu_mc_item *items, int n, int min_bytes, int *channels, size_t *frames, int *max_frames) {
+        if (list_seen.size() != (size_t)num_channels) list_seen.assign((size_t)num_channels, 0u);
+        if (++list_call == 0u) {
+            std::fill(list_seen.begin(), list_seen.end(), 0u);
+            list_call = 1u;
+        }
+        size_t total = 0;
+        int most = 0, listed = 0;
+        for (int i = 0; i < n; i++) {
+            const lc3gpu_mc_item &it = items[i];
+            if (it.n_channels < 1 || it.n_channels > LC3_MCITEMS_MAX_CHANNELS) return LC3GPU_EINVAL;
+            if (it.first_channel < 0 || it.first_channel > num_channels - it.n_channels) return LC3GPU_ECHANNEL;
+            for (int c = 0; c < it.n_channels; c++) {
+                uint32_t &seen = list_seen[(size_t)(it.first_channel + c)];
+                if (seen == list_call) return LC3GPU_ECHANNEL;
+                seen = list_call;
+            }
+            const GroupHost &g0 = groups[(size_t)streams[(size_t)it.first_channel].group];
+            bool same_size = true;
+            for (int c = 1; c < it.n_channels; c++) {  // (lc3_encoder.rs:117-124: one configuration, one num_bytes_per_channel)
+                const GroupHost &g = groups[(size_t)streams[(size_t)(it.first_channel + c)].group];
+                if (g.h.slot != g0.h.slot) return LC3GPU_EINVAL;
+                same_size = same_size && g.nbytes == g0.nbytes;
+            }
+            if (it.nbytes == 0 && !same_size) return LC3GPU_ELENGTH;
+            if (it.n_frames < 1) return LC3GPU_ELENGTH;
+            if (it.nbytes != 0 && (it.nbytes < min_bytes || it.nbytes > LC3_MAX_NE)) return LC3GPU_ELENGTH;
+            total += (size_t)it.n_frames * (size_t)it.n_channels;
+            most = std::max(most, it.n_frames);
+            listed += it.n_channels;
+        }
+        if (total > (size_t)0x7fffffff) return LC3GPU_ELENGTH;  // (frame counts and flag offsets are 32-bit on the device)
+        *channels = listed;
+        *frames = total;
+        *max_frames = most;
+        return LC3GPU_OK;
+    }
+    // its plan (lc3_mcitems_build: the items plan over the expanded list, n_list channels), built and sent as mitems_send does
+    int mcitems_send(const lc3gpu_mc_item *items, int n, int n_list, const uint8_t *fresh, hipStream_t s) {
+        static_assert(sizeof(lc3gpu_mc_item) == sizeof(lc3_mcitem), "lc3gpu_mc_item is the plan's item");
+        mlist_describe();
+        uint8_t *slot = nullptr;
+        const int rc = mlist_ring.acquire(mlist_bytes(num_channels), &slot);
+        if (rc) return rc;
+        lc3_mcitems_build(mlist_groups.data(), mlist_streams.data(), fresh, (const lc3_mcitem *)items, n, (int32_t *)slot,
+                          (lc3_stream_io *)(slot + mlist_tab_offset(n_list)), mitems_plan);
+        return mlist_ring.upload(mlist_bytes(n_list), s);
+    }
     const int32_t *d_mlist_entries() const { return (const int32_t *)mlist_ring.d; }
     const lc3_stream_io *d_mlist_tab(int n) const { return (const lc3_stream_io *)(mlist_ring.d + mlist_tab_offset(n)); }
     // a multi-unit library's list twins carry a body per compile-time view and none for the run-time view (LC3_GROUP_VIEW_LIST)
@@ -3245,6 +3494,20 @@ static int lc3_pack_pc_optin() {
     done[dev] = true;
     return LC3GPU_OK;
 }
+// ... and the pair packer of the mc-items call (lc3gpu_encode_mixed_mc_items): at 128 frames per workgroup it passes the default 64 KB
+// from frame sizes of about 360 bytes on.  A list of its own, so that what the other calls opt in to is what it was
+static int lc3_pack_pc_mc_optin() {
+    static bool done[LC3_MAX_DEVICES] = {};
+    static std::mutex mu;
+    std::lock_guard<std::mutex> lock(mu);
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    if (dev < 0 || dev >= LC3_MAX_DEVICES) return LC3GPU_EINVAL;
+    if (done[dev]) return LC3GPU_OK;
+    HIP_TRY(hipFuncSetAttribute((const void *)LC3_MIXED_LAUNCH(lc3_pack_pc_mc_items_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    done[dev] = true;
+    return LC3GPU_OK;
+}
 // Frames per workgroup of the pair kernels: 128 (four waves, one per SIMD; ~40 KB of LDS at 150-byte frames).  Such a workgroup takes
 // the place of exactly ONE workgroup of a wave-per-stream kernel (40 KB, a wave per SIMD) when another handle's call runs beside it on
 // another HIP stream; with 256 frames (70 KB, two waves per SIMD) it displaced two for as long as it ran.  Measured: two-stream
@@ -3279,6 +3542,19 @@ static int lc3_parse_pc_optin() {
 #define LC3_X(i, V) HIP_TRY(hipFuncSetAttribute((const void *)lc3_parse_pc_kernel<V>, hipFuncAttributeMaxDynamicSharedMemorySize, LC3_PC_LDS_MAX));
     LC3_FOR_EACH_VIEW(LC3_X)
 #undef LC3_X
+    done[dev] = true;
+    return LC3GPU_OK;
+}
+// ... and the pair parser of the mc-items call (see lc3_pack_pc_mc_optin)
+static int lc3_parse_pc_mc_optin() {
+    static bool done[LC3_MAX_DEVICES] = {};
+    static std::mutex mu;
+    std::lock_guard<std::mutex> lock(mu);
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    if (dev < 0 || dev >= LC3_MAX_DEVICES) return LC3GPU_EINVAL;
+    if (done[dev]) return LC3GPU_OK;
+    HIP_TRY(hipFuncSetAttribute((const void *)LC3_MIXED_LAUNCH(lc3_parse_pc_mc_items_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LC3_PC_LDS_MAX));
     done[dev] = true;
     return LC3GPU_OK;
 }
@@ -3437,7 +3713,7 @@ static int state_blobs_load_channels(HandleCommon &hc, ST *d_states, const int32
 
 extern "C" {
 
-int lc3gpu_version(void) { return 320; }
+int lc3gpu_version(void) { return 330; }
 
 const char *lc3gpu_strerror(int code) {
     switch (code) {
@@ -4145,6 +4421,87 @@ int lc3gpu_encode_mixed_items(lc3gpu_encoder *e, const lc3gpu_item *items, int n
     return call.end(rc);
 }
 
+// A list of mc items of a mixed handle: lc3gpu_encode_mixed_items over the items' channels, each one channel of C in WAV sample order
+// (lc3_mcitems_build).  The front half and the packers are the mc twins, which read C from the table row; the vector quantiser and the
+// back half see plane columns only and are the items call's kernels.
+int lc3gpu_encode_mixed_mc_items(lc3gpu_encoder *e, const lc3gpu_mc_item *items, int n_items, const int16_t *d_pcm, uint8_t *d_out,
+                                 void *stream_) {
+    if (!e || !e->mixed || n_items < 0) return LC3GPU_EINVAL;
+    if (n_items == 0) return LC3GPU_OK;
+    if (!items || !d_pcm || !d_out || ((uintptr_t)d_pcm & 3u) != 0) return LC3GPU_EINVAL;
+    if (!e->mixed_list_views_ok()) return LC3GPU_EUNSUPPORTED;
+    size_t frames = 0;
+    int max_frames = 0, n_list = 0;
+    int rc = e->mc_items_check(items, n_items, 20, &n_list, &frames, &max_frames);
+    if (rc) return rc;
+    LC3_ON_DEVICE(e);
+    hipStream_t stream = (hipStream_t)stream_;
+    BatchCall call(*e, stream);
+    rc = call.begin();
+    if (rc == LC3GPU_OK) rc = encoder_reserve_planes(e, frames, stream);
+    if (rc == LC3GPU_OK) rc = e->mcitems_send(items, n_items, n_list, e->fresh_mask.data(), stream);
+    if (rc) return rc;
+    const lc3_mitems_plan &P = e->mitems_plan;
+    const int32_t *d_entries = e->d_mlist_entries();
+    const lc3_io io = {0, e->d_mlist_tab(n_list)};
+    const dim3 wg_block(64 * LC3_WG_WAVES);
+    const bool pairs = lc3_prep_symbols_mode(frames) == 0 && lc3_pack_pc_enabled();
+    if (pairs && (rc = lc3_pack_pc_mc_optin()) != LC3GPU_OK) return rc;  // (before anything is launched)
+    call.arm();
+    rc = encode_stages(
+        e, stream, 0, nullptr,
+        [&] {
+            return items_stage(*e, P, [&](ItemsGroups groups, int) {
+                GroupTable t;
+                groups(256u, t);
+                hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_enc_front_mc_items_kernel), dim3(t.wg_stream), wg_block, 0, stream, t.G, e->d_states, d_entries,
+                                   d_pcm, e->d_mid, e->d_planes, io, e->spec_flags);
+                return LC3GPU_OK;
+            });
+        },
+        [&] {
+            return items_stage(*e, P, [&](ItemsGroups groups, int) {
+                GroupTable t;
+                groups(256u, t);
+                hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_sns_vq_items_kernel), dim3(t.wg_frame), dim3(256), 0, stream, t.G, e->d_mid, e->d_planes,
+                                   e->spec_flags);
+                return LC3GPU_OK;
+            });
+        },
+        [&] {
+            return items_stage(*e, P, [&](ItemsGroups groups, int) {
+                GroupTable t;
+                groups(256u, t);
+                hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_enc_back_items_kernel), dim3(t.wg_stream), wg_block, 0, stream, t.G, e->d_states, d_entries,
+                                   (const float *)e->d_mid, e->d_planes, e->spec_flags | lc3_prep_symbols_flag(frames, true));
+                return LC3GPU_OK;
+            });
+        },
+        [] { return LC3GPU_OK; },
+        [&] {
+            return items_stage(*e, P, [&](ItemsGroups groups, int max_nbytes) {
+                GroupTable t;  // (the LDS of a launch set is sized by ITS largest frame)
+                if (pairs) {
+                    const unsigned pfpb = lc3_pack_pc_fpb(max_nbytes);
+                    groups(pfpb, t);
+                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_pack_pc_mc_items_kernel), dim3(t.wg_frame), dim3(2 * pfpb),
+                                       lc3_pack_pc_lds(pfpb, max_nbytes), stream, t.G, (const int32_t *)e->d_planes, d_out, io, e->d_pc_timeouts);
+                } else {
+                    const unsigned fpb = lc3_frame_block_fit(LC3_PACK_LDS_FIXED, (size_t)max_nbytes);
+                    const size_t lds = LC3_PACK_LDS_FIXED + (((size_t)fpb * (size_t)max_nbytes + 3) & ~(size_t)3) + 4;
+                    groups(fpb, t);
+                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_pack_mc_items_kernel), dim3(t.wg_frame), dim3(fpb), lds, stream, t.G,
+                                       (const int32_t *)e->d_planes, d_out, io);
+                }
+                return LC3GPU_OK;
+            });
+        });
+    if (rc == LC3GPU_OK)
+        for (int i = 0; i < n_items; i++)
+            for (int c = 0; c < items[i].n_channels; c++) e->fresh_mask[(size_t)e->streams[(size_t)(items[i].first_channel + c)].internal] = 0;
+    return call.end(rc);
+}
+
 static int encode_frame_host(lc3gpu_encoder *e, int channel_index, const int16_t *samples_in, int n_samples,
                              uint8_t *buf_out, int nbytes, float *dbg) {
     if (!e || !samples_in || !buf_out) return LC3GPU_EINVAL;
@@ -4806,6 +5163,88 @@ int lc3gpu_decode_mixed_items(lc3gpu_decoder *d, const lc3gpu_item *items, int n
         });
     if (rc == LC3GPU_OK)
         for (int i = 0; i < n_items; i++) d->fresh_clear(d->streams[(size_t)items[i].channel].internal);
+    return call.end(rc);
+}
+
+// A list of mc items of a mixed handle, as lc3gpu_encode_mixed_mc_items: the parsers and the synthesis forms are the mc twins, the wave-
+// per-frame reconstruction and the TNS kernel the items call's
+int lc3gpu_decode_mixed_mc_items(lc3gpu_decoder *d, const lc3gpu_mc_item *items, int n_items, const uint8_t *d_in, const uint8_t *d_bad,
+                                 int16_t *d_pcm, void *stream_) {
+    if (!d || !d->mixed || n_items < 0) return LC3GPU_EINVAL;
+    if (n_items == 0) return LC3GPU_OK;
+    if (!items || !d_in || !d_pcm || ((uintptr_t)d_pcm & 3u) != 0) return LC3GPU_EINVAL;
+    if (!d->mixed_list_views_ok()) return LC3GPU_EUNSUPPORTED;
+    size_t frames = 0;
+    int max_frames = 0, n_list = 0;
+    int rc = d->mc_items_check(items, n_items, 1, &n_list, &frames, &max_frames);
+    if (rc) return rc;
+    LC3_ON_DEVICE(d);
+    hipStream_t stream = (hipStream_t)stream_;
+    const int mode = lc3_recon_mode(frames, max_frames);
+    const bool pairs = mode == LC3_RECON_LANE && lc3_parse_pc_enabled();
+    BatchCall call(*d, stream);
+    rc = call.begin();
+    if (rc == LC3GPU_OK) rc = decoder_reserve_planes(d, frames, stream);
+    if (rc == LC3GPU_OK && mode == LC3_RECON_WAVE) rc = lc3_tns_lds_optin();
+    if (rc == LC3GPU_OK && pairs) rc = lc3_parse_pc_mc_optin();
+    if (rc == LC3GPU_OK) rc = d->mcitems_send(items, n_items, n_list, d->fresh_mask.data(), stream);
+    if (rc) return rc;
+    const lc3_mitems_plan &P = d->mitems_plan;
+    const int32_t *d_entries = d->d_mlist_entries();
+    const lc3_io io = {0, d->d_mlist_tab(n_list)};
+    call.arm();
+    rc = decode_stages(
+        d, stream, 0, mode,
+        [&] {
+            return items_stage(*d, P, [&](ItemsGroups groups, int max_nbytes) {
+                GroupTable t;
+                if (pairs) {
+                    const unsigned pfpb = lc3_parse_pc_fpb(max_nbytes);
+                    groups(pfpb, t);
+                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_parse_pc_mc_items_kernel), dim3(t.wg_frame), dim3(2 * pfpb),
+                                       lc3_parse_pc_lds(pfpb, max_nbytes), stream, t.G, d_in, d_bad, d->d_planes, io, d->d_pc_timeouts);
+                } else {
+                    const unsigned fpb = lc3_frame_block_fit(LC3_PARSE_LDS_FIXED, (size_t)(64 + max_nbytes));
+                    const size_t lds = LC3_PARSE_LDS_FIXED + (size_t)fpb * (size_t)(64 + max_nbytes);
+                    groups(fpb, t);
+                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_parse_mc_items_kernel), dim3(t.wg_frame), dim3(fpb), lds, stream, t.G, d_in, d_bad, d->d_planes,
+                                       io, mode);
+                }
+                return LC3GPU_OK;
+            });
+        },
+        [&] {
+            return items_stage(*d, P, [&](ItemsGroups groups, int) {
+                GroupTable t;
+                groups((unsigned)LC3_WG_WAVES, t);
+                hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_recon_items_kernel), dim3(t.wg_frame), dim3(64 * LC3_WG_WAVES), 0, stream, t.G, d->d_planes);
+                return LC3GPU_OK;
+            });
+        },
+        [&] {
+            return items_stage(*d, P, [&](ItemsGroups groups, int) {
+                GroupTable t;
+                groups((unsigned)LC3_TNS_FPB, t);
+                hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_tns_items_kernel), dim3(t.wg_frame), dim3(LC3_TNS_FPB), LC3_TNS_LDS, stream, t.G, d->d_planes);
+                return LC3GPU_OK;
+            });
+        },
+        [&] {
+            return items_stage(*d, P, [&](ItemsGroups groups, int) {
+                GroupTable t;
+                groups(256u, t);
+                if (mode == LC3_RECON_LATE)
+                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_decode_mc_items_late_kernel), dim3(t.wg_stream), dim3(64 * LC3_WG_WAVES), 0, stream, t.G,
+                                       d->d_states, d_entries, (const int32_t *)d->d_planes, d_pcm, io);
+                else
+                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_decode_mc_items_kernel), dim3(t.wg_stream), dim3(64 * LC3_WG_WAVES), 0, stream, t.G,
+                                       d->d_states, d_entries, (const int32_t *)d->d_planes, d_pcm, io);
+                return LC3GPU_OK;
+            });
+        });
+    if (rc == LC3GPU_OK)
+        for (int i = 0; i < n_items; i++)
+            for (int c = 0; c < items[i].n_channels; c++) d->fresh_clear(d->streams[(size_t)(items[i].first_channel + c)].internal);
     return call.end(rc);
 }
 

@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "lc3gpu.h")
 
 OPAQUE = {"lc3gpu_encoder": "Lc3GpuEncoder", "lc3gpu_decoder": "Lc3GpuDecoder", "lc3gpu_pipeline": "Lc3GpuPipeline",
-          "lc3gpu_stream_desc": "Lc3GpuStreamDesc", "lc3gpu_frame_info": "Lc3GpuFrameInfo", "lc3gpu_item": "Lc3GpuItem"}
+          "lc3gpu_stream_desc": "Lc3GpuStreamDesc", "lc3gpu_frame_info": "Lc3GpuFrameInfo", "lc3gpu_item": "Lc3GpuItem", "lc3gpu_mc_item": "Lc3GpuMcItem"}
 SCALAR = {"int": "i32", "unsigned": "u32", "unsigned int": "u32", "float": "f32", "double": "f64", "size_t": "usize",
           "int16_t": "i16", "uint16_t": "u16", "uint8_t": "u8", "int32_t": "i32", "uint32_t": "u32", "int64_t": "i64", "uint64_t": "u64",
           "unsigned long long": "u64", "char": "c_char", "void": "c_void"}
@@ -207,6 +207,15 @@ impl Lc3EncoderGpu {
     pub unsafe fn encode_mixed_items_device(&mut self, items: &[Lc3GpuItem], d_pcm: *const i16, d_out: *mut u8, hip_stream: *mut c_void) -> i32 {
         lc3gpu_encode_mixed_items(self.h, items.as_ptr(), items.len() as i32, d_pcm, d_out, hip_stream)
     }
+    /// Multi-channel items of a mixed-configuration handle: WAV sample order in, the channels' frames back to back out, the order
+    /// examples/encode.rs:96-115 reads and writes.
+    ///
+    /// # Safety
+    /// `d_pcm` / `d_out` must be device allocations laid out as include/lc3gpu.h states for lc3gpu_encode_mixed_mc_items that outlive the
+    /// call's work; `items` is host memory and free again when the call returns.
+    pub unsafe fn encode_mixed_mc_items_device(&mut self, items: &[Lc3GpuMcItem], d_pcm: *const i16, d_out: *mut u8, hip_stream: *mut c_void) -> i32 {
+        lc3gpu_encode_mixed_mc_items(self.h, items.as_ptr(), items.len() as i32, d_pcm, d_out, hip_stream)
+    }
     /// a new `EncoderChannel` for each named channel (from its next call on; no wait); the others are untouched
     pub fn reset_channels(&mut self, channels: &[i32]) -> Result<(), i32> {
         let rc = unsafe { lc3gpu_encoder_reset_channels(self.h, channels.as_ptr(), channels.len() as i32) };
@@ -299,6 +308,15 @@ impl Lc3DecoderGpu {
                                             hip_stream: *mut c_void) -> i32 {
         lc3gpu_decode_mixed_items(self.h, items.as_ptr(), items.len() as i32, d_in, d_bad_frame, d_pcm, hip_stream)
     }
+    /// Multi-channel items: the channels' frames back to back in, WAV sample order out (examples/decode.rs:93-118).
+    ///
+    /// # Safety
+    /// device allocations laid out as include/lc3gpu.h states for lc3gpu_decode_mixed_mc_items that outlive the call's work; `items` is
+    /// host memory and free again when the call returns.
+    pub unsafe fn decode_mixed_mc_items_device(&mut self, items: &[Lc3GpuMcItem], d_in: *const u8, d_bad_frame: *const u8, d_pcm: *mut i16,
+                                               hip_stream: *mut c_void) -> i32 {
+        lc3gpu_decode_mixed_mc_items(self.h, items.as_ptr(), items.len() as i32, d_in, d_bad_frame, d_pcm, hip_stream)
+    }
     /// a new `DecoderChannel` for each named channel (from its next call on; no wait; its PLC count goes to zero)
     pub fn reset_channels(&mut self, channels: &[i32]) -> Result<(), i32> {
         let rc = unsafe { lc3gpu_decoder_reset_channels(self.h, channels.as_ptr(), channels.len() as i32) };
@@ -373,7 +391,7 @@ def generate():
         "",
     ]
     for c, r in sorted(OPAQUE.items()):
-        if c in ("lc3gpu_stream_desc", "lc3gpu_frame_info", "lc3gpu_item"):
+        if c in ("lc3gpu_stream_desc", "lc3gpu_frame_info", "lc3gpu_item", "lc3gpu_mc_item"):
             continue
         lines += ["#[repr(C)]", "pub struct %s {" % r, "    _private: [u8; 0],", "}"]
     lines += ["/// one stream of a mixed-configuration handle (lc3gpu_stream_desc)", "#[repr(C)]", "#[derive(Clone, Copy, Debug)]",
@@ -382,6 +400,10 @@ def generate():
               "/// descriptor's)", "#[repr(C)]", "#[derive(Clone, Copy, Debug, Default)]", "pub struct Lc3GpuItem {", "    pub channel: i32,",
               "    pub n_frames: i32,", "    pub nbytes: i32,", "    pub reserved: i32,", "}",
               "const _: () = assert!(core::mem::size_of::<Lc3GpuItem>() == 16);"]
+    lines += ["/// one item of the *_mixed_mc_items calls (lc3gpu_mc_item, 16 bytes): the channels of one stream, its frames in this call and their",
+              "/// size (0 = the descriptors')", "#[repr(C)]", "#[derive(Clone, Copy, Debug, Default)]", "pub struct Lc3GpuMcItem {",
+              "    pub first_channel: i32,", "    pub n_channels: i32,", "    pub n_frames: i32,", "    pub nbytes: i32,", "}",
+              "const _: () = assert!(core::mem::size_of::<Lc3GpuMcItem>() == 16);"]
     lines += ["/// one frame's record of lc3gpu_inspect (lc3gpu_frame_info, 128 bytes): status LC3GPU_FRAME_*, the side information",
               "/// (decoder/side_info.rs:20-31) and the arithmetic data (decoder/arithmetic_codec.rs:99-107)", "#[repr(C)]",
               "#[derive(Clone, Copy, Debug, Default)]", "pub struct Lc3GpuFrameInfo {"]
