@@ -298,6 +298,80 @@ _Static_assert(sizeof(lc3gpu_mc_item) == 16, "lc3gpu_mc_item is 16 bytes");
 #endif
 int lc3gpu_encode_mixed_mc_items(lc3gpu_encoder *enc, const lc3gpu_mc_item *items, int n_items, const int16_t *d_pcm, uint8_t *d_out,
                                  void *hip_stream);
+/* Batch over a list of VIEWS of a mixed handle: frames and PCM read and written IN PLACE.  A server's data never lies compact in list
+ * order: received frames sit in per-stream jitter rings of fixed-size slots behind packet headers, PCM sits in per-stream rings or in a
+ * capture buffer with more channels than the stream uses, and which streams are due changes every tick.  A view is an item that also
+ * says where its data lies, so a tick needs no gather or scatter pass around the call.  The contract of lc3gpu_encode_mixed_items (which
+ * see), with these differences:
+ *   views     HOST lc3gpu_view[n_views], any order, no channel twice; may be reused as soon as the call returns.  `channel`, `n_frames`
+ *             and `nbytes` as in lc3gpu_item; the other fields place the view's frames
+ *   placement with nf the frame length and nb the effective frame size of the view:
+ *               sample n of frame t   d_pcm[pcm_off + t * pcm_pitch + n * pcm_stride]
+ *               frame t's bytes       d_out / d_in [byte_off + t * byte_pitch ..  + nb)
+ *               frame t's flag        d_bad_frame[flag_off + t * flag_pitch]   (decoder, and only when d_bad_frame is given)
+ *             a pitch of 0 stands for the compact one: nf * pcm_stride, nb, 1.  pcm_stride 1 is a planar stream and is read and written
+ *             with 32-bit accesses (pcm_off and pcm_pitch even, d_pcm 4-byte aligned); pcm_stride C >= 2 is one channel of C in WAV
+ *             sample order, 16-bit accesses (d_pcm 2-byte aligned).  The encoder's history for frame t > 0 is the tail of frame t-1
+ *             wherever that frame lies.  Only a frame's own nb bytes and nf samples are written: every byte and sample between and
+ *             around them is left as it was
+ *   sizes     pcm_elems, out_bytes / in_bytes, n_flags: the extents of the caller's buffers in elements, bytes and flags.  EVERY sample,
+ *             byte and flag of every frame of every view is checked against them on the host, in 64-bit arithmetic that cannot
+ *             overflow; a call that would touch anything outside is refused and never reaches the device
+ *   overlap   inputs may overlap freely (two views may read the same PCM).  Output ranges of different views may INTERLEAVE: a stereo SDU
+ *             is two views with byte_pitch = 2 * nb whose byte_off are nb apart.  Frames that truly overlap on output are the caller's
+ *             error: the content of the overlapping bytes or samples is then unspecified; every write is still inside the checked extents
+ *   checks    on the host before anything is queued; a refused call has launched nothing, written nothing, advanced no channel and
+ *             consumed no pending reset:
+ *               channel out of range or named twice                  LC3GPU_ECHANNEL
+ *               n_frames < 1                                         LC3GPU_ELENGTH
+ *               nbytes not 0 and outside 20..400 (encoder)           LC3GPU_ELENGTH
+ *               nbytes not 0 and outside 1..400 (decoder)            LC3GPU_ELENGTH
+ *               more than 2^31 - 1 frames in one call                LC3GPU_ELENGTH
+ *               any sample, byte or flag of any frame of a view
+ *               outside [0, pcm_elems), [0, out_bytes / in_bytes)
+ *               or [0, n_flags)                                      LC3GPU_ELENGTH
+ *               pcm_stride outside 1..8                              LC3GPU_EINVAL
+ *               a negative offset                                    LC3GPU_EINVAL
+ *               a non-zero pitch below its minimum (nf * pcm_stride,
+ *               nb, 1)                                               LC3GPU_EINVAL
+ *               reserved != 0                                        LC3GPU_EINVAL
+ *               pcm_stride == 1 with an odd pcm_off, an odd
+ *               pcm_pitch or a d_pcm base not 4-byte aligned         LC3GPU_EINVAL
+ *               pcm_stride >= 2 with a d_pcm base not 2-byte aligned LC3GPU_EINVAL
+ *               a null pointer, n_views < 0, a UNIFORM handle, a
+ *               bound handle on another stream                       LC3GPU_EINVAL
+ *               n_views == 0                                         LC3GPU_OK (nothing launched)
+ *             LC3GPU_EPAIR and LC3GPU_EUNSUPPORTED as for lc3gpu_*_mixed_items
+ *   state     exactly that of the items calls.  Two equivalences are part of the contract: views whose placements are the items call's
+ *             prefix sums (pcm_stride 1, all pitches 0) give the bytes, the PCM, the state blobs and the PLC counts of
+ *             lc3gpu_*_mixed_items; views that spell out an mc item's channels (channel c of C at bases P, B, F: pcm_off = P + c,
+ *             pcm_stride = C, pcm_pitch = nf * C, byte_off = B + c * nb, byte_pitch = C * nb, flag_off = F + c, flag_pitch = C) give
+ *             those of lc3gpu_*_mixed_mc_items
+ *   mixing    views, mc-items, items, mixed-list, lc3gpu_*_mixed and *_frame calls may alternate on a handle
+ *   launches  as for the items calls: the bucket key is (configuration, effective nbytes, n_frames), placement is no part of it; ONE
+ *             launch per kernel per 24 buckets, one upload, one host check
+ * NOT provided (out of scope): a size per frame within a view, ring wrap inside one view (the caller sizes the ring so that a tick does
+ * not wrap, or names the two parts in two calls), strides above 8, the host-resident calls, the pipeline object, uniform handles. */
+typedef struct lc3gpu_view {
+    int32_t channel;     /* descriptor index of the mixed handle */
+    int32_t n_frames;    /* >= 1 */
+    int32_t nbytes;      /* frame size this call; 0 = the descriptor's */
+    int32_t pcm_stride;  /* elements between two samples of a frame: 1..8 (1 = planar; C = one channel of C in WAV order) */
+    int64_t pcm_off;     /* element index of sample 0 of frame 0 in d_pcm */
+    int64_t byte_off;    /* byte index of frame 0 in d_out / d_in */
+    int64_t flag_off;    /* decoder: index of frame 0's flag in d_bad_frame (ignored when that is NULL, and by the encoder) */
+    int32_t pcm_pitch;   /* elements from frame t to frame t+1; 0 = nf * pcm_stride; otherwise >= nf * pcm_stride */
+    int32_t byte_pitch;  /* bytes from frame t to frame t+1; 0 = effective nbytes; otherwise >= effective nbytes */
+    int32_t flag_pitch;  /* 0 = 1; otherwise >= 1 */
+    int32_t reserved[3]; /* 0 */
+} lc3gpu_view;
+#ifdef __cplusplus
+static_assert(sizeof(lc3gpu_view) == 64, "lc3gpu_view is 64 bytes");
+#else
+_Static_assert(sizeof(lc3gpu_view) == 64, "lc3gpu_view is 64 bytes");
+#endif
+int lc3gpu_encode_mixed_views(lc3gpu_encoder *enc, const lc3gpu_view *views, int n_views, const int16_t *d_pcm, size_t pcm_elems,
+                              uint8_t *d_out, size_t out_bytes, void *hip_stream);
 
 /* per-channel state blobs (checkpoint / CPU cross-checks): size per channel, device->host copy, host->device.
  * nbytes must equal state_size * num_channels (LC3GPU_ELENGTH otherwise); both calls synchronise the device.  A channel's blob
@@ -423,6 +497,11 @@ int lc3gpu_decode_mixed_items(lc3gpu_decoder *dec, const lc3gpu_item *items, int
  * item or NULL, and frame sizes 1..400. */
 int lc3gpu_decode_mixed_mc_items(lc3gpu_decoder *dec, const lc3gpu_mc_item *items, int n_items, const uint8_t *d_in,
                                  const uint8_t *d_bad_frame, int16_t *d_pcm, void *hip_stream);
+/* Batch decode over a list of VIEWS of a mixed handle: the contract of lc3gpu_encode_mixed_views (which see) with d_in / in_bytes like that
+ * call's d_out / out_bytes, d_pcm written where it reads, d_bad_frame / n_flags the flag array and its length (NULL: no flags are read and
+ * flag_off, flag_pitch and n_flags are ignored), and frame sizes 1..400. */
+int lc3gpu_decode_mixed_views(lc3gpu_decoder *dec, const lc3gpu_view *views, int n_views, const uint8_t *d_in, size_t in_bytes,
+                              const uint8_t *d_bad_frame, size_t n_flags, int16_t *d_pcm, size_t pcm_elems, void *hip_stream);
 
 size_t lc3gpu_decoder_state_size(const lc3gpu_decoder *dec);
 int lc3gpu_decoder_state_save(lc3gpu_decoder *dec, void *host_dst, size_t nbytes);

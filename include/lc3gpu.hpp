@@ -91,6 +91,13 @@ public:
         int rc = lc3gpu_encode_mixed_mc_items(h_, items.data(), (int)items.size(), d_pcm, d_out, hip_stream);
         if (rc) throw Error(rc, "encode_mixed_mc_items");
     }
+    // mixed handle: views (lc3gpu_view: an item with the placement of its PCM and its frames), read and written in place; pcm_elems /
+    // out_bytes are the buffers' extents, which every view is checked against (lc3gpu_encode_mixed_views)
+    void encode_mixed_views(const std::vector<lc3gpu_view> &views, const int16_t *d_pcm, size_t pcm_elems, uint8_t *d_out, size_t out_bytes,
+                            void *hip_stream = nullptr) {
+        int rc = lc3gpu_encode_mixed_views(h_, views.data(), (int)views.size(), d_pcm, pcm_elems, d_out, out_bytes, hip_stream);
+        if (rc) throw Error(rc, "encode_mixed_views");
+    }
     // back to the freshly constructed state from the next call on: every channel, or the named ones (a new EncoderChannel); no wait
     void reset() {
         int rc = lc3gpu_encoder_reset(h_);
@@ -187,6 +194,12 @@ public:
                                const uint8_t *d_bad_frame = nullptr) {
         int rc = lc3gpu_decode_mixed_mc_items(h_, items.data(), (int)items.size(), d_in, d_bad_frame, d_pcm, hip_stream);
         if (rc) throw Error(rc, "decode_mixed_mc_items");
+    }
+    // mixed handle: views (see Encoder::encode_mixed_views); d_bad_frame / n_flags the flag array and its length, or nullptr / 0
+    void decode_mixed_views(const std::vector<lc3gpu_view> &views, const uint8_t *d_in, size_t in_bytes, int16_t *d_pcm, size_t pcm_elems,
+                            void *hip_stream = nullptr, const uint8_t *d_bad_frame = nullptr, size_t n_flags = 0) {
+        int rc = lc3gpu_decode_mixed_views(h_, views.data(), (int)views.size(), d_in, in_bytes, d_bad_frame, n_flags, d_pcm, pcm_elems, hip_stream);
+        if (rc) throw Error(rc, "decode_mixed_views");
     }
     // every channel, or the named ones (a new DecoderChannel; their PLC counts go to zero); no wait
     void reset() {

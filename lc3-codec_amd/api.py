@@ -256,6 +256,8 @@ def load_library():
     L.lc3gpu_decode_mixed_items.argtypes = [vp, vp, i, vp, vp, vp, vp]
     L.lc3gpu_encode_mixed_mc_items.argtypes = [vp, vp, i, vp, vp, vp]
     L.lc3gpu_decode_mixed_mc_items.argtypes = [vp, vp, i, vp, vp, vp, vp]
+    L.lc3gpu_encode_mixed_views.argtypes = [vp, vp, i, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp]
+    L.lc3gpu_decode_mixed_views.argtypes = [vp, vp, i, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp]
     L.lc3gpu_encoder_reset_channels.argtypes = [vp, vp, i]
     L.lc3gpu_decoder_reset_channels.argtypes = [vp, vp, i]
     L.lc3gpu_encoder_state_save_channels.argtypes = [vp, vp, i, vp, ctypes.c_size_t]
@@ -349,6 +351,7 @@ ABI_SYMBOLS = [
     "lc3gpu_decoder_state_load_channels", "lc3gpu_encode_mixed_list", "lc3gpu_decode_mixed_list",
     "lc3gpu_encode_mixed_items", "lc3gpu_decode_mixed_items",
     "lc3gpu_encode_mixed_mc_items", "lc3gpu_decode_mixed_mc_items",
+    "lc3gpu_encode_mixed_views", "lc3gpu_decode_mixed_views",
 ]
 
 # LC3GPU_SPEC_*: opt-in corrections of the reference's deviations from the LC3 specification (default 0 = reference behaviour)
@@ -516,6 +519,49 @@ def _mc_item_list(items):
     return out
 
 
+# lc3gpu_view (include/lc3gpu.h), 64 bytes: an item of the *_mixed_views calls with its own placement
+VIEW_FIELDS = ("channel", "n_frames", "nbytes", "pcm_stride", "pcm_off", "byte_off", "flag_off", "pcm_pitch", "byte_pitch", "flag_pitch")
+VIEW_DTYPE = np.dtype({"names": list(VIEW_FIELDS) + ["reserved"],
+                       "formats": [np.int32] * 4 + [np.int64] * 3 + [np.int32] * 3 + [(np.int32, 3)],
+                       "offsets": [0, 4, 8, 12, 16, 24, 32, 40, 44, 48, 52], "itemsize": 64})
+
+
+def _view_list(views):
+    """a sequence of tuples (channel, n_frames, nbytes, pcm_stride, pcm_off, byte_off[, flag_off[, pcm_pitch[, byte_pitch[, flag_pitch]]]])
+    or of dicts over VIEW_FIELDS (channel, n_frames, pcm_off and byte_off required; pcm_stride defaults to 1, everything else to 0), or
+    a VIEW_DTYPE array -> contiguous HOST VIEW_DTYPE[n], the lc3gpu_view array of the *_mixed_views calls"""
+    if isinstance(views, np.ndarray) and views.dtype == VIEW_DTYPE:
+        return np.ascontiguousarray(views.reshape(-1))
+    rows = list(views)
+    out = np.zeros(len(rows), VIEW_DTYPE)
+    for i, r in enumerate(rows):
+        if isinstance(r, dict):
+            unknown = set(r) - set(VIEW_FIELDS)
+            missing = {"channel", "n_frames", "pcm_off", "byte_off"} - set(r)
+            if unknown or missing:
+                raise TypeError("a view names %s and may name %s" % ("channel, n_frames, pcm_off, byte_off", ", ".join(VIEW_FIELDS)))
+            r = dict({"pcm_stride": 1}, **r)
+        else:
+            r = tuple(r)
+            if not 6 <= len(r) <= len(VIEW_FIELDS):
+                raise TypeError("a view is (channel, n_frames, nbytes, pcm_stride, pcm_off, byte_off[, flag_off[, pcm_pitch[, byte_pitch[, flag_pitch]]]])")
+            r = dict(zip(VIEW_FIELDS, r))
+        for name, v in r.items():
+            if not isinstance(v, (int, np.integer)):
+                raise TypeError("view fields must be integers")
+            out[i][name] = v
+    return out
+
+
+def _numel(x, what):
+    """elements of a torch tensor or numpy array (the buffer extents the *_mixed_views calls check every view against)"""
+    if hasattr(x, "numel"):
+        return int(x.numel())
+    if isinstance(x, np.ndarray):
+        return int(x.size)
+    raise TypeError("%s: pass the buffer's extent when the buffer is a bare pointer" % what)
+
+
 class Lc3Config:
     """common/config.rs:18-100"""
 
@@ -678,6 +724,19 @@ class Lc3Encoder:
         rc = self._L.lc3gpu_encode_mixed_mc_items(self._h, _ptr(it), int(it.shape[0]), _ptr(d_pcm), _ptr(d_out), _ptr(stream))
         if rc:
             raise Lc3EncoderError(rc, "encode_mixed_mc_items")
+
+    def encode_mixed_views(self, views, d_pcm, d_out, stream=None, pcm_elems=None, out_bytes=None):
+        """a mixed handle's batch over views (`_view_list`: tuples or dicts of lc3gpu_view's fields): encode_mixed_items with a placement
+        per item -- sample n of frame t at d_pcm[pcm_off + t * pcm_pitch + n * pcm_stride], frame t's bytes at d_out[byte_off + t *
+        byte_pitch] -- so frames and PCM in rings or in a wide capture buffer are read and written in place.  pcm_elems / out_bytes: the
+        buffers' extents (default: the tensors' sizes); every view is checked against them on the host and a call that would leave them
+        is refused with LC3GPU_ELENGTH.  Asynchronous on `stream` (lc3gpu_encode_mixed_views)"""
+        v = _view_list(views)
+        pe = _numel(d_pcm, "pcm_elems") if pcm_elems is None else int(pcm_elems)
+        ob = _numel(d_out, "out_bytes") if out_bytes is None else int(out_bytes)
+        rc = self._L.lc3gpu_encode_mixed_views(self._h, _ptr(v), int(v.shape[0]), _ptr(d_pcm), pe, _ptr(d_out), ob, _ptr(stream))
+        if rc:
+            raise Lc3EncoderError(rc, "encode_mixed_views")
 
     def reset(self, channels=None):
         """every channel (channels=None) or the named ones back to the freshly constructed state from their next call on; no wait"""
@@ -930,6 +989,19 @@ class Lc3Decoder:
         rc = self._L.lc3gpu_decode_mixed_mc_items(self._h, _ptr(it), int(it.shape[0]), _ptr(d_in), _ptr(d_bad_frame), _ptr(d_pcm), _ptr(stream))
         if rc:
             raise Lc3DecoderError(rc, "decode_mixed_mc_items")
+
+    def decode_mixed_views(self, views, d_in, d_pcm, stream=None, d_bad_frame=None, in_bytes=None, pcm_elems=None, n_flags=None):
+        """a mixed handle's batch over views, as Lc3Encoder.encode_mixed_views: frame t's bytes at d_in[byte_off + t * byte_pitch], its flag
+        at d_bad_frame[flag_off + t * flag_pitch] (when given), its samples written to d_pcm[pcm_off + t * pcm_pitch + n * pcm_stride] and
+        nothing else; frame sizes 1..400 (lc3gpu_decode_mixed_views)"""
+        v = _view_list(views)
+        ib = _numel(d_in, "in_bytes") if in_bytes is None else int(in_bytes)
+        pe = _numel(d_pcm, "pcm_elems") if pcm_elems is None else int(pcm_elems)
+        nfl = 0 if d_bad_frame is None else (_numel(d_bad_frame, "n_flags") if n_flags is None else int(n_flags))
+        rc = self._L.lc3gpu_decode_mixed_views(self._h, _ptr(v), int(v.shape[0]), _ptr(d_in), ib, _ptr(d_bad_frame), nfl, _ptr(d_pcm), pe,
+                                               _ptr(stream))
+        if rc:
+            raise Lc3DecoderError(rc, "decode_mixed_views")
 
     def reset(self, channels=None):
         """every channel (channels=None) or the named ones back to the freshly constructed state (PLC count 0) from their next call on; no wait"""

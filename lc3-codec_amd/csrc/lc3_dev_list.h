@@ -135,4 +135,54 @@ __device__ __forceinline__ void lc3_list_synth_stream_mc(LC3_CFG_PARAM, lc3_dec_
     if (valid) lc3_dec_state_store(c, L, lane, gst);
 }
 
+// ---- a stream whose frames lie where the caller says (lc3gpu_*_mixed_views) ---------------------------------------------------------------
+// pcm_s = sample 0 of frame 0; sample n of frame t is pcm_s[t * pitch + n * stride]: stride as above, pitch >= nf * stride the elements
+// from one frame to the next (ring slots, a capture buffer wider than the stream), both per-stream data read with the list entry and
+// wave-uniform.  The frames of a stream need not be contiguous, so the MDCT history of frame t > 0 is taken from where frame t - 1 LIES:
+// its samples z .. nf-1, at prev + z * stride -- not from frame - (nf - z) * stride, which is the gap in front of the frame.  Only a
+// frame's own nf samples are read (written); what lies between the frames is never touched.
+// Barrier rule: the four streams of a workgroup may differ in stride AND pitch.  The stride selects a load (store) sequence as above; the
+// pitch is an address term of the frame pointer and nothing else: no gathered block, no table staging and no prologue hook depends on it.
+// Ring rule: unchanged -- freshness and the ring flags are the stream's own, the pitch moves only where lc3_decode_frame_wave stores.
+// stride == 1 keeps the 32-bit path: the host admits only even pcm_off and even pitch there, so every frame starts on a 4-byte boundary.
+LC3_CFG_TEMPLATE __device__ __forceinline__ void lc3_list_front_stream_view(LC3_CFG_PARAM, lc3_enc_lds &L, int lane, lc3_enc_state *gst, int fresh,
+                                                                           int valid, const int16_t *pcm_s, int stride, int pitch, float *mid,
+                                                                           int32_t *planes, size_t fbase, int nbytes, int n_frames, int spec_flags,
+                                                                           int outline_ltpf) {
+    LC3_CFG_BIND;
+    const int z = c.z;
+    if (lane == 0) L.spec_flags = spec_flags;
+    if (LC3_UNIFORM_I32(fresh)) lc3_enc_state_init(L, lane, gst, valid);  // (wave-level fences only: see the barrier rule)
+    else lc3_enc_state_load(L, lane, gst);
+    for (int t = 0; t < n_frames; t++) {
+        const size_t f = fbase + (size_t)t;
+        int32_t *plane = valid ? LC3_PLANE_COL(planes, f, EP_WORDS) : nullptr;
+        float *mcol = valid ? mid + f * (size_t)MP_WORDS : nullptr;
+        const int16_t *frame = pcm_s + (size_t)t * (size_t)pitch;
+        // the history inside the call is the tail of the previous frame where that frame lies; the state blob's copy is planar
+        const int16_t *hist =
+            t > 0 ? pcm_s + (size_t)(t - 1) * (size_t)pitch + (size_t)z * (size_t)stride : (fresh ? nullptr : gst->hist);
+        lc3_encode_front_wave(LC3_CFG_PASS, L, lane, frame, hist, gst, mcol, plane, LC3_PLANE_STRIDE, nbytes, nullptr, stride, t > 0 ? stride : 1,
+                              (t % LC3_WG_WAVES) + (t + 2 < n_frames ? 0x100 : 0), outline_ltpf);
+    }
+    if (valid) lc3_enc_state_store(c, L, lane, gst, n_frames > 0 ? pcm_s + (size_t)(n_frames - 1) * (size_t)pitch : nullptr, stride);
+}
+
+LC3_CFG_TEMPLATE_AND(class TABLES = lc3_no_prologue)
+__device__ __forceinline__ void lc3_list_synth_stream_view(LC3_CFG_PARAM, lc3_dec_lds &L, int lane, lc3_dec_state *gst, int fresh, int valid,
+                                                           int nbytes, const int32_t *planes, size_t fbase, int n_frames, int16_t *pcm_s, int stride,
+                                                           int pitch, int late, TABLES tables = TABLES()) {
+    LC3_CFG_BIND;
+    lc3_i4 st_regs = {0, 0, 0, 0};
+    if (!LC3_UNIFORM_I32(fresh)) st_regs = lc3_dec_state_issue(lane, gst);
+    lc3_decode_stream_wave(LC3_CFG_PASS, L, lane, nbytes, planes, fbase, n_frames, gst, valid, pcm_s, (size_t)pitch, stride, late, nullptr, 0,
+                           [&]() {
+                               tables();
+                               if (LC3_UNIFORM_I32(fresh)) lc3_dec_state_init(L, lane, gst, valid);  // (see the ring rule)
+                               else lc3_dec_state_commit(L, lane, st_regs);
+                           },
+                           fresh);
+    if (valid) lc3_dec_state_store(c, L, lane, gst);
+}
+
 #endif  // LC3_DEV_LIST_H_

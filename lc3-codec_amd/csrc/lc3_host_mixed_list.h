@@ -140,9 +140,11 @@ struct lc3_mitems_plan {
 #define LC3_MITEMS_MAX_NBYTES 400
 
 // items: already checked (channel in range and not twice, n_frames >= 1, nbytes 0 or in range).  fresh: per INTERNAL index.
-// pos_of: when given, item i's launch position.
-static inline void lc3_mitems_build(const lc3_mlist_group *groups, const lc3_mlist_stream *streams, const uint8_t *fresh, const lc3_mitem *items,
-                                    int n_items, int32_t *entries, lc3_stream_io *tab, lc3_mitems_plan &P, int *pos_of = nullptr) {
+// pos_of: when given, item i's launch position.  ITEM: anything with the fields channel, n_frames, nbytes -- lc3_mitem, or the view of a
+// views call (lc3_mview below), which is bucketed as it lies in the caller's array; tab: may be null there (a views call has rows of its own).
+template <class ITEM>
+static inline void lc3_mitems_build_of(const lc3_mlist_group *groups, const lc3_mlist_stream *streams, const uint8_t *fresh, const ITEM *items,
+                                       int n_items, int32_t *entries, lc3_stream_io *tab, lc3_mitems_plan &P, int *pos_of) {
     P.buckets.clear();
     P.cell.assign((size_t)LC3_MITEMS_SLOTS * (LC3_MITEMS_MAX_NBYTES + 1), -1);
     P.bucket_of.resize((size_t)n_items);
@@ -194,15 +196,21 @@ static inline void lc3_mitems_build(const lc3_mlist_group *groups, const lc3_mli
         const lc3_mitems_bucket &b = P.buckets[(size_t)r];
         const int p = next[(size_t)r]++;  // (stable: the list's order inside a bucket)
         entries[p] = (int32_t)((uint32_t)st.internal | (fresh[st.internal] ? 0x80000000u : 0u));
-        tab[p].pcm_off1 = po;
-        tab[p].byte_off1 = bo;
-        tab[p].flag_idx = (int)fo;
-        tab[p].pad = 0;
-        if (pos_of) pos_of[i] = p;  // (lc3_mcitems_build: the item's launch position)
+        if (tab) {
+            tab[p].pcm_off1 = po;
+            tab[p].byte_off1 = bo;
+            tab[p].flag_idx = (int)fo;
+            tab[p].pad = 0;
+        }
+        if (pos_of) pos_of[i] = p;  // (lc3_mcitems_build, lc3_mviews_build: the item's launch position)
         po += (long long)b.n_frames * (long long)groups[b.group].nf;
         bo += (long long)b.n_frames * (long long)b.nbytes;
         fo += b.n_frames;
     }
+}
+static inline void lc3_mitems_build(const lc3_mlist_group *groups, const lc3_mlist_stream *streams, const uint8_t *fresh, const lc3_mitem *items,
+                                    int n_items, int32_t *entries, lc3_stream_io *tab, lc3_mitems_plan &P, int *pos_of = nullptr) {
+    lc3_mitems_build_of(groups, streams, fresh, items, n_items, entries, tab, P, pos_of);
 }
 
 // ---- items of several channels in WAV sample order (lc3gpu_encode_mixed_mc_items / lc3gpu_decode_mixed_mc_items) ------------------------
@@ -253,6 +261,99 @@ static inline void lc3_mcitems_build(const lc3_mlist_group *groups, const lc3_ml
         po += (long long)T * (long long)nf * (long long)C;
         bo += (long long)T * (long long)C * (long long)nb;
         fo += (long long)T * (long long)C;
+    }
+}
+
+// ---- every item with a placement of its own (lc3gpu_encode_mixed_views / lc3gpu_decode_mixed_views) --------------------------------------
+// A view is an item (channel, n_frames, nbytes) that also says WHERE its data lies: sample n of frame t at element
+// pcm_off + t * pcm_pitch + n * pcm_stride, frame t's bytes at byte_off + t * byte_pitch, its flag at flag_off + t * flag_pitch.  One
+// descriptor covers the compact items layout (stride 1, pitches 0 = the defaults), one channel of an mc item (stride C, pitches C * nf,
+// C * nbytes, C), a slot ring and a sub-channel of a wide capture buffer.  Buckets, launch positions, launch sets and rows are those of an
+// items call over the views' (channel, n_frames, nbytes): placement is no part of the key.  What differs is the per-stream device row:
+//   rows[pos]      lc3_view_io: the three offsets, the stride and the three RESOLVED pitches (the 0 = default of the caller's view is
+//                  filled in here, so the kernels test nothing).  A row type of its own: lc3_stream_io is read by every other kernel
+// With caller-given offsets the extent check (lc3_mviews_check) is the only thing between a typo and a stray access on the device: it
+// runs before the plan is built, in unsigned 64-bit arithmetic that cannot overflow, and a refused call builds and sends nothing.
+struct lc3_mview {  // = lc3gpu_view (include/lc3gpu.h)
+    int32_t channel, n_frames, nbytes, pcm_stride;
+    int64_t pcm_off, byte_off, flag_off;
+    int32_t pcm_pitch, byte_pitch, flag_pitch;
+    int32_t reserved[3];
+};
+struct lc3_view_io {
+    long long pcm_off, byte_off, flag_off;  // elements, bytes, flags: frame 0 of the stream in the caller's buffers
+    int stride;                             // elements between two samples of a frame (1: the 32-bit PCM path; >= 2: the 16-bit one)
+    int pcm_pitch, byte_pitch, flag_pitch;  // from frame t to frame t + 1, resolved (never 0)
+};
+#define LC3_MVIEWS_MAX_STRIDE 8
+// what lc3_mviews_check returns: the values of LC3GPU_OK / LC3GPU_EINVAL / LC3GPU_ECHANNEL / LC3GPU_ELENGTH (include/lc3gpu.h)
+enum { LC3_MVIEWS_OK = 0, LC3_MVIEWS_EINVAL = -1, LC3_MVIEWS_ECHANNEL = -2, LC3_MVIEWS_ELENGTH = -3 };
+// the caller's buffers: the PCM base ADDRESS (its alignment is checked, nothing is read), the element / byte / flag counts the views must
+// stay inside, whether flags are read at all (a decoder with d_bad_frame), and the smallest frame size (20 encoder, 1 decoder)
+struct lc3_mviews_bounds {
+    uint64_t pcm_base, pcm_elems, io_bytes, n_flags;
+    int use_flags, min_bytes;
+};
+// [off, off + (T - 1) * pitch + last] inside [0, size): T < 2^31 and pitch < 2^31, so the span stays below 2^62 + 2^31 and no step wraps
+static inline bool lc3_mviews_inside(int64_t off, int T, int pitch, uint64_t last, uint64_t size) {
+    if ((uint64_t)off >= size) return false;  // (off >= 0: checked by the caller)
+    const uint64_t span = (uint64_t)(T - 1) * (uint64_t)pitch + last;
+    return span < size - (uint64_t)off;
+}
+// Every check of a views call but the handle's own (null pointers, uniform handle, bound stream).  seen / call: per channel the number of
+// the call that named it last, and this call's number (the repeated-channel check of the list calls).  frames / max_frames: the call's
+// total and its largest per-view count.  Nothing is written but seen[].
+static inline int lc3_mviews_check(const lc3_mlist_group *groups, const lc3_mlist_stream *streams, int n_channels, const lc3_mview *views,
+                                   int n_views, const lc3_mviews_bounds &B, uint32_t *seen, uint32_t call, size_t *frames, int *max_frames) {
+    uint64_t total = 0;
+    int most = 0;
+    for (int i = 0; i < n_views; i++) {
+        const lc3_mview &v = views[i];
+        if (v.channel < 0 || v.channel >= n_channels || seen[v.channel] == call) return LC3_MVIEWS_ECHANNEL;
+        seen[v.channel] = call;
+        if (v.n_frames < 1) return LC3_MVIEWS_ELENGTH;
+        if (v.nbytes != 0 && (v.nbytes < B.min_bytes || v.nbytes > LC3_MITEMS_MAX_NBYTES)) return LC3_MVIEWS_ELENGTH;
+        if (v.reserved[0] != 0 || v.reserved[1] != 0 || v.reserved[2] != 0) return LC3_MVIEWS_EINVAL;
+        if (v.pcm_stride < 1 || v.pcm_stride > LC3_MVIEWS_MAX_STRIDE) return LC3_MVIEWS_EINVAL;
+        if (v.pcm_off < 0 || v.byte_off < 0 || (B.use_flags && v.flag_off < 0)) return LC3_MVIEWS_EINVAL;
+        const lc3_mlist_group &g = groups[streams[v.channel].group];
+        const int nbytes = v.nbytes ? v.nbytes : g.nbytes, min_pitch = g.nf * v.pcm_stride;  // (<= 480 * 8)
+        if (v.pcm_pitch != 0 && v.pcm_pitch < min_pitch) return LC3_MVIEWS_EINVAL;
+        if (v.byte_pitch != 0 && v.byte_pitch < nbytes) return LC3_MVIEWS_EINVAL;
+        if (B.use_flags && v.flag_pitch < 0) return LC3_MVIEWS_EINVAL;
+        if (v.pcm_stride == 1) {  // the 32-bit path: every frame's first sample on a 4-byte boundary
+            if ((v.pcm_off & 1) != 0 || (v.pcm_pitch & 1) != 0 || (B.pcm_base & 3u) != 0) return LC3_MVIEWS_EINVAL;
+        } else if ((B.pcm_base & 1u) != 0) return LC3_MVIEWS_EINVAL;
+        const int pp = v.pcm_pitch ? v.pcm_pitch : min_pitch, bp = v.byte_pitch ? v.byte_pitch : nbytes, fp = v.flag_pitch ? v.flag_pitch : 1;
+        if (!lc3_mviews_inside(v.pcm_off, v.n_frames, pp, (uint64_t)(g.nf - 1) * (uint64_t)v.pcm_stride, B.pcm_elems)) return LC3_MVIEWS_ELENGTH;
+        if (!lc3_mviews_inside(v.byte_off, v.n_frames, bp, (uint64_t)(nbytes - 1), B.io_bytes)) return LC3_MVIEWS_ELENGTH;
+        if (B.use_flags && !lc3_mviews_inside(v.flag_off, v.n_frames, fp, 0, B.n_flags)) return LC3_MVIEWS_ELENGTH;
+        total += (uint64_t)v.n_frames;
+        if (total > (uint64_t)0x7fffffff) return LC3_MVIEWS_ELENGTH;  // (frame counts are 32-bit on the device)
+        if (v.n_frames > most) most = v.n_frames;
+    }
+    *frames = (size_t)total;
+    *max_frames = most;
+    return LC3_MVIEWS_OK;
+}
+// views: already checked (lc3_mviews_check).  entries / rows: one per view, in launch order.  fresh: per INTERNAL index.  use_flags == 0
+// (no flags are read): the rows' flag fields are 0 / 1 whatever the views hold
+static inline void lc3_mviews_build(const lc3_mlist_group *groups, const lc3_mlist_stream *streams, const uint8_t *fresh, const lc3_mview *views,
+                                    int n_views, int use_flags, int32_t *entries, lc3_view_io *rows, lc3_mitems_plan &P) {
+    // buckets and launch positions are the items plan's over the views as they lie (no copy of the list, no compact offsets)
+    P.pos_of.resize((size_t)n_views);
+    lc3_mitems_build_of(groups, streams, fresh, views, n_views, entries, (lc3_stream_io *)nullptr, P, P.pos_of.data());
+    for (int i = 0; i < n_views; i++) {
+        const lc3_mview &v = views[i];
+        const lc3_mlist_group &g = groups[streams[v.channel].group];
+        lc3_view_io &r = rows[P.pos_of[(size_t)i]];
+        r.pcm_off = v.pcm_off;
+        r.byte_off = v.byte_off;
+        r.flag_off = use_flags ? v.flag_off : 0;
+        r.stride = v.pcm_stride;
+        r.pcm_pitch = v.pcm_pitch ? v.pcm_pitch : g.nf * v.pcm_stride;
+        r.byte_pitch = v.byte_pitch ? v.byte_pitch : (v.nbytes ? v.nbytes : g.nbytes);
+        r.flag_pitch = (use_flags && v.flag_pitch) ? v.flag_pitch : 1;
     }
 }
 

@@ -80,6 +80,8 @@
 #define LC3_IN_ITEMS_TU(k) LC3_IN_MIXED_LIST_TU(k)
 // the seven mc twins (lc3gpu_*_mixed_mc_items: front half, packers, parsers, synthesis forms), each beside the items kernel it is a twin of
 #define LC3_IN_MC_ITEMS_TU(k) LC3_IN_MIXED_LIST_TU(k)
+// the seven view twins (lc3gpu_*_mixed_views: the same seven kernels once more), each beside the mc kernel it is a twin of
+#define LC3_IN_VIEWS_TU(k) LC3_IN_MIXED_LIST_TU(k)
 #define LC3_CAT_(a, b) a##b
 #define LC3_CAT(a, b) LC3_CAT_(a, b)
 
@@ -596,9 +598,15 @@ __device__ __forceinline__ size_t lc3_io_flag_idx(const lc3_io &io, int first, s
 
 // The lane-per-frame bodies' compile-time IOABS switch: 0 = the table's offsets count per frame of the launch (times T), 1 = absolute (an
 // items call), 2 = absolute with the stream's channel count C in the row's spare word (an mc-items call): frame t of the stream has its
-// bytes at byte_off1 + t * C * nbytes and its flag at flag_idx + t * C
+// bytes at byte_off1 + t * C * nbytes and its flag at flag_idx + t * C, 3 = a views call: io.tab is the address of the call's lc3_view_io
+// rows (lc3_io_views; lc3_host_mixed_list.h), frame t has its bytes at byte_off + t * byte_pitch and its flag at flag_off + t * flag_pitch
+__device__ __forceinline__ const lc3_view_io *lc3_io_views(const lc3_io &io) { return (const lc3_view_io *)(const void *)io.tab; }
 template <int IOABS>
 __device__ __forceinline__ size_t lc3_io_byte_off_abs(const lc3_io &io, int nbytes, int first, size_t s, size_t t, int T) {
+    if (IOABS == 3) {
+        const lc3_view_io &r = lc3_io_views(io)[(size_t)first + s];
+        return (size_t)r.byte_off + t * (size_t)r.byte_pitch;
+    }
     if (IOABS == 2) {
         const lc3_stream_io &r = io.tab[(size_t)first + s];
         return (size_t)r.byte_off1 + t * (size_t)r.pad * (size_t)nbytes;
@@ -607,6 +615,10 @@ __device__ __forceinline__ size_t lc3_io_byte_off_abs(const lc3_io &io, int nbyt
 }
 template <int IOABS>
 __device__ __forceinline__ size_t lc3_io_flag_idx_abs(const lc3_io &io, int first, size_t s, size_t t, int T) {
+    if (IOABS == 3) {
+        const lc3_view_io &r = lc3_io_views(io)[(size_t)first + s];
+        return (size_t)r.flag_off + t * (size_t)r.flag_pitch;
+    }
     if (IOABS == 2) {
         const lc3_stream_io &r = io.tab[(size_t)first + s];
         return (size_t)r.flag_idx + t * (size_t)r.pad;
@@ -861,6 +873,49 @@ __global__ __launch_bounds__(64 * LC3_WG_WAVES, LC3_FRONT_WAVES) void LC3_MIXED_
 #endif
 #if LC3_MULTI_TU && LC3_TU_KIND == 0
 __global__ __launch_bounds__(64 * LC3_WG_WAVES, LC3_FRONT_WAVES) void lc3_enc_front_mc_items_kernel_all(
+    lc3_groups G, lc3_enc_state *states, const int32_t *entries, const int16_t *pcm, float *mid, int32_t *planes, lc3_io io, int spec_flags);
+#endif
+
+// ---- views: a listed stream's frames lie where the caller says (lc3gpu_*_mixed_views; lc3_mviews_build) ---------------------------------
+// Twins of the seven mc kernels.  io.tab carries the address of the call's lc3_view_io rows (lc3_io_views): launch position p has its
+// first sample / first frame / first flag, the sample stride and the three frame pitches, all resolved on the host.  Stride and pitch
+// are per-stream data, read as the list entry is; the four streams of a workgroup may differ in both.  Barrier rule: stride picks the
+// load / store sequence, the pitch is a term of the frame's address, nothing else (lc3_dev_list.h); rows, buckets and frame counts are
+// the items call's.  Every address a kernel forms lies inside the extents the host checked before the call was queued.
+template <class CV>
+__device__ __forceinline__ void lc3_enc_front_body_views(lc3_cfg_slot<CV> cfg, unsigned wg, lc3_enc_state *states, const int32_t *entries,
+                                                         int first_pos, int n_streams, const int16_t *pcm, float *mid, int32_t *planes,
+                                                         int nbytes, int n_frames, const lc3_view_io *rows, int spec_flags) {
+    const int lane = threadIdx.x & 63, wave = LC3_WAVE_ID();
+    lc3_enc_lds &L = lc3_enc_wg[wave];
+    const int s_raw = (int)wg * LC3_WG_WAVES + wave;
+    const int valid = s_raw < n_streams;
+    const int s = valid ? s_raw : n_streams - 1;  // (a shadow wave stays inside its own row)
+    typename CV::bind_t c0 = CV::bind(lc3_cfg_table[cfg.id]);
+    const int entry = lc3_list_entry(entries, first_pos + s);
+    lc3_enc_state *gst = states + (size_t)lc3_list_channel(entry);
+    const lc3_view_io *row = rows + (first_pos + s);
+    const int16_t *pcm_s = pcm + (size_t)lc3_mlist_off(&row->pcm_off);
+    const int stride = lc3_list_entry(&row->stride, 0), pitch = lc3_list_entry(&row->pcm_pitch, 0);
+#ifndef LC3_TABLES_IN_GLOBAL
+    lc3_front_tables_stage_image(c0.stage_image);
+    lc3_fft_tables_stage_image(c0.stage_image);  // ends with the workgroup barrier
+#endif
+    lc3_list_front_stream_view(cfg, L, lane, gst, lc3_list_fresh(entry), valid, pcm_s, stride, pitch, mid, planes, (size_t)s * (size_t)n_frames,
+                               nbytes, n_frames, spec_flags, 1);
+}
+#if LC3_IN_VIEWS_TU(0)
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, LC3_FRONT_WAVES) void LC3_MIXED_KERNEL(lc3_enc_front_view_items_kernel)(
+    lc3_groups G, lc3_enc_state *states, const int32_t *entries, const int16_t *pcm, float *mid, int32_t *planes, lc3_io io, int spec_flags) {
+    const lc3_group &g = G.g[lc3_find_group(G, blockIdx.x, 0)];
+    float *m = mid + (size_t)g.frame_base * (size_t)MP_WORDS;
+    int32_t *p = planes + (size_t)g.frame_base * (size_t)EP_WORDS;
+    LC3_GROUP_VIEW_LIST(lc3_enc_front_body_views, g, blockIdx.x - g.wg_stream, states, entries, g.first_stream, g.n_streams, pcm, m, p, g.nbytes,
+                        g.n_frames, lc3_io_views(io), spec_flags);
+}
+#endif
+#if LC3_MULTI_TU && LC3_TU_KIND == 0
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, LC3_FRONT_WAVES) void lc3_enc_front_view_items_kernel_all(
     lc3_groups G, lc3_enc_state *states, const int32_t *entries, const int16_t *pcm, float *mid, int32_t *planes, lc3_io io, int spec_flags);
 #endif
 
@@ -1136,6 +1191,17 @@ __global__ __launch_bounds__(256) void LC3_MIXED_KERNEL(lc3_pack_mc_items_kernel
 #endif
 #if LC3_MULTI_TU && LC3_TU_KIND == 0
 __global__ __launch_bounds__(256) void lc3_pack_mc_items_kernel_all(lc3_groups G, const int32_t *planes, uint8_t *out, lc3_io io);
+#endif
+// ... of a views call: frame (s, t) goes to byte_off + t * byte_pitch of the stream's row (IOABS 3; see lc3_enc_front_view_items_kernel)
+#if LC3_IN_VIEWS_TU(1)
+__global__ __launch_bounds__(256) void LC3_MIXED_KERNEL(lc3_pack_view_items_kernel)(lc3_groups G, const int32_t *planes, uint8_t *out, lc3_io io) {
+    const lc3_group &g = G.g[lc3_find_group(G, blockIdx.x, 1)];
+    lc3_pack_body<3>(blockIdx.x - g.wg_frame, g.ne, planes + (size_t)g.frame_base * (size_t)EP_WORDS, out, g.nbytes, g.n_streams * g.n_frames,
+                     g.n_frames, g.first_stream, io);
+}
+#endif
+#if LC3_MULTI_TU && LC3_TU_KIND == 0
+__global__ __launch_bounds__(256) void lc3_pack_view_items_kernel_all(lc3_groups G, const int32_t *planes, uint8_t *out, lc3_io io);
 #endif
 
 // ---- a frame size per frame (lc3gpu_encode_vbr; lc3_dev_enc_vbr.h) ----------------------------------------------------------------------
@@ -1450,6 +1516,18 @@ __global__ __launch_bounds__(512) void LC3_MIXED_KERNEL(lc3_pack_pc_mc_items_ker
 __global__ __launch_bounds__(512) void lc3_pack_pc_mc_items_kernel_all(lc3_groups G, const int32_t *planes, uint8_t *out, lc3_io io,
                                                                        unsigned *pc_timeouts);
 #endif
+#if LC3_IN_VIEWS_TU(1)
+__global__ __launch_bounds__(512) void LC3_MIXED_KERNEL(lc3_pack_pc_view_items_kernel)(lc3_groups G, const int32_t *planes, uint8_t *out, lc3_io io,
+                                                                                  unsigned *pc_timeouts) {
+    const lc3_group &g = G.g[lc3_find_group(G, blockIdx.x, 1)];
+    lc3_pack_pc_body<3>(blockIdx.x - g.wg_frame, g.ne, planes + (size_t)g.frame_base * (size_t)EP_WORDS, out, g.nbytes, g.n_streams * g.n_frames,
+                        g.n_frames, g.first_stream, io, pc_timeouts);
+}
+#endif
+#if LC3_MULTI_TU && LC3_TU_KIND == 0
+__global__ __launch_bounds__(512) void lc3_pack_pc_view_items_kernel_all(lc3_groups G, const int32_t *planes, uint8_t *out, lc3_io io,
+                                                                    unsigned *pc_timeouts);
+#endif
 
 // The packer's symbols as a stage of its own (lc3_enc_symbols_frame, lc3_dev_enc.h): one WAVE per frame.  A workgroup stages the
 // context lookup table once (lc3_spec_tab) and walks frames wg * 4 + wave, + 4 * gridDim.x, ...; eight waves per SIMD.  Selectable
@@ -1638,6 +1716,29 @@ __global__ __launch_bounds__(256) void LC3_MIXED_KERNEL(lc3_parse_mc_items_kerne
 __global__ __launch_bounds__(256) void lc3_parse_mc_items_kernel_all(lc3_groups G, const uint8_t *in, const uint8_t *bad, int32_t *planes, lc3_io io,
                                                                      int late);
 #endif
+// ... of a views call: frame (s, t) comes from byte_off + t * byte_pitch, its flag from flag_off + t * flag_pitch (IOABS 3).  The switch
+// names the body itself, as in lc3_parse_items_kernel
+#if LC3_IN_VIEWS_TU(2)
+__global__ __launch_bounds__(256) void LC3_MIXED_KERNEL(lc3_parse_view_items_kernel)(lc3_groups G, const uint8_t *in, const uint8_t *bad, int32_t *planes,
+                                                                                lc3_io io, int late) {
+    const lc3_group &g = G.g[lc3_find_group(G, blockIdx.x, 1)];
+    int32_t *p = planes + (size_t)g.frame_base * (size_t)LC3_PLANE_WORDS;
+    const int T = LC3_UNIFORM_I32(g.n_frames), nfr = LC3_UNIFORM_I32(g.n_streams) * T;  // (the row's words are workgroup-uniform)
+    switch (g.fixed) {
+#define LC3_X(i, V) \
+    case i: lc3_parse_body<V, 3>(lc3_cfg_slot<V>{g.slot}, blockIdx.x - g.wg_frame, in, bad, p, g.nbytes, nfr, T, g.first_stream, io, late); break;
+        LC3_FOR_EACH_VIEW(LC3_X)
+#undef LC3_X
+    default:
+        lc3_parse_body<lc3_cfg_any, 3>(lc3_cfg_slot<lc3_cfg_any>{g.slot}, blockIdx.x - g.wg_frame, in, bad, p, g.nbytes, nfr, T, g.first_stream, io, late);
+        break;
+    }
+}
+#endif
+#if LC3_MULTI_TU && LC3_TU_KIND == 0
+__global__ __launch_bounds__(256) void lc3_parse_view_items_kernel_all(lc3_groups G, const uint8_t *in, const uint8_t *bad, int32_t *planes, lc3_io io,
+                                                                  int late);
+#endif
 
 // The parser of a full batch as PRODUCER / CONSUMER wave pairs (lc3_pc_produce / lc3_pc_consume, lc3_dev_dec_parse.h): a workgroup of
 // 2 x fpb threads parses fpb frames; wave w of its first half runs the range decoder's recurrence for 64 frames, wave w of the second half
@@ -1799,6 +1900,24 @@ __global__ __launch_bounds__(512) void LC3_MIXED_KERNEL(lc3_parse_pc_mc_items_ke
 #if LC3_MULTI_TU && LC3_TU_KIND == 0
 __global__ __launch_bounds__(512) void lc3_parse_pc_mc_items_kernel_all(lc3_groups G, const uint8_t *in, const uint8_t *bad, int32_t *planes, lc3_io io,
                                                                         unsigned *pc_timeouts);
+#endif
+template <class CV>
+__device__ __forceinline__ void lc3_parse_pc_body_views(lc3_cfg_slot<CV> cfg, unsigned wg, const uint8_t *in, const uint8_t *bad, int32_t *planes,
+                                                        int nbytes, int n_frames, int T, int first_pos, lc3_io io, unsigned *pc_timeouts) {
+    lc3_parse_pc_body<CV, 3>(cfg, wg, in, bad, planes, nbytes, n_frames, T, first_pos, io, pc_timeouts);
+}
+#if LC3_IN_VIEWS_TU(3)
+__global__ __launch_bounds__(512) void LC3_MIXED_KERNEL(lc3_parse_pc_view_items_kernel)(lc3_groups G, const uint8_t *in, const uint8_t *bad,
+                                                                                   int32_t *planes, lc3_io io, unsigned *pc_timeouts) {
+    const lc3_group &g = G.g[lc3_find_group(G, blockIdx.x, 1)];
+    int32_t *p = planes + (size_t)g.frame_base * (size_t)LC3_PLANE_WORDS;
+    LC3_GROUP_VIEW_LIST(lc3_parse_pc_body_views, g, blockIdx.x - g.wg_frame, in, bad, p, g.nbytes, g.n_streams * g.n_frames, g.n_frames,
+                        g.first_stream, io, pc_timeouts);
+}
+#endif
+#if LC3_MULTI_TU && LC3_TU_KIND == 0
+__global__ __launch_bounds__(512) void lc3_parse_pc_view_items_kernel_all(lc3_groups G, const uint8_t *in, const uint8_t *bad, int32_t *planes, lc3_io io,
+                                                                     unsigned *pc_timeouts);
 #endif
 
 // Spectrum reconstruction D4-D8 of a full batch (lc3_dev_dec_recon.h), between the parser and the synthesis kernel:
@@ -2164,6 +2283,70 @@ __global__ __launch_bounds__(64 * LC3_WG_WAVES, 4) void lc3_decode_mc_items_kern
 __global__ __launch_bounds__(64 * LC3_WG_WAVES, 4) void lc3_decode_mc_items_late_kernel_all(lc3_groups G, lc3_dec_state *states,
                                                                                         const int32_t *entries, const int32_t *planes,
                                                                                         int16_t *pcm, lc3_io io);
+#endif
+// ... of a views call: the stream's samples `stride` elements apart, its frames `pcm_pitch` (see lc3_enc_front_view_items_kernel)
+template <class CV, int LATE>
+__device__ __forceinline__ void lc3_decode_body_views(lc3_cfg_slot<CV> cfg, unsigned wg, lc3_dec_state *states, const int32_t *entries,
+                                                      int first_pos, int n_streams, const int32_t *planes, int16_t *pcm, int nbytes, int n_frames,
+                                                      const lc3_view_io *rows) {
+    const int lane = threadIdx.x & 63, wave = LC3_WAVE_ID();
+    lc3_dec_lds &L = lc3_dec_wg[wave];
+    const int s_raw = (int)wg * LC3_WG_WAVES + wave;
+    const int valid = s_raw < n_streams;
+    const int s = valid ? s_raw : n_streams - 1;  // (a shadow wave stays inside its own row)
+    typename CV::bind_t c0 = CV::bind(lc3_cfg_table[cfg.id]);
+    const int entry = lc3_list_entry(entries, first_pos + s);
+    lc3_dec_state *gst = states + (size_t)lc3_list_channel(entry);
+    const lc3_view_io *row = rows + (first_pos + s);
+    int16_t *pcm_s = pcm + (size_t)lc3_mlist_off(&row->pcm_off);
+    const int stride = lc3_list_entry(&row->stride, 0), pitch = lc3_list_entry(&row->pcm_pitch, 0);
+#ifndef LC3_TABLES_IN_GLOBAL
+    const lc3_fft_image_regs tab_regs = lc3_fft_tables_image_issue(c0.stage_image);
+#endif
+    lc3_list_synth_stream_view(cfg, L, lane, gst, lc3_list_fresh(entry), valid, nbytes, planes, (size_t)s * (size_t)n_frames, n_frames, pcm_s,
+                               stride, pitch, LATE, [&]() {
+#ifndef LC3_TABLES_IN_GLOBAL
+                                   lc3_fft_tables_image_commit(tab_regs);
+#endif
+                               });
+}
+template <class CV>
+__device__ __forceinline__ void lc3_decode_body_views_now(lc3_cfg_slot<CV> cfg, unsigned wg, lc3_dec_state *states, const int32_t *entries,
+                                                          int first_pos, int n_streams, const int32_t *planes, int16_t *pcm, int nbytes,
+                                                          int n_frames, const lc3_view_io *rows) {
+    lc3_decode_body_views<CV, 0>(cfg, wg, states, entries, first_pos, n_streams, planes, pcm, nbytes, n_frames, rows);
+}
+template <class CV>
+__device__ __forceinline__ void lc3_decode_body_views_late(lc3_cfg_slot<CV> cfg, unsigned wg, lc3_dec_state *states, const int32_t *entries,
+                                                           int first_pos, int n_streams, const int32_t *planes, int16_t *pcm, int nbytes,
+                                                           int n_frames, const lc3_view_io *rows) {
+    lc3_decode_body_views<CV, 1>(cfg, wg, states, entries, first_pos, n_streams, planes, pcm, nbytes, n_frames, rows);
+}
+#if LC3_IN_VIEWS_TU(4)
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, 4) void LC3_MIXED_KERNEL(lc3_decode_view_items_kernel)(lc3_groups G, lc3_dec_state *states,
+                                                                                const int32_t *entries, const int32_t *planes,
+                                                                                int16_t *pcm, lc3_io io) {
+    const lc3_group &g = G.g[lc3_find_group(G, blockIdx.x, 0)];
+    const int32_t *p = planes + (size_t)g.frame_base * (size_t)LC3_PLANE_WORDS;
+    LC3_GROUP_VIEW_LIST(lc3_decode_body_views_now, g, blockIdx.x - g.wg_stream, states, entries, g.first_stream, g.n_streams, p, pcm, g.nbytes,
+                        g.n_frames, lc3_io_views(io));
+}
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, 4) void LC3_MIXED_KERNEL(lc3_decode_view_items_late_kernel)(lc3_groups G, lc3_dec_state *states,
+                                                                                     const int32_t *entries, const int32_t *planes,
+                                                                                     int16_t *pcm, lc3_io io) {
+    asm volatile("" : "+s"(states), "+s"(entries), "+s"(planes), "+s"(pcm));  // (as in lc3_decode_mc_items_late_kernel: no scratch slot left behind)
+    const lc3_group &g = G.g[lc3_find_group(G, blockIdx.x, 0)];
+    const int32_t *p = planes + (size_t)g.frame_base * (size_t)LC3_PLANE_WORDS;
+    LC3_GROUP_VIEW_LIST(lc3_decode_body_views_late, g, blockIdx.x - g.wg_stream, states, entries, g.first_stream, g.n_streams, p, pcm, g.nbytes,
+                        g.n_frames, lc3_io_views(io));
+}
+#endif
+#if LC3_MULTI_TU && LC3_TU_KIND == 0
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, 4) void lc3_decode_view_items_kernel_all(lc3_groups G, lc3_dec_state *states, const int32_t *entries,
+                                                                                const int32_t *planes, int16_t *pcm, lc3_io io);
+__global__ __launch_bounds__(64 * LC3_WG_WAVES, 4) void lc3_decode_view_items_late_kernel_all(lc3_groups G, lc3_dec_state *states,
+                                                                                     const int32_t *entries, const int32_t *planes,
+                                                                                     int16_t *pcm, lc3_io io);
 #endif
 #if LC3_MULTI_TU && LC3_TU_KIND == 0
 __global__ __launch_bounds__(64 * LC3_WG_WAVES, 4) void lc3_decode_mixed_list_kernel_all(lc3_groups G, lc3_dec_state *states, const int32_t *entries,
@@ -3031,6 +3214,8 @@ struct HandleCommon {
     std::vector<lc3_mlist_stream> mlist_streams;  // per caller stream
     static size_t mlist_tab_offset(int n) { return (sizeof(int32_t) * (size_t)n + 7) & ~(size_t)7; }
     static size_t mlist_bytes(int n) { return mlist_tab_offset(n) + sizeof(lc3_stream_io) * (size_t)n; }
+    // a views call's rows (lc3_view_io) are the larger ones: what a slot of the ring is sized for, whichever call comes first
+    static size_t mviews_bytes(int n) { return mlist_tab_offset(n) + sizeof(lc3_view_io) * (size_t)n; }
     // builds the plan P of a call over channels[n] (already checked; fresh: per internal index) in a free pinned slot and sends it, in
     // stream order on `s`; the handle's description in the plan's terms is written down at the first call
     void mlist_describe() {
@@ -3044,7 +3229,7 @@ struct HandleCommon {
     int mlist_send(const int32_t *channels, int n, const uint8_t *fresh, hipStream_t s, lc3_mlist_plan &P) {
         mlist_describe();
         uint8_t *slot = nullptr;
-        const int rc = mlist_ring.acquire(mlist_bytes(num_channels), &slot);
+        const int rc = mlist_ring.acquire(mviews_bytes(num_channels), &slot);
         if (rc) return rc;
         lc3_mlist_build(mlist_groups.data(), (int)mlist_groups.size(), mlist_streams.data(), fresh, channels, n, (int32_t *)slot,
                         (lc3_stream_io *)(slot + mlist_tab_offset(n)), P);
@@ -3082,7 +3267,7 @@ struct HandleCommon {
         static_assert(sizeof(lc3gpu_item) == sizeof(lc3_mitem), "lc3gpu_item is the plan's item");
         mlist_describe();
         uint8_t *slot = nullptr;
-        const int rc = mlist_ring.acquire(mlist_bytes(num_channels), &slot);
+        const int rc = mlist_ring.acquire(mviews_bytes(num_channels), &slot);
         if (rc) return rc;
         lc3_mitems_build(mlist_groups.data(), mlist_streams.data(), fresh, (const lc3_mitem *)items, n, (int32_t *)slot,
                          (lc3_stream_io *)(slot + mlist_tab_offset(n)), mitems_plan);
@@ -3133,12 +3318,38 @@ struct HandleCommon {
         static_assert(sizeof(lc3gpu_mc_item) == sizeof(lc3_mcitem), "lc3gpu_mc_item is the plan's item");
         mlist_describe();
         uint8_t *slot = nullptr;
-        const int rc = mlist_ring.acquire(mlist_bytes(num_channels), &slot);
+        const int rc = mlist_ring.acquire(mviews_bytes(num_channels), &slot);
         if (rc) return rc;
         lc3_mcitems_build(mlist_groups.data(), mlist_streams.data(), fresh, (const lc3_mcitem *)items, n, (int32_t *)slot,
                           (lc3_stream_io *)(slot + mlist_tab_offset(n_list)), mitems_plan);
         return mlist_ring.upload(mlist_bytes(n_list), s);
     }
+    // The views of a views call (lc3gpu_*_mixed_views), checked on the host by lc3_mviews_check -- items, placements, alignment and the
+    // extents of every view inside the caller's buffer sizes; nothing is queued or changed
+    int views_check(const lc3gpu_view *views, int n, const lc3_mviews_bounds &B, size_t *frames, int *max_frames) {
+        static_assert(sizeof(lc3gpu_view) == sizeof(lc3_mview) && sizeof(lc3gpu_view) == 64, "lc3gpu_view is the plan's view");
+        static_assert(LC3_MVIEWS_EINVAL == LC3GPU_EINVAL && LC3_MVIEWS_ECHANNEL == LC3GPU_ECHANNEL && LC3_MVIEWS_ELENGTH == LC3GPU_ELENGTH,
+                      "the plan's codes are the ABI's");
+        mlist_describe();
+        if (list_seen.size() != (size_t)num_channels) list_seen.assign((size_t)num_channels, 0u);
+        if (++list_call == 0u) {
+            std::fill(list_seen.begin(), list_seen.end(), 0u);
+            list_call = 1u;
+        }
+        return lc3_mviews_check(mlist_groups.data(), mlist_streams.data(), num_channels, (const lc3_mview *)views, n, B, list_seen.data(), list_call,
+                                frames, max_frames);
+    }
+    // its plan (lc3_mviews_build), built and sent as mitems_send does: entries and, behind them, the lc3_view_io rows (44 bytes per view)
+    int mviews_send(const lc3gpu_view *views, int n, int use_flags, const uint8_t *fresh, hipStream_t s) {
+        uint8_t *slot = nullptr;
+        const int rc = mlist_ring.acquire(mviews_bytes(num_channels), &slot);
+        if (rc) return rc;
+        lc3_mviews_build(mlist_groups.data(), mlist_streams.data(), fresh, (const lc3_mview *)views, n, use_flags, (int32_t *)slot,
+                         (lc3_view_io *)(slot + mlist_tab_offset(n)), mitems_plan);
+        return mlist_ring.upload(mviews_bytes(n), s);
+    }
+    // the rows' device address in the form the kernels' lc3_io carries it (lc3_io_views)
+    const lc3_stream_io *d_mviews_rows(int n) const { return (const lc3_stream_io *)(const void *)(mlist_ring.d + mlist_tab_offset(n)); }
     const int32_t *d_mlist_entries() const { return (const int32_t *)mlist_ring.d; }
     const lc3_stream_io *d_mlist_tab(int n) const { return (const lc3_stream_io *)(mlist_ring.d + mlist_tab_offset(n)); }
     // a multi-unit library's list twins carry a body per compile-time view and none for the run-time view (LC3_GROUP_VIEW_LIST)
@@ -3508,6 +3719,19 @@ static int lc3_pack_pc_mc_optin() {
     done[dev] = true;
     return LC3GPU_OK;
 }
+// ... and the pair packer of the views call (lc3gpu_encode_mixed_views), as lc3_pack_pc_mc_optin
+static int lc3_pack_pc_views_optin() {
+    static bool done[LC3_MAX_DEVICES] = {};
+    static std::mutex mu;
+    std::lock_guard<std::mutex> lock(mu);
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    if (dev < 0 || dev >= LC3_MAX_DEVICES) return LC3GPU_EINVAL;
+    if (done[dev]) return LC3GPU_OK;
+    HIP_TRY(hipFuncSetAttribute((const void *)LC3_MIXED_LAUNCH(lc3_pack_pc_view_items_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    done[dev] = true;
+    return LC3GPU_OK;
+}
 // Frames per workgroup of the pair kernels: 128 (four waves, one per SIMD; ~40 KB of LDS at 150-byte frames).  Such a workgroup takes
 // the place of exactly ONE workgroup of a wave-per-stream kernel (40 KB, a wave per SIMD) when another handle's call runs beside it on
 // another HIP stream; with 256 frames (70 KB, two waves per SIMD) it displaced two for as long as it ran.  Measured: two-stream
@@ -3555,6 +3779,19 @@ static int lc3_parse_pc_mc_optin() {
     if (dev < 0 || dev >= LC3_MAX_DEVICES) return LC3GPU_EINVAL;
     if (done[dev]) return LC3GPU_OK;
     HIP_TRY(hipFuncSetAttribute((const void *)LC3_MIXED_LAUNCH(lc3_parse_pc_mc_items_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LC3_PC_LDS_MAX));
+    done[dev] = true;
+    return LC3GPU_OK;
+}
+// ... and the pair parser of the views call (see lc3_pack_pc_views_optin)
+static int lc3_parse_pc_views_optin() {
+    static bool done[LC3_MAX_DEVICES] = {};
+    static std::mutex mu;
+    std::lock_guard<std::mutex> lock(mu);
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    if (dev < 0 || dev >= LC3_MAX_DEVICES) return LC3GPU_EINVAL;
+    if (done[dev]) return LC3GPU_OK;
+    HIP_TRY(hipFuncSetAttribute((const void *)LC3_MIXED_LAUNCH(lc3_parse_pc_view_items_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LC3_PC_LDS_MAX));
     done[dev] = true;
     return LC3GPU_OK;
 }
@@ -3713,7 +3950,7 @@ static int state_blobs_load_channels(HandleCommon &hc, ST *d_states, const int32
 
 extern "C" {
 
-int lc3gpu_version(void) { return 330; }
+int lc3gpu_version(void) { return 340; }
 
 const char *lc3gpu_strerror(int code) {
     switch (code) {
@@ -4502,6 +4739,87 @@ int lc3gpu_encode_mixed_mc_items(lc3gpu_encoder *e, const lc3gpu_mc_item *items,
     return call.end(rc);
 }
 
+// A list of views of a mixed handle: lc3gpu_encode_mixed_items with a placement per item (lc3_mviews_build).  The front half and the
+// packers are the view twins, which read stride and pitches from the call's lc3_view_io rows; the vector quantiser and the back half see
+// plane columns only and are the items call's kernels.  Every check -- the extents of every view among them -- comes before anything is queued
+int lc3gpu_encode_mixed_views(lc3gpu_encoder *e, const lc3gpu_view *views, int n_views, const int16_t *d_pcm, size_t pcm_elems, uint8_t *d_out,
+                              size_t out_bytes, void *stream_) {
+    if (!e || !e->mixed || n_views < 0) return LC3GPU_EINVAL;
+    if (n_views == 0) return LC3GPU_OK;
+    if (!views || !d_pcm || !d_out) return LC3GPU_EINVAL;
+    if (!e->mixed_list_views_ok()) return LC3GPU_EUNSUPPORTED;
+    size_t frames = 0;
+    int max_frames = 0;
+    const lc3_mviews_bounds bounds = {(uint64_t)(uintptr_t)d_pcm, (uint64_t)pcm_elems, (uint64_t)out_bytes, 0, 0, 20};
+    int rc = e->views_check(views, n_views, bounds, &frames, &max_frames);
+    if (rc) return rc;
+    LC3_ON_DEVICE(e);
+    hipStream_t stream = (hipStream_t)stream_;
+    BatchCall call(*e, stream);
+    rc = call.begin();
+    if (rc == LC3GPU_OK) rc = encoder_reserve_planes(e, frames, stream);
+    if (rc == LC3GPU_OK) rc = e->mviews_send(views, n_views, 0, e->fresh_mask.data(), stream);
+    if (rc) return rc;
+    const lc3_mitems_plan &P = e->mitems_plan;
+    const int32_t *d_entries = e->d_mlist_entries();
+    const lc3_io io = {0, e->d_mviews_rows(n_views)};
+    const dim3 wg_block(64 * LC3_WG_WAVES);
+    const bool pairs = lc3_prep_symbols_mode(frames) == 0 && lc3_pack_pc_enabled();
+    if (pairs && (rc = lc3_pack_pc_views_optin()) != LC3GPU_OK) return rc;  // (before anything is launched)
+    call.arm();
+    rc = encode_stages(
+        e, stream, 0, nullptr,
+        [&] {
+            return items_stage(*e, P, [&](ItemsGroups groups, int) {
+                GroupTable t;
+                groups(256u, t);
+                hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_enc_front_view_items_kernel), dim3(t.wg_stream), wg_block, 0, stream, t.G, e->d_states, d_entries,
+                                   d_pcm, e->d_mid, e->d_planes, io, e->spec_flags);
+                return LC3GPU_OK;
+            });
+        },
+        [&] {
+            return items_stage(*e, P, [&](ItemsGroups groups, int) {
+                GroupTable t;
+                groups(256u, t);
+                hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_sns_vq_items_kernel), dim3(t.wg_frame), dim3(256), 0, stream, t.G, e->d_mid, e->d_planes,
+                                   e->spec_flags);
+                return LC3GPU_OK;
+            });
+        },
+        [&] {
+            return items_stage(*e, P, [&](ItemsGroups groups, int) {
+                GroupTable t;
+                groups(256u, t);
+                hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_enc_back_items_kernel), dim3(t.wg_stream), wg_block, 0, stream, t.G, e->d_states, d_entries,
+                                   (const float *)e->d_mid, e->d_planes, e->spec_flags | lc3_prep_symbols_flag(frames, true));
+                return LC3GPU_OK;
+            });
+        },
+        [] { return LC3GPU_OK; },
+        [&] {
+            return items_stage(*e, P, [&](ItemsGroups groups, int max_nbytes) {
+                GroupTable t;  // (the LDS of a launch set is sized by ITS largest frame)
+                if (pairs) {
+                    const unsigned pfpb = lc3_pack_pc_fpb(max_nbytes);
+                    groups(pfpb, t);
+                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_pack_pc_view_items_kernel), dim3(t.wg_frame), dim3(2 * pfpb),
+                                       lc3_pack_pc_lds(pfpb, max_nbytes), stream, t.G, (const int32_t *)e->d_planes, d_out, io, e->d_pc_timeouts);
+                } else {
+                    const unsigned fpb = lc3_frame_block_fit(LC3_PACK_LDS_FIXED, (size_t)max_nbytes);
+                    const size_t lds = LC3_PACK_LDS_FIXED + (((size_t)fpb * (size_t)max_nbytes + 3) & ~(size_t)3) + 4;
+                    groups(fpb, t);
+                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_pack_view_items_kernel), dim3(t.wg_frame), dim3(fpb), lds, stream, t.G,
+                                       (const int32_t *)e->d_planes, d_out, io);
+                }
+                return LC3GPU_OK;
+            });
+        });
+    if (rc == LC3GPU_OK)
+        for (int i = 0; i < n_views; i++) e->fresh_mask[(size_t)e->streams[(size_t)views[i].channel].internal] = 0;
+    return call.end(rc);
+}
+
 static int encode_frame_host(lc3gpu_encoder *e, int channel_index, const int16_t *samples_in, int n_samples,
                              uint8_t *buf_out, int nbytes, float *dbg) {
     if (!e || !samples_in || !buf_out) return LC3GPU_EINVAL;
@@ -5245,6 +5563,89 @@ int lc3gpu_decode_mixed_mc_items(lc3gpu_decoder *d, const lc3gpu_mc_item *items,
     if (rc == LC3GPU_OK)
         for (int i = 0; i < n_items; i++)
             for (int c = 0; c < items[i].n_channels; c++) d->fresh_clear(d->streams[(size_t)(items[i].first_channel + c)].internal);
+    return call.end(rc);
+}
+
+// A list of views of a mixed handle, as lc3gpu_encode_mixed_views: the parsers and the synthesis forms are the view twins, the wave-per-
+// frame reconstruction and the TNS kernel the items call's.  Flags are read, and their extents checked, only when d_bad is given
+int lc3gpu_decode_mixed_views(lc3gpu_decoder *d, const lc3gpu_view *views, int n_views, const uint8_t *d_in, size_t in_bytes, const uint8_t *d_bad,
+                              size_t n_flags, int16_t *d_pcm, size_t pcm_elems, void *stream_) {
+    if (!d || !d->mixed || n_views < 0) return LC3GPU_EINVAL;
+    if (n_views == 0) return LC3GPU_OK;
+    if (!views || !d_in || !d_pcm) return LC3GPU_EINVAL;
+    if (!d->mixed_list_views_ok()) return LC3GPU_EUNSUPPORTED;
+    size_t frames = 0;
+    int max_frames = 0;
+    const int use_flags = d_bad != nullptr;
+    const lc3_mviews_bounds bounds = {(uint64_t)(uintptr_t)d_pcm, (uint64_t)pcm_elems, (uint64_t)in_bytes, (uint64_t)n_flags, use_flags, 1};
+    int rc = d->views_check(views, n_views, bounds, &frames, &max_frames);
+    if (rc) return rc;
+    LC3_ON_DEVICE(d);
+    hipStream_t stream = (hipStream_t)stream_;
+    const int mode = lc3_recon_mode(frames, max_frames);
+    const bool pairs = mode == LC3_RECON_LANE && lc3_parse_pc_enabled();
+    BatchCall call(*d, stream);
+    rc = call.begin();
+    if (rc == LC3GPU_OK) rc = decoder_reserve_planes(d, frames, stream);
+    if (rc == LC3GPU_OK && mode == LC3_RECON_WAVE) rc = lc3_tns_lds_optin();
+    if (rc == LC3GPU_OK && pairs) rc = lc3_parse_pc_views_optin();
+    if (rc == LC3GPU_OK) rc = d->mviews_send(views, n_views, use_flags, d->fresh_mask.data(), stream);
+    if (rc) return rc;
+    const lc3_mitems_plan &P = d->mitems_plan;
+    const int32_t *d_entries = d->d_mlist_entries();
+    const lc3_io io = {0, d->d_mviews_rows(n_views)};
+    call.arm();
+    rc = decode_stages(
+        d, stream, 0, mode,
+        [&] {
+            return items_stage(*d, P, [&](ItemsGroups groups, int max_nbytes) {
+                GroupTable t;
+                if (pairs) {
+                    const unsigned pfpb = lc3_parse_pc_fpb(max_nbytes);
+                    groups(pfpb, t);
+                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_parse_pc_view_items_kernel), dim3(t.wg_frame), dim3(2 * pfpb),
+                                       lc3_parse_pc_lds(pfpb, max_nbytes), stream, t.G, d_in, d_bad, d->d_planes, io, d->d_pc_timeouts);
+                } else {
+                    const unsigned fpb = lc3_frame_block_fit(LC3_PARSE_LDS_FIXED, (size_t)(64 + max_nbytes));
+                    const size_t lds = LC3_PARSE_LDS_FIXED + (size_t)fpb * (size_t)(64 + max_nbytes);
+                    groups(fpb, t);
+                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_parse_view_items_kernel), dim3(t.wg_frame), dim3(fpb), lds, stream, t.G, d_in, d_bad, d->d_planes,
+                                       io, mode);
+                }
+                return LC3GPU_OK;
+            });
+        },
+        [&] {
+            return items_stage(*d, P, [&](ItemsGroups groups, int) {
+                GroupTable t;
+                groups((unsigned)LC3_WG_WAVES, t);
+                hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_recon_items_kernel), dim3(t.wg_frame), dim3(64 * LC3_WG_WAVES), 0, stream, t.G, d->d_planes);
+                return LC3GPU_OK;
+            });
+        },
+        [&] {
+            return items_stage(*d, P, [&](ItemsGroups groups, int) {
+                GroupTable t;
+                groups((unsigned)LC3_TNS_FPB, t);
+                hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_tns_items_kernel), dim3(t.wg_frame), dim3(LC3_TNS_FPB), LC3_TNS_LDS, stream, t.G, d->d_planes);
+                return LC3GPU_OK;
+            });
+        },
+        [&] {
+            return items_stage(*d, P, [&](ItemsGroups groups, int) {
+                GroupTable t;
+                groups(256u, t);
+                if (mode == LC3_RECON_LATE)
+                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_decode_view_items_late_kernel), dim3(t.wg_stream), dim3(64 * LC3_WG_WAVES), 0, stream, t.G,
+                                       d->d_states, d_entries, (const int32_t *)d->d_planes, d_pcm, io);
+                else
+                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_decode_view_items_kernel), dim3(t.wg_stream), dim3(64 * LC3_WG_WAVES), 0, stream, t.G,
+                                       d->d_states, d_entries, (const int32_t *)d->d_planes, d_pcm, io);
+                return LC3GPU_OK;
+            });
+        });
+    if (rc == LC3GPU_OK)
+        for (int i = 0; i < n_views; i++) d->fresh_clear(d->streams[(size_t)views[i].channel].internal);
     return call.end(rc);
 }
 

@@ -17,7 +17,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "lc3gpu.h")
 
 OPAQUE = {"lc3gpu_encoder": "Lc3GpuEncoder", "lc3gpu_decoder": "Lc3GpuDecoder", "lc3gpu_pipeline": "Lc3GpuPipeline",
-          "lc3gpu_stream_desc": "Lc3GpuStreamDesc", "lc3gpu_frame_info": "Lc3GpuFrameInfo", "lc3gpu_item": "Lc3GpuItem", "lc3gpu_mc_item": "Lc3GpuMcItem"}
+          "lc3gpu_stream_desc": "Lc3GpuStreamDesc", "lc3gpu_frame_info": "Lc3GpuFrameInfo", "lc3gpu_item": "Lc3GpuItem", "lc3gpu_mc_item": "Lc3GpuMcItem",
+          "lc3gpu_view": "Lc3GpuView"}
 SCALAR = {"int": "i32", "unsigned": "u32", "unsigned int": "u32", "float": "f32", "double": "f64", "size_t": "usize",
           "int16_t": "i16", "uint16_t": "u16", "uint8_t": "u8", "int32_t": "i32", "uint32_t": "u32", "int64_t": "i64", "uint64_t": "u64",
           "unsigned long long": "u64", "char": "c_char", "void": "c_void"}
@@ -216,6 +217,16 @@ impl Lc3EncoderGpu {
     pub unsafe fn encode_mixed_mc_items_device(&mut self, items: &[Lc3GpuMcItem], d_pcm: *const i16, d_out: *mut u8, hip_stream: *mut c_void) -> i32 {
         lc3gpu_encode_mixed_mc_items(self.h, items.as_ptr(), items.len() as i32, d_pcm, d_out, hip_stream)
     }
+    /// Views of a mixed-configuration handle: every item with the placement of its PCM and its frames, read and written in place
+    /// (jitter rings, a capture buffer wider than the stream).
+    ///
+    /// # Safety
+    /// `d_pcm` / `d_out` must be device allocations of at least `pcm_elems` elements / `out_bytes` bytes that outlive the call's work;
+    /// every view is checked against these extents on the host.  `views` is host memory and free again when the call returns.
+    pub unsafe fn encode_mixed_views_device(&mut self, views: &[Lc3GpuView], d_pcm: *const i16, pcm_elems: usize, d_out: *mut u8, out_bytes: usize,
+                                            hip_stream: *mut c_void) -> i32 {
+        lc3gpu_encode_mixed_views(self.h, views.as_ptr(), views.len() as i32, d_pcm, pcm_elems, d_out, out_bytes, hip_stream)
+    }
     /// a new `EncoderChannel` for each named channel (from its next call on; no wait); the others are untouched
     pub fn reset_channels(&mut self, channels: &[i32]) -> Result<(), i32> {
         let rc = unsafe { lc3gpu_encoder_reset_channels(self.h, channels.as_ptr(), channels.len() as i32) };
@@ -317,6 +328,16 @@ impl Lc3DecoderGpu {
                                                hip_stream: *mut c_void) -> i32 {
         lc3gpu_decode_mixed_mc_items(self.h, items.as_ptr(), items.len() as i32, d_in, d_bad_frame, d_pcm, hip_stream)
     }
+    /// Views: frames read where they lie, PCM written where it belongs, nothing else touched (lc3gpu_decode_mixed_views).
+    ///
+    /// # Safety
+    /// device allocations of at least `in_bytes` bytes, `n_flags` flags (or a null `d_bad_frame`) and `pcm_elems` elements that outlive
+    /// the call's work; `views` is host memory and free again when the call returns.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn decode_mixed_views_device(&mut self, views: &[Lc3GpuView], d_in: *const u8, in_bytes: usize, d_bad_frame: *const u8, n_flags: usize,
+                                            d_pcm: *mut i16, pcm_elems: usize, hip_stream: *mut c_void) -> i32 {
+        lc3gpu_decode_mixed_views(self.h, views.as_ptr(), views.len() as i32, d_in, in_bytes, d_bad_frame, n_flags, d_pcm, pcm_elems, hip_stream)
+    }
     /// a new `DecoderChannel` for each named channel (from its next call on; no wait; its PLC count goes to zero)
     pub fn reset_channels(&mut self, channels: &[i32]) -> Result<(), i32> {
         let rc = unsafe { lc3gpu_decoder_reset_channels(self.h, channels.as_ptr(), channels.len() as i32) };
@@ -391,7 +412,7 @@ def generate():
         "",
     ]
     for c, r in sorted(OPAQUE.items()):
-        if c in ("lc3gpu_stream_desc", "lc3gpu_frame_info", "lc3gpu_item", "lc3gpu_mc_item"):
+        if c in ("lc3gpu_stream_desc", "lc3gpu_frame_info", "lc3gpu_item", "lc3gpu_mc_item", "lc3gpu_view"):
             continue
         lines += ["#[repr(C)]", "pub struct %s {" % r, "    _private: [u8; 0],", "}"]
     lines += ["/// one stream of a mixed-configuration handle (lc3gpu_stream_desc)", "#[repr(C)]", "#[derive(Clone, Copy, Debug)]",
@@ -404,6 +425,12 @@ def generate():
               "/// size (0 = the descriptors')", "#[repr(C)]", "#[derive(Clone, Copy, Debug, Default)]", "pub struct Lc3GpuMcItem {",
               "    pub first_channel: i32,", "    pub n_channels: i32,", "    pub n_frames: i32,", "    pub nbytes: i32,", "}",
               "const _: () = assert!(core::mem::size_of::<Lc3GpuMcItem>() == 16);"]
+    lines += ["/// one view of the *_mixed_views calls (lc3gpu_view, 64 bytes): an item -- channel, frames in this call, their size (0 = the",
+              "/// descriptor's) -- with the placement of its PCM, its frames and its flags in the caller's buffers; a pitch of 0 = the compact one",
+              "#[repr(C)]", "#[derive(Clone, Copy, Debug, Default)]", "pub struct Lc3GpuView {", "    pub channel: i32,", "    pub n_frames: i32,",
+              "    pub nbytes: i32,", "    pub pcm_stride: i32,", "    pub pcm_off: i64,", "    pub byte_off: i64,", "    pub flag_off: i64,",
+              "    pub pcm_pitch: i32,", "    pub byte_pitch: i32,", "    pub flag_pitch: i32,", "    pub reserved: [i32; 3],", "}",
+              "const _: () = assert!(core::mem::size_of::<Lc3GpuView>() == 64);"]
     lines += ["/// one frame's record of lc3gpu_inspect (lc3gpu_frame_info, 128 bytes): status LC3GPU_FRAME_*, the side information",
               "/// (decoder/side_info.rs:20-31) and the arithmetic data (decoder/arithmetic_codec.rs:99-107)", "#[repr(C)]",
               "#[derive(Clone, Copy, Debug, Default)]", "pub struct Lc3GpuFrameInfo {"]
