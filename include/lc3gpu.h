@@ -502,6 +502,69 @@ int lc3gpu_decode_mixed_mc_items(lc3gpu_decoder *dec, const lc3gpu_mc_item *item
  * flag_off, flag_pitch and n_flags are ignored), and frame sizes 1..400. */
 int lc3gpu_decode_mixed_views(lc3gpu_decoder *dec, const lc3gpu_view *views, int n_views, const uint8_t *d_in, size_t in_bytes,
                               const uint8_t *d_bad_frame, size_t n_flags, int16_t *d_pcm, size_t pcm_elems, void *hip_stream);
+/* Frame inspection over a list of VIEWS: the status and the side information of every frame of a tick, read where the frames lie and
+ * written where their flags lie -- what lc3gpu_inspect reports, for the very lc3gpu_view array the tick passes to
+ * lc3gpu_decode_mixed_views, in one launch and without a gather or scatter pass around it.  Inspection needs no codec handle (the
+ * reference's side_info_reader::read needs only the configuration), so the streams' configurations are fixed once in an INSPECTOR, which
+ * also owns the pinned upload ring and the device tables a handle-less call has nowhere to keep.
+ *   create    descs: the array the caller passes to lc3gpu_decoder_create_mixed (copied): fs_hz one of the six rates (8 kHz included),
+ *             frame_us 7500 or 10000 (LC3GPU_EINVAL otherwise), nbytes 1..400 (LC3GPU_ELENGTH otherwise); n_streams >= 1.  max_views >= 1
+ *             is the most views one call may name (it sizes the ring and the tables once; LC3GPU_EINVAL below 1).  The inspector is bound
+ *             to the device that is current at creation, is not thread-safe and is independent of every codec handle.  No device:
+ *             LC3GPU_ENODEVICE
+ *   views     HOST lc3gpu_view[n_views], any order; may be reused as soon as the call returns.  Read: channel (the descriptor index),
+ *             n_frames, nbytes (0 = the descriptor's), byte_off, byte_pitch, flag_off, flag_pitch and reserved (0), each with the meaning
+ *             it has in the decode call.  NOT read: pcm_stride, pcm_off, pcm_pitch -- a view the decode call would refuse for its PCM
+ *             placement is not refused here
+ *   placement with nb the effective frame size of the view:
+ *               frame t's bytes        d_in[byte_off + t * byte_pitch ..  + nb)
+ *               frame t's flag         d_bad_frame[flag_off + t * flag_pitch]   (when d_bad_frame is given)
+ *               frame t's status byte  d_status[flag_off + t * flag_pitch]      (when d_status is given)
+ *               frame t's record       d_info[flag_off + t * flag_pitch]        (when d_info is given; 128 bytes)
+ *             the outputs follow the flag placement; a pitch of 0 stands for the compact one (nb, 1).  At least one of d_status and d_info
+ *             must be given.  Only a frame's own status byte and record are written: every byte between and around them is left as it was
+ *   repeats   a channel MAY be named by several views (inspection carries no state): the two parts of a ring that wraps are two views
+ *             of one call.  Two views that write the same output index are the caller's error: the content there is unspecified, every
+ *             write is still inside the checked extents
+ *   written   two equivalences are part of the contract.  The record of a frame is, byte for byte, the record lc3gpu_inspect writes when
+ *             called with the descriptor's (frame_us, fs_hz), slot_bytes = nb, d_nbytes = NULL, that frame's nb bytes and its flag
+ *             (LC3GPU_FRAME_EMPTY therefore cannot occur); the status byte is that record's `status` (every status value fits a byte).
+ *             And, as for lc3gpu_inspect: status != 0 exactly for the frames lc3gpu_decode_mixed_views conceals, given the same
+ *             descriptors, views, bytes and flags (the pair-give-up exception stated there applies)
+ *   checks    on the host before anything is queued; a refused call has launched nothing and written nothing:
+ *               channel outside [0, n_streams)                       LC3GPU_ECHANNEL
+ *               n_frames < 1                                         LC3GPU_ELENGTH
+ *               nbytes not 0 and outside 1..400                      LC3GPU_ELENGTH
+ *               more than 2^31 - 1 frames in one call                LC3GPU_ELENGTH
+ *               n_views > max_views                                  LC3GPU_ELENGTH
+ *               any byte, flag, status byte or record of any frame
+ *               outside [0, in_bytes), [0, n_flags), [0, n_status),
+ *               [0, n_info)                                          LC3GPU_ELENGTH
+ *               a negative byte_off or flag_off                      LC3GPU_EINVAL
+ *               a non-zero pitch below its minimum (nb, 1)           LC3GPU_EINVAL
+ *               reserved != 0                                        LC3GPU_EINVAL
+ *               both outputs NULL                                    LC3GPU_EINVAL
+ *               null insp, views or d_in                             LC3GPU_EINVAL
+ *               n_views < 0                                          LC3GPU_EINVAL
+ *               d_info not 4-byte aligned                            LC3GPU_EINVAL
+ *               an output array's address range ([d_status,
+ *               + n_status), [d_info, + n_info * 128)) overlapping
+ *               d_in's, d_bad_frame's or the other output's          LC3GPU_EINVAL
+ *               n_views == 0                                         LC3GPU_OK (nothing launched)
+ *             the extent check works in unsigned 64-bit arithmetic that cannot wrap; extents are checked only against the arrays that are
+ *             given (n_flags, n_status, n_info of a NULL array are ignored).  HIP errors: LC3GPU_EHIP
+ *   order     asynchronous on hip_stream, ordered as any kernel on that stream.  In the steady state the call does not synchronise the
+ *             host; it waits for the oldest of its own uploads only when more calls are in flight than the ring has slots
+ *   launches  ONE launch and ONE upload of O(views + workgroups) bytes per call, whatever mix of configurations, sizes and frame counts
+ *             the views hold; with d_info == NULL one byte per frame leaves the device's compute units instead of 128
+ * NOT provided (out of scope): a size per frame within a view, uniform handles and flat batches (lc3gpu_inspect is theirs), the pipeline
+ * object, host-resident buffers. */
+typedef struct lc3gpu_inspector lc3gpu_inspector;
+int lc3gpu_inspector_create(lc3gpu_inspector **out, int n_streams, const lc3gpu_stream_desc *descs, int max_views);
+int lc3gpu_inspector_destroy(lc3gpu_inspector *insp);
+int lc3gpu_inspect_mixed_views(lc3gpu_inspector *insp, const lc3gpu_view *views, int n_views, const uint8_t *d_in, size_t in_bytes,
+                               const uint8_t *d_bad_frame, size_t n_flags, uint8_t *d_status, size_t n_status, lc3gpu_frame_info *d_info,
+                               size_t n_info, void *hip_stream);
 
 size_t lc3gpu_decoder_state_size(const lc3gpu_decoder *dec);
 int lc3gpu_decoder_state_save(lc3gpu_decoder *dec, void *host_dst, size_t nbytes);

@@ -252,6 +252,33 @@ inline void inspect(FrameDuration d, SamplingFrequency f, const uint8_t *d_in, l
     if (rc) throw Error(rc, "inspect");
 }
 
+// The inspector (lc3gpu_inspect_mixed_views): the status and the side information of every frame of a tick, for the very views the tick
+// passes to Lc3Decoder::decode_mixed_views; streams = the array of Lc3Decoder(streams), max_views the most views one call may name.
+// Independent of every codec handle
+class Lc3Inspector {
+public:
+    Lc3Inspector(const std::vector<lc3gpu_stream_desc> &streams, size_t max_views) {
+        int rc = lc3gpu_inspector_create(&h_, (int)streams.size(), streams.data(), (int)max_views);
+        if (rc) throw Error(rc, "Lc3Inspector::new");
+    }
+    ~Lc3Inspector() { lc3gpu_inspector_destroy(h_); }
+    Lc3Inspector(const Lc3Inspector &) = delete;
+    Lc3Inspector &operator=(const Lc3Inspector &) = delete;
+    // frame t of a view: its status byte at d_status[flag_off + t * flag_pitch], its record at d_info[the same index]; either output may be
+    // nullptr (with extent 0), not both; d_bad_frame / n_flags the flag array and its length, or nullptr / 0
+    void inspect_mixed_views(const std::vector<lc3gpu_view> &views, const uint8_t *d_in, size_t in_bytes, uint8_t *d_status, size_t n_status,
+                             lc3gpu_frame_info *d_info = nullptr, size_t n_info = 0, const uint8_t *d_bad_frame = nullptr, size_t n_flags = 0,
+                             void *hip_stream = nullptr) {
+        int rc = lc3gpu_inspect_mixed_views(h_, views.data(), (int)views.size(), d_in, in_bytes, d_bad_frame, n_flags, d_status, n_status, d_info,
+                                            n_info, hip_stream);
+        if (rc) throw Error(rc, "inspect_mixed_views");
+    }
+    lc3gpu_inspector *handle() { return h_; }
+
+private:
+    lc3gpu_inspector *h_ = nullptr;
+};
+
 // ---- the reference's no_std / no-alloc API shape (lc3_encoder.rs:37-40,212-303, lc3_decoder.rs:56-60,247-310): the
 // number of channels is a compile-time constant instead of a constructor argument (`Lc3Encoder::<NUM_CH>::new(duration,
 // frequency, ..)`, `Lc3Encoder::<NUM_CH>::calc_working_buffer_lengths(duration, frequency)`; default 2 as in the

@@ -28,6 +28,7 @@ from .api import (  # noqa: F401
     LAYOUT_INTERLEAVED,
     LAYOUT_PLANAR,
     Lc3GpuError,
+    Lc3Inspector,
     Lc3Pipeline,
     PinnedBuffer,
     SPEC_8KHZ_ENCODE,

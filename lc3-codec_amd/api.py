@@ -22,7 +22,12 @@ _PROFILE = os.environ.get("LC3GPU_PROFILE", "0") == "1"
 _LIB = os.path.join(_HERE, "lib", os.environ.get("LC3GPU_LIB") or ("liblc3gpu_prof.so" if _PROFILE else "liblc3gpu.so"))
 _SRC = os.path.join(_HERE, "csrc", "lc3gpu.hip")
 # host-only sources of the library on top of its own C ABI (the pipeline object): plain C++ beside the HIP translation units
-_HOST_SRCS = [os.path.join(_HERE, "csrc", "lc3gpu_pipeline.cpp")]
+_HOST_SRCS = [os.path.join(_HERE, "csrc", "lc3gpu_pipeline.cpp"), os.path.join(_HERE, "csrc", "lc3gpu_inspector_api.cpp")]
+# The companion library of the inspector (lc3gpu_inspect_mixed_views): device code of its own, beside whichever main library is built.  The
+# main library links it (run path $ORIGIN) and holds host-side entry points only, so its own kernels are what they were.
+_INSPECTOR_LIB = os.path.join(os.path.dirname(_LIB), "liblc3gpu_inspector.so")
+_INSPECTOR_SRC = os.path.join(_HERE, "csrc", "lc3gpu_inspector.hip")
+_INSPECTOR_ONLY = ("lc3gpu_inspector.hip", "lc3_host_inspect_views.h")  # sources no unit of the main library sees
 
 class Lc3GpuError(RuntimeError):
     def __init__(self, code, what=""):
@@ -59,6 +64,11 @@ _lib = None
 
 def library_path():
     return _LIB
+
+
+def inspector_library_path():
+    """the companion library of the inspector (lc3gpu_inspect_mixed_views), which the main library links"""
+    return _INSPECTOR_LIB
 
 
 def _translation_units():
@@ -102,12 +112,14 @@ def build_native(force=False, verbose=False):
     (LC3GPU_PROFILE=1) and builds with LC3_HIPCC_EXTRA compile it whole, with the four views of the round-1..4 library.
     LC3_HIPCC_EXTRA_MAIN="-D..." (timing experiments on the headline kernels): the multi-unit build with those flags on the MAIN unit only;
     the other units' objects are the production ones.  A library remembers the switches it was built with (<lib>.stamp) and is rebuilt
-    when they differ; experiment builds need their own file name (LC3GPU_LIB) so that they never replace the default library."""
+    when they differ; experiment builds need their own file name (LC3GPU_LIB) so that they never replace the default library.
+    Every flavour links the inspector's companion library (csrc/lc3gpu_inspector.hip -> lib/liblc3gpu_inspector.so, one ordinary unit),
+    which is built and stamped here first; its own sources are no part of what the main library's translation units are stamped with."""
     srcs = [os.path.join(_HERE, "csrc", f) for f in os.listdir(os.path.join(_HERE, "csrc")) if f.endswith((".h", ".hip", ".cpp"))]
     srcs += [os.path.join(_ROOT, "include", "lc3gpu.h"), os.path.join(_ROOT, "tables", "lc3_tables.h")]
     src_hash = _sources_hash(srcs)  # taken BEFORE anything is compiled: what the objects below are guaranteed to be at least as old as
     # (the HIP translation units do not see the host-only sources: an edit there relinks the library without recompiling them)
-    dev_hash = _sources_hash([p_ for p_ in srcs if not p_.endswith(".cpp")])
+    dev_hash = _sources_hash([p_ for p_ in srcs if not p_.endswith(".cpp") and os.path.basename(p_) not in _INSPECTOR_ONLY])
     extra = os.environ.get("LC3_HIPCC_EXTRA", "").split()  # compiler experiments
     extra_main = os.environ.get("LC3_HIPCC_EXTRA_MAIN", "").split()
     if (extra or extra_main) and not os.environ.get("LC3GPU_LIB"):
@@ -124,13 +136,32 @@ def build_native(force=False, verbose=False):
         except OSError:
             return False
 
-    if not force and os.path.exists(_LIB) and stamped(stamp, sig):
-        return _LIB
     os.makedirs(os.path.dirname(_LIB), exist_ok=True)
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function",
              "-Wno-missing-braces"]
+    # the companion first (every flavour of the main library links the same one): one ordinary unit, stamped with its sources' contents
+    insp_sig = "sources=%s\n" % _sources_hash([p_ for p_ in srcs if not p_.endswith(".cpp")])
+    if force or not os.path.exists(_INSPECTOR_LIB) or not stamped(_INSPECTOR_LIB + ".stamp", insp_sig):
+        tmp = _INSPECTOR_LIB + ".tmp%d" % os.getpid()
+        cmd = ["hipcc"] + flags + ["-shared", "-o", tmp, _INSPECTOR_SRC]
+        if verbose:
+            print(" ".join(cmd))
+        try:
+            subprocess.check_call(cmd)
+            os.replace(tmp, _INSPECTOR_LIB)
+        finally:
+            if os.path.exists(tmp):
+                os.remove(tmp)
+        with open(_INSPECTOR_LIB + ".stamp", "w") as f:
+            f.write(insp_sig)
+        force_link = True
+    else:
+        force_link = False
+    if not force and not force_link and os.path.exists(_LIB) and stamped(stamp, sig):
+        return _LIB
+    link_insp = ["-L" + os.path.dirname(_INSPECTOR_LIB), "-llc3gpu_inspector", "-Wl,-rpath,$ORIGIN"]
     if single:
-        cmd = ["hipcc"] + extra + (["-DLC3_PROFILE"] if _PROFILE else []) + flags + ["-shared", "-o", _LIB, _SRC] + _HOST_SRCS
+        cmd = ["hipcc"] + extra + (["-DLC3_PROFILE"] if _PROFILE else []) + flags + ["-shared", "-o", _LIB, _SRC] + _HOST_SRCS + link_insp
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
@@ -185,7 +216,7 @@ def build_native(force=False, verbose=False):
         obj = os.path.join(objdir, os.path.splitext(os.path.basename(src))[0] + ".o")
         subprocess.check_call(["hipcc", "-O2", "-std=c++17", "-fPIC", "-c", "-o", obj, src])
         host_objs.append(obj)
-    cmd = ["hipcc", "--offload-arch=gfx950", "-fPIC", "-shared", "-o", _LIB] + sorted(unit_obj(u) for u in units) + host_objs
+    cmd = ["hipcc", "--offload-arch=gfx950", "-fPIC", "-shared", "-o", _LIB] + sorted(unit_obj(u) for u in units) + host_objs + link_insp
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
@@ -267,6 +298,9 @@ def load_library():
     L.lc3gpu_encoder_size_clamps.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     L.lc3gpu_decode_vbr.argtypes = [vp, vp, vp, vp, vp, i, i, vp]
     L.lc3gpu_inspect.argtypes = [i, i, vp, vp, vp, i, i, vp, vp]
+    L.lc3gpu_inspector_create.argtypes = [ctypes.POINTER(vp), i, vp, i]
+    L.lc3gpu_inspector_destroy.argtypes = [vp]
+    L.lc3gpu_inspect_mixed_views.argtypes = [vp, vp, i, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp]
     L.lc3gpu_encoder_state_size.restype = ctypes.c_size_t
     L.lc3gpu_encoder_state_size.argtypes = [vp]
     L.lc3gpu_encoder_state_save.argtypes = [vp, vp, ctypes.c_size_t]
@@ -352,6 +386,7 @@ ABI_SYMBOLS = [
     "lc3gpu_encode_mixed_items", "lc3gpu_decode_mixed_items",
     "lc3gpu_encode_mixed_mc_items", "lc3gpu_decode_mixed_mc_items",
     "lc3gpu_encode_mixed_views", "lc3gpu_decode_mixed_views",
+    "lc3gpu_inspector_create", "lc3gpu_inspector_destroy", "lc3gpu_inspect_mixed_views",
 ]
 
 # LC3GPU_SPEC_*: opt-in corrections of the reference's deviations from the LC3 specification (default 0 = reference behaviour)
@@ -1089,6 +1124,70 @@ class Lc3Decoder:
             self.close()
         except Exception:
             pass
+
+
+class Lc3Inspector:
+    """lc3gpu_inspector: the status and the side information of every frame of a tick, for the very views the tick passes to
+    Lc3Decoder.decode_mixed_views.  descs = [(fs_hz, frame_us, nbytes), ...] as for Lc3Decoder.mixed; max_views = the most views one call
+    may name.  Independent of every codec handle; bound to the device current at creation."""
+
+    def __init__(self, descs, max_views):
+        self._L = load_library()
+        self.descs = [(int(d[0]), int(d[1]), int(d[2])) for d in descs]
+        self.num_channels = len(self.descs)
+        self.max_views = int(max_views)
+        h = ctypes.c_void_p()
+        rc = self._L.lc3gpu_inspector_create(ctypes.byref(h), self.num_channels, _desc_array(self.descs), self.max_views)
+        if rc:
+            raise Lc3GpuError(rc, "Lc3Inspector::new")
+        self._h = h
+
+    def inspect_mixed_views(self, views, d_in, d_status=None, d_info=None, d_bad_frame=None, stream=None, in_bytes=None, n_status=None, n_info=None,
+                            n_flags=None):
+        """one launch over all views: frame t of a view has its bytes at d_in[byte_off + t * byte_pitch], its flag at
+        d_bad_frame[flag_off + t * flag_pitch] (when given); its status byte goes to d_status[the same index] (uint8) and its record to
+        d_info[the same index] (FRAME_INFO_DTYPE, 128 bytes; as a uint8 tensor: 128 elements per record).  At least one of d_status and
+        d_info; the extents default to the buffers' sizes (lc3gpu_inspect_mixed_views)"""
+        v = _view_list(views)
+        ib = _numel(d_in, "in_bytes") if in_bytes is None else int(in_bytes)
+        nfl = 0 if d_bad_frame is None else (_numel(d_bad_frame, "n_flags") if n_flags is None else int(n_flags))
+        nst = 0 if d_status is None else (_numel(d_status, "n_status") if n_status is None else int(n_status))
+        if d_info is None:
+            nin = 0
+        elif n_info is not None:
+            nin = int(n_info)
+        elif isinstance(d_info, np.ndarray) or hasattr(d_info, "element_size"):
+            size = d_info.itemsize if isinstance(d_info, np.ndarray) else d_info.element_size()
+            nin = _numel(d_info, "n_info") * int(size) // FRAME_INFO_DTYPE.itemsize
+        else:
+            raise TypeError("n_info: pass the buffer's extent when the buffer is a bare pointer")
+        rc = self._L.lc3gpu_inspect_mixed_views(self._h, _ptr(v), int(v.shape[0]), _ptr(d_in), ib, _ptr(d_bad_frame), nfl, _ptr(d_status), nst,
+                                                _ptr(d_info), nin, _ptr(stream))
+        if rc:
+            raise Lc3GpuError(rc, "inspect_mixed_views")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.lc3gpu_inspector_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def inspector_plan_info(max_nbytes):
+    """-> (frames per workgroup, dynamic LDS bytes, upload ring slots) of an inspector call whose largest frame size is max_nbytes: the
+    plan's own figures, from the companion library (tests and tools)"""
+    load_library()  # (the main library first: it brings the companion in, and the one HIP runtime of the process)
+    C = ctypes.CDLL(_INSPECTOR_LIB)
+    fpb, lds, slots = ctypes.c_int(), ctypes.c_size_t(), ctypes.c_int()
+    rc = C.lc3insp_plan_info(int(max_nbytes), ctypes.byref(fpb), ctypes.byref(lds), ctypes.byref(slots))
+    if rc:
+        raise Lc3GpuError(rc, "inspector_plan_info")
+    return fpb.value, lds.value, slots.value
 
 
 class PinnedBuffer:

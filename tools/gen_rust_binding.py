@@ -18,7 +18,7 @@ HEADER = os.path.join(ROOT, "include", "lc3gpu.h")
 
 OPAQUE = {"lc3gpu_encoder": "Lc3GpuEncoder", "lc3gpu_decoder": "Lc3GpuDecoder", "lc3gpu_pipeline": "Lc3GpuPipeline",
           "lc3gpu_stream_desc": "Lc3GpuStreamDesc", "lc3gpu_frame_info": "Lc3GpuFrameInfo", "lc3gpu_item": "Lc3GpuItem", "lc3gpu_mc_item": "Lc3GpuMcItem",
-          "lc3gpu_view": "Lc3GpuView"}
+          "lc3gpu_view": "Lc3GpuView", "lc3gpu_inspector": "Lc3GpuInspector"}
 SCALAR = {"int": "i32", "unsigned": "u32", "unsigned int": "u32", "float": "f32", "double": "f64", "size_t": "usize",
           "int16_t": "i16", "uint16_t": "u16", "uint8_t": "u8", "int32_t": "i32", "uint32_t": "u32", "int64_t": "i64", "uint64_t": "u64",
           "unsigned long long": "u64", "char": "c_char", "void": "c_void"}
@@ -367,6 +367,41 @@ impl Drop for Lc3DecoderGpu {
 pub unsafe fn inspect_device(d: FrameDuration, f: SamplingFrequency, d_in: *const u8, d_nbytes: *const u16, d_bad_frame: *const u8, slot_bytes: usize,
                              n_frames: usize, d_info: *mut Lc3GpuFrameInfo, hip_stream: *mut c_void) -> i32 {
     lc3gpu_inspect(frame_us(d), fs_hz(f), d_in, d_nbytes, d_bad_frame, slot_bytes as i32, n_frames as i32, d_info, hip_stream)
+}
+
+/// The inspector (include/lc3gpu.h): the status and the side information of every frame of a tick, read where the frames lie and written
+/// where their flags lie -- for the very views the tick passes to `decode_mixed_views_device`.  Independent of every codec handle.
+pub struct Lc3InspectorGpu {
+    h: *mut Lc3GpuInspector,
+}
+impl Lc3InspectorGpu {
+    /// `descs`: the array the caller passes to lc3gpu_decoder_create_mixed; `max_views`: the most views one call may name
+    pub fn new(descs: &[Lc3GpuStreamDesc], max_views: usize) -> Result<Self, i32> {
+        let mut h = core::ptr::null_mut();
+        let rc = unsafe { lc3gpu_inspector_create(&mut h, descs.len() as i32, descs.as_ptr(), max_views as i32) };
+        if rc == LC3GPU_OK { Ok(Self { h }) } else { Err(rc) }
+    }
+    /// One launch over all views: frame t of a view gets its status byte at `d_status[flag_off + t * flag_pitch]` and its 128-byte record at
+    /// `d_info[...]` of the same index; either output may be null, not both.
+    ///
+    /// # Safety
+    /// device allocations of at least `in_bytes` bytes, `n_flags` flags (or a null `d_bad_frame`), `n_status` bytes and `n_info` records
+    /// (either may be null) that outlive the call's work; every view is checked against these extents on the host.  `views` is host memory
+    /// and free again when the call returns.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn inspect_mixed_views_device(&mut self, views: &[Lc3GpuView], d_in: *const u8, in_bytes: usize, d_bad_frame: *const u8, n_flags: usize,
+                                             d_status: *mut u8, n_status: usize, d_info: *mut Lc3GpuFrameInfo, n_info: usize,
+                                             hip_stream: *mut c_void) -> i32 {
+        lc3gpu_inspect_mixed_views(self.h, views.as_ptr(), views.len() as i32, d_in, in_bytes, d_bad_frame, n_flags, d_status, n_status, d_info, n_info,
+                                   hip_stream)
+    }
+}
+impl Drop for Lc3InspectorGpu {
+    fn drop(&mut self) {
+        unsafe {
+            lc3gpu_inspector_destroy(self.h);
+        }
+    }
 }
 
 /// Encode + decode of many channels in the arrangement that measured fastest (include/lc3gpu.h, "pipeline"): device buffers, asynchronous.
