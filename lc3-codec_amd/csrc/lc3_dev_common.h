@@ -125,6 +125,11 @@
 #endif
 
 #define LC3_WAVE 64
+// A point where the code leans on the lanes of a wave running in lockstep: every lane has done the reads above before any lane does the
+// writes below.  One instruction stream on the GPU: nothing to emit.  Where lanes are threads (the CPU wave emulator) it is a barrier.
+#ifndef LC3_LOCKSTEP
+#define LC3_LOCKSTEP() do { } while (0)
+#endif
 // does the predicate hold on any lane of the (lane-per-frame) wave?  Translation units that run frames one at a time: the lane's own.
 #ifndef LC3_WAVE_ANY
 #define LC3_WAVE_ANY(pred) ((pred) != 0)

@@ -249,7 +249,9 @@ __device__ __forceinline__ void lc3_ltpf_run(const CC &c, lc3_dec_lds &L, int la
     float *xh = L.st.x_hat_ltpf_mem;
     for (int n0 = n_begin; n0 < n_end; n0 += bsz) {
         const int n = n0 + lane;
-        if (lane < bsz && n < n_end) {
+        const bool on = lane < bsz && n < n_end;
+        float y = 0.0f;
+        if (on) {
             float acc = 0.0f;
             for (int k = 0; k <= l_num; k++) {
                 const int j = n - k;
@@ -266,8 +268,12 @@ __device__ __forceinline__ void lc3_ltpf_run(const CC &c, lc3_dec_lds &L, int la
             } else if (ramp == 2) {
                 acc *= 1.0f - ((float)n / (float)c.norm);
             }
-            xh[blk + n] = inp[n] - acc;
+            y = inp[n] - acc;
         }
+        // A lag beyond the ring's history (pitch_int + l_den/2 > ring - nf: the long lags of every configuration) wraps into THIS
+        // frame's block, at samples the reference has not replaced yet when it reads them: every lane reads before any lane writes
+        LC3_LOCKSTEP();
+        if (on) xh[blk + n] = y;
         LC3_SYNC();
     }
 }

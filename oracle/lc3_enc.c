@@ -12,6 +12,10 @@
 long lc3o_enc_path_count[4];
 int lc3o_enc_path_counting = 0;
 #define LC3O_ENC_COUNT(i) do { if (lc3o_enc_path_counting) __sync_fetch_and_add(&lc3o_enc_path_count[i], 1L); } while (0)
+/* a second statistic, switched on by the same flag (tests/test_corner_pcm.py): [0] frames the MDCT stage flags as near Nyquist, [1] frames
+ * whose estimated global gain index lies below gg_min and is raised to it (global_gain_limitation, a non-silent frame) */
+long lc3o_enc_corner_count[2];
+#define LC3O_ENC_CORNER(i) do { if (lc3o_enc_path_counting) __sync_fetch_and_add(&lc3o_enc_corner_count[i], 1L); } while (0)
 
 #define LC3_TABLE_QUAL static const
 #include "../tables/lc3_tables.h"
@@ -1023,6 +1027,7 @@ lc3o_quant_result lc3o_enc_quant(const lc3o_config *c, lc3o_quant_state *st, con
         gg_min = (int)lc3m_f32_to_i16(ceilf(28.0f * lc3m_log10f(x_f_max / (32768.0f - 0.375f)))) - gg_off;
     else gg_min = 0;
     if (gg_ind < gg_min || x_f_max == 0.0f) {
+        if (x_f_max > 0.0f) LC3O_ENC_CORNER(1);
         reset_offset = 1;
         gg_ind = gg_min;
     } else reset_offset = 0;
@@ -1378,6 +1383,7 @@ int lc3o_encode_frame(lc3o_encoder *e, const int16_t *x_s, uint8_t *out, int nby
     lc3o_quant_result spec;
     e->frame_index += 1;
     near_nyquist = lc3o_enc_mdct_run(e, x_s, e->mdct_out, e->energy_bands);
+    if (near_nyquist) LC3O_ENC_CORNER(0);
     bw = lc3o_enc_bandwidth(c, e->energy_bands);
     attack = lc3o_enc_attack(c, &e->att, x_s, nbytes);
     sns = lc3o_enc_sns(c, e->mdct_out, e->energy_bands, attack);

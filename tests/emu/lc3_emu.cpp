@@ -26,6 +26,7 @@
 static pthread_barrier_t g_wave_bar[LC3_WG_WAVES], g_wg_bar;
 static thread_local int tl_wave = 0;
 #define LC3_SYNC() pthread_barrier_wait(&g_wave_bar[tl_wave])
+#define LC3_LOCKSTEP() LC3_SYNC()  /* lanes are threads here: what lockstep gives a wave for free has to be waited for */
 #define LC3_SERIAL_BEGIN(T, L, lane, phase, K)                                   \
     {                                                                            \
         T *lc3_wg_base_ = &(L) - tl_wave;                                        \

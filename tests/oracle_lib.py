@@ -177,6 +177,17 @@ def encoder_path_counts(reset=False):
     return out
 
 
+def encoder_corner_counts(reset=False):
+    """[frames the MDCT stage flags as near Nyquist, non-silent frames whose global gain index is raised to gg_min] inside the oracle since the
+    last reset; a second statistic beside encoder_path_counts, switched on by the same flag"""
+    cnt = (ctypes.c_long * 2).in_dll(lib(), "lc3o_enc_corner_count")
+    ctypes.c_int.in_dll(lib(), "lc3o_enc_path_counting").value = 1
+    out = [int(v) for v in cnt]
+    if reset:
+        cnt[0] = cnt[1] = 0
+    return out
+
+
 def timed_run(pcm, nbytes, fs_hz=48000, frame_us=10000, threads=1, roundtrip=True, seconds=5.0, library=None):
     """bench.py's cpu_baseline leg: `threads` host threads, each with ONE persistent encoder (and decoder) that codes its own stream
     of consecutive frames (pcm[t % S], cycled) for `seconds`; thread start-up, allocation and initialisation lie outside the timed
