@@ -565,6 +565,89 @@ int lc3gpu_inspector_destroy(lc3gpu_inspector *insp);
 int lc3gpu_inspect_mixed_views(lc3gpu_inspector *insp, const lc3gpu_view *views, int n_views, const uint8_t *d_in, size_t in_bytes,
                                const uint8_t *d_bad_frame, size_t n_flags, uint8_t *d_status, size_t n_status, lc3gpu_frame_info *d_info,
                                size_t n_info, void *hip_stream);
+/* Frame analysis over a list of VIEWS: the reconstructed spectrum, the 64 band energies and the total energy of every frame of a tick, read
+ * where the frames lie and written at the frames' flag indices -- for the very lc3gpu_view array the tick passes to
+ * lc3gpu_decode_mixed_views and lc3gpu_inspect_mixed_views, in one launch, without decoding to PCM.  Everything the decoder does up to the
+ * input of its inverse transform (residual bits, noise filling, global gain, TNS synthesis, SNS gains: reference
+ * decoder/lc3_decoder.rs:99-131) reads the frame and the configuration only, so the call needs no codec handle: the streams' configurations
+ * are fixed once in an ANALYZER, which also owns the pinned upload ring, the device tables and the scratch columns the frames are rebuilt in.
+ *   create    descs, n_streams and max_views exactly as for lc3gpu_inspector_create: fs_hz one of the six rates (8 kHz included), frame_us
+ *             7500 or 10000 (LC3GPU_EINVAL otherwise), nbytes 1..400 (LC3GPU_ELENGTH otherwise); n_streams >= 1; max_views >= 1 is the
+ *             most views one call may name (LC3GPU_EINVAL below 1).  max_frames >= 1 is the most frames one call may hold: it sizes,
+ *             once, the scratch columns (one column of 648 words per frame, in device memory; LC3GPU_EINVAL below 1).  The analyzer is
+ *             bound to the device that is current at creation, is not thread-safe and is independent of every codec handle and of the
+ *             inspector.  No device: LC3GPU_ENODEVICE
+ *   views     HOST lc3gpu_view[n_views], any order; may be reused as soon as the call returns.  Read and NOT read exactly as in
+ *             lc3gpu_inspect_mixed_views: read are channel, n_frames, nbytes (0 = the descriptor's), byte_off, byte_pitch, flag_off,
+ *             flag_pitch and reserved (0); NOT read: pcm_stride, pcm_off, pcm_pitch
+ *   placement with nb the effective frame size of the view and i = flag_off + t * flag_pitch the OUTPUT INDEX of frame t:
+ *               frame t's bytes         d_in[byte_off + t * byte_pitch ..  + nb)
+ *               frame t's flag          d_bad_frame[i]                              (when d_bad_frame is given)
+ *               frame t's energy        d_energy[i]                                 (when d_energy is given)
+ *               frame t's band row      d_bands[i * LC3GPU_BANDS ..  + 64)           (when d_bands is given)
+ *               frame t's spectrum row  d_spec[i * LC3GPU_SPEC_LINES ..  + 400)      (when d_spec is given)
+ *             a pitch of 0 stands for the compact one (nb, 1).  At least one of the three outputs must be given.  Only a frame's own float
+ *             and rows are written: everything between and around them is left as it was
+ *   repeats   a channel MAY be named by several views (analysis carries no state): the two parts of a ring that wraps are two views of
+ *             one call.  Two views that write the same output index are the caller's error: the content there is unspecified, every write
+ *             is still inside the checked extents
+ *   written   for a GOOD frame -- one for which lc3gpu_inspect_mixed_views reports status 0 -- with ne and nb its configuration's numbers of
+ *             coded lines and of bands, I[] its band index table and x[k] the reference's x_hat after spectral_noise_shaping::decode:
+ *               d_spec[i * 400 + k]  = x[k] for k < ne, 0.0f for ne <= k < 400: bit for bit the LC3GPU_DBG_SPEC dump of
+ *                                      lc3gpu_decode_frame_debug
+ *               d_bands[i * 64 + b]  = the encoder's band-energy formula applied to x (reference encoder/modified_dct.rs:140-152):
+ *                                      e = 0.0f; for k in I[b] .. I[b + 1] - 1 ascending: e += x[k] * x[k] / (float)(I[b + 1] - I[b]);
+ *                                      0.0f for nb <= b < 64
+ *               d_energy[i]          = e = 0.0f; for k in 0 .. ne - 1 ascending: e += x[k] * x[k]
+ *             in f32, one operation at a time: multiply, then divide, then add; nothing fused.  For a frame the decoder would CONCEAL
+ *             (status != 0: flagged, side-information or arithmetic error): d_energy[i] = -1.0f -- an energy is never negative, so this is
+ *             the marker -- and the frame's d_bands and d_spec rows are all 0.0f.  The analyzer does not conceal: concealment is the
+ *             decoder's carried state, and this call has none.  Part of the contract: d_energy[i] < 0 exactly where
+ *             lc3gpu_inspect_mixed_views writes a non-zero status, given the same descriptors, views, bytes and flags
+ *   checks    on the host before anything is queued; a refused call has launched nothing and written nothing.  The whole refusal table of
+ *             lc3gpu_inspect_mixed_views applies, with the three outputs in place of d_status / d_info:
+ *               channel outside [0, n_streams)                       LC3GPU_ECHANNEL
+ *               n_frames < 1                                         LC3GPU_ELENGTH
+ *               nbytes not 0 and outside 1..400                      LC3GPU_ELENGTH
+ *               more than 2^31 - 1 frames in one call                LC3GPU_ELENGTH
+ *               more than max_frames frames in one call              LC3GPU_ELENGTH
+ *               n_views > max_views                                  LC3GPU_ELENGTH
+ *               any byte, flag, energy, band row or spectrum row of
+ *               any frame outside [0, in_bytes), [0, n_flags),
+ *               [0, n_energy), [0, n_bands), [0, n_spec)             LC3GPU_ELENGTH
+ *               a negative byte_off or flag_off                      LC3GPU_EINVAL
+ *               a non-zero pitch below its minimum (nb, 1)           LC3GPU_EINVAL
+ *               reserved != 0                                        LC3GPU_EINVAL
+ *               all three outputs NULL                               LC3GPU_EINVAL
+ *               null an, views or d_in                               LC3GPU_EINVAL
+ *               n_views < 0                                          LC3GPU_EINVAL
+ *               d_energy or d_bands not 4-byte aligned               LC3GPU_EINVAL
+ *               d_spec not 16-byte aligned                           LC3GPU_EINVAL
+ *               an output array's address range ([d_energy,
+ *               + n_energy * 4), [d_bands, + n_bands * 256), [d_spec,
+ *               + n_spec * 1600)) overlapping d_in's, d_bad_frame's
+ *               or another output's                                  LC3GPU_EINVAL
+ *               n_views == 0                                         LC3GPU_OK (nothing launched)
+ *             the extent check works in unsigned 64-bit arithmetic that cannot wrap; extents are checked only against the arrays that are
+ *             given (n_flags, n_energy, n_bands, n_spec of a NULL array are ignored).  HIP errors: LC3GPU_EHIP
+ *   order     asynchronous on hip_stream, ordered as any kernel on that stream.  In the steady state the call does not synchronise the
+ *             host; it waits for the oldest of its own uploads only when more calls are in flight than the ring has slots.  The calls of
+ *             ONE analyzer share its scratch columns: a call on another stream than the analyzer's previous call is ordered behind that
+ *             call on the device (an event wait), as the codec handles order theirs
+ *   launches  ONE launch and ONE upload of O(views) bytes per call, whatever mix of configurations, sizes and frame counts the views hold
+ * NOT provided (out of scope): a size per frame within a view, uniform handles and flat batches, PCM-domain measures, concealed spectra,
+ * host-resident buffers, the pipeline object. */
+#define LC3GPU_BANDS 64        /* row length of d_bands (nb <= 64 for every configuration) */
+#define LC3GPU_SPEC_LINES 400  /* row length of d_spec  (ne <= 400) */
+typedef struct lc3gpu_analyzer lc3gpu_analyzer;
+int lc3gpu_analyzer_create(lc3gpu_analyzer **out, int n_streams, const lc3gpu_stream_desc *descs, int max_views, int max_frames);
+int lc3gpu_analyzer_destroy(lc3gpu_analyzer *an);
+int lc3gpu_analyze_mixed_views(lc3gpu_analyzer *an, const lc3gpu_view *views, int n_views, const uint8_t *d_in, size_t in_bytes,
+                               const uint8_t *d_bad_frame, size_t n_flags,
+                               float *d_energy, size_t n_energy,   /* one float per output index, or NULL */
+                               float *d_bands, size_t n_bands,     /* n_bands rows of LC3GPU_BANDS floats, or NULL */
+                               float *d_spec, size_t n_spec,       /* n_spec rows of LC3GPU_SPEC_LINES floats, or NULL */
+                               void *hip_stream);
 
 size_t lc3gpu_decoder_state_size(const lc3gpu_decoder *dec);
 int lc3gpu_decoder_state_save(lc3gpu_decoder *dec, void *host_dst, size_t nbytes);

@@ -279,6 +279,35 @@ private:
     lc3gpu_inspector *h_ = nullptr;
 };
 
+// The analyzer (lc3gpu_analyze_mixed_views): the reconstructed spectrum, the 64 band energies and the total energy of every frame of a
+// tick, for the very views the tick passes to Lc3Decoder::decode_mixed_views, without decoding to PCM; streams = the array of
+// Lc3Decoder(streams), max_views / max_frames the most views one call may name and the most frames it may hold.  Independent of every codec
+// handle and of the inspector
+class Lc3Analyzer {
+public:
+    Lc3Analyzer(const std::vector<lc3gpu_stream_desc> &streams, size_t max_views, size_t max_frames) {
+        int rc = lc3gpu_analyzer_create(&h_, (int)streams.size(), streams.data(), (int)max_views, (int)max_frames);
+        if (rc) throw Error(rc, "Lc3Analyzer::new");
+    }
+    ~Lc3Analyzer() { lc3gpu_analyzer_destroy(h_); }
+    Lc3Analyzer(const Lc3Analyzer &) = delete;
+    Lc3Analyzer &operator=(const Lc3Analyzer &) = delete;
+    // frame t of a view, i = flag_off + t * flag_pitch: its energy at d_energy[i] (-1 for a frame the decoder would conceal), its band row at
+    // d_bands[i * LC3GPU_BANDS], its spectrum row at d_spec[i * LC3GPU_SPEC_LINES] (16-byte aligned); any output may be nullptr (with extent
+    // 0), not all three; d_bad_frame / n_flags the flag array and its length, or nullptr / 0
+    void analyze_mixed_views(const std::vector<lc3gpu_view> &views, const uint8_t *d_in, size_t in_bytes, float *d_energy, size_t n_energy,
+                             float *d_bands = nullptr, size_t n_bands = 0, float *d_spec = nullptr, size_t n_spec = 0,
+                             const uint8_t *d_bad_frame = nullptr, size_t n_flags = 0, void *hip_stream = nullptr) {
+        int rc = lc3gpu_analyze_mixed_views(h_, views.data(), (int)views.size(), d_in, in_bytes, d_bad_frame, n_flags, d_energy, n_energy, d_bands,
+                                            n_bands, d_spec, n_spec, hip_stream);
+        if (rc) throw Error(rc, "analyze_mixed_views");
+    }
+    lc3gpu_analyzer *handle() { return h_; }
+
+private:
+    lc3gpu_analyzer *h_ = nullptr;
+};
+
 // ---- the reference's no_std / no-alloc API shape (lc3_encoder.rs:37-40,212-303, lc3_decoder.rs:56-60,247-310): the
 // number of channels is a compile-time constant instead of a constructor argument (`Lc3Encoder::<NUM_CH>::new(duration,
 // frequency, ..)`, `Lc3Encoder::<NUM_CH>::calc_working_buffer_lengths(duration, frequency)`; default 2 as in the

@@ -22,12 +22,18 @@ _PROFILE = os.environ.get("LC3GPU_PROFILE", "0") == "1"
 _LIB = os.path.join(_HERE, "lib", os.environ.get("LC3GPU_LIB") or ("liblc3gpu_prof.so" if _PROFILE else "liblc3gpu.so"))
 _SRC = os.path.join(_HERE, "csrc", "lc3gpu.hip")
 # host-only sources of the library on top of its own C ABI (the pipeline object): plain C++ beside the HIP translation units
-_HOST_SRCS = [os.path.join(_HERE, "csrc", "lc3gpu_pipeline.cpp"), os.path.join(_HERE, "csrc", "lc3gpu_inspector_api.cpp")]
+_HOST_SRCS = [os.path.join(_HERE, "csrc", "lc3gpu_pipeline.cpp"), os.path.join(_HERE, "csrc", "lc3gpu_inspector_api.cpp"),
+              os.path.join(_HERE, "csrc", "lc3gpu_analyzer_api.cpp")]
 # The companion library of the inspector (lc3gpu_inspect_mixed_views): device code of its own, beside whichever main library is built.  The
 # main library links it (run path $ORIGIN) and holds host-side entry points only, so its own kernels are what they were.
 _INSPECTOR_LIB = os.path.join(os.path.dirname(_LIB), "liblc3gpu_inspector.so")
 _INSPECTOR_SRC = os.path.join(_HERE, "csrc", "lc3gpu_inspector.hip")
 _INSPECTOR_ONLY = ("lc3gpu_inspector.hip", "lc3_host_inspect_views.h")  # sources no unit of the main library sees
+# The companion library of the analyzer (lc3gpu_analyze_mixed_views), the second of its kind: one ordinary unit, its kernel and its scratch
+# columns beside the main library, which links it the same way.
+_ANALYZER_LIB = os.path.join(os.path.dirname(_LIB), "liblc3gpu_analyzer.so")
+_ANALYZER_SRC = os.path.join(_HERE, "csrc", "lc3gpu_analyzer.hip")
+_ANALYZER_ONLY = ("lc3gpu_analyzer.hip", "lc3_host_analyze_views.h", "lc3_dev_dec_analyze.h")  # sources only the analyzer's unit sees
 
 class Lc3GpuError(RuntimeError):
     def __init__(self, code, what=""):
@@ -69,6 +75,11 @@ def library_path():
 def inspector_library_path():
     """the companion library of the inspector (lc3gpu_inspect_mixed_views), which the main library links"""
     return _INSPECTOR_LIB
+
+
+def analyzer_library_path():
+    """the companion library of the analyzer (lc3gpu_analyze_mixed_views), which the main library links"""
+    return _ANALYZER_LIB
 
 
 def _translation_units():
@@ -114,12 +125,13 @@ def build_native(force=False, verbose=False):
     the other units' objects are the production ones.  A library remembers the switches it was built with (<lib>.stamp) and is rebuilt
     when they differ; experiment builds need their own file name (LC3GPU_LIB) so that they never replace the default library.
     Every flavour links the inspector's companion library (csrc/lc3gpu_inspector.hip -> lib/liblc3gpu_inspector.so, one ordinary unit),
-    which is built and stamped here first; its own sources are no part of what the main library's translation units are stamped with."""
+    which is built and stamped here first; its own sources are no part of what the main library's translation units are stamped with.
+    The analyzer's companion (csrc/lc3gpu_analyzer.hip -> lib/liblc3gpu_analyzer.so) is built, stamped and linked the same way."""
     srcs = [os.path.join(_HERE, "csrc", f) for f in os.listdir(os.path.join(_HERE, "csrc")) if f.endswith((".h", ".hip", ".cpp"))]
     srcs += [os.path.join(_ROOT, "include", "lc3gpu.h"), os.path.join(_ROOT, "tables", "lc3_tables.h")]
     src_hash = _sources_hash(srcs)  # taken BEFORE anything is compiled: what the objects below are guaranteed to be at least as old as
     # (the HIP translation units do not see the host-only sources: an edit there relinks the library without recompiling them)
-    dev_hash = _sources_hash([p_ for p_ in srcs if not p_.endswith(".cpp") and os.path.basename(p_) not in _INSPECTOR_ONLY])
+    dev_hash = _sources_hash([p_ for p_ in srcs if not p_.endswith(".cpp") and os.path.basename(p_) not in _INSPECTOR_ONLY + _ANALYZER_ONLY])
     extra = os.environ.get("LC3_HIPCC_EXTRA", "").split()  # compiler experiments
     extra_main = os.environ.get("LC3_HIPCC_EXTRA_MAIN", "").split()
     if (extra or extra_main) and not os.environ.get("LC3GPU_LIB"):
@@ -139,27 +151,28 @@ def build_native(force=False, verbose=False):
     os.makedirs(os.path.dirname(_LIB), exist_ok=True)
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function",
              "-Wno-missing-braces"]
-    # the companion first (every flavour of the main library links the same one): one ordinary unit, stamped with its sources' contents
-    insp_sig = "sources=%s\n" % _sources_hash([p_ for p_ in srcs if not p_.endswith(".cpp")])
-    if force or not os.path.exists(_INSPECTOR_LIB) or not stamped(_INSPECTOR_LIB + ".stamp", insp_sig):
-        tmp = _INSPECTOR_LIB + ".tmp%d" % os.getpid()
-        cmd = ["hipcc"] + flags + ["-shared", "-o", tmp, _INSPECTOR_SRC]
-        if verbose:
-            print(" ".join(cmd))
-        try:
-            subprocess.check_call(cmd)
-            os.replace(tmp, _INSPECTOR_LIB)
-        finally:
-            if os.path.exists(tmp):
-                os.remove(tmp)
-        with open(_INSPECTOR_LIB + ".stamp", "w") as f:
-            f.write(insp_sig)
-        force_link = True
-    else:
-        force_link = False
+    # the companions first (every flavour of the main library links the same ones): one ordinary unit each, stamped with the contents of
+    # the sources that unit can see (the inspector's stamp is what it was before the analyzer existed)
+    force_link = False
+    for comp_lib, comp_src, hidden in ((_INSPECTOR_LIB, _INSPECTOR_SRC, _ANALYZER_ONLY), (_ANALYZER_LIB, _ANALYZER_SRC, ("lc3gpu_inspector.hip",))):
+        comp_sig = "sources=%s\n" % _sources_hash([p_ for p_ in srcs if not p_.endswith(".cpp") and os.path.basename(p_) not in hidden])
+        if force or not os.path.exists(comp_lib) or not stamped(comp_lib + ".stamp", comp_sig):
+            tmp = comp_lib + ".tmp%d" % os.getpid()
+            cmd = ["hipcc"] + flags + ["-shared", "-o", tmp, comp_src]
+            if verbose:
+                print(" ".join(cmd))
+            try:
+                subprocess.check_call(cmd)
+                os.replace(tmp, comp_lib)
+            finally:
+                if os.path.exists(tmp):
+                    os.remove(tmp)
+            with open(comp_lib + ".stamp", "w") as f:
+                f.write(comp_sig)
+            force_link = True
     if not force and not force_link and os.path.exists(_LIB) and stamped(stamp, sig):
         return _LIB
-    link_insp = ["-L" + os.path.dirname(_INSPECTOR_LIB), "-llc3gpu_inspector", "-Wl,-rpath,$ORIGIN"]
+    link_insp = ["-L" + os.path.dirname(_INSPECTOR_LIB), "-llc3gpu_inspector", "-llc3gpu_analyzer", "-Wl,-rpath,$ORIGIN"]
     if single:
         cmd = ["hipcc"] + extra + (["-DLC3_PROFILE"] if _PROFILE else []) + flags + ["-shared", "-o", _LIB, _SRC] + _HOST_SRCS + link_insp
         if verbose:
@@ -301,6 +314,10 @@ def load_library():
     L.lc3gpu_inspector_create.argtypes = [ctypes.POINTER(vp), i, vp, i]
     L.lc3gpu_inspector_destroy.argtypes = [vp]
     L.lc3gpu_inspect_mixed_views.argtypes = [vp, vp, i, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp]
+    L.lc3gpu_analyzer_create.argtypes = [ctypes.POINTER(vp), i, vp, i, i]
+    L.lc3gpu_analyzer_destroy.argtypes = [vp]
+    L.lc3gpu_analyze_mixed_views.argtypes = [vp, vp, i, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp,
+                                             ctypes.c_size_t, vp]
     L.lc3gpu_encoder_state_size.restype = ctypes.c_size_t
     L.lc3gpu_encoder_state_size.argtypes = [vp]
     L.lc3gpu_encoder_state_save.argtypes = [vp, vp, ctypes.c_size_t]
@@ -387,6 +404,7 @@ ABI_SYMBOLS = [
     "lc3gpu_encode_mixed_mc_items", "lc3gpu_decode_mixed_mc_items",
     "lc3gpu_encode_mixed_views", "lc3gpu_decode_mixed_views",
     "lc3gpu_inspector_create", "lc3gpu_inspector_destroy", "lc3gpu_inspect_mixed_views",
+    "lc3gpu_analyzer_create", "lc3gpu_analyzer_destroy", "lc3gpu_analyze_mixed_views",
 ]
 
 # LC3GPU_SPEC_*: opt-in corrections of the reference's deviations from the LC3 specification (default 0 = reference behaviour)
@@ -1188,6 +1206,80 @@ def inspector_plan_info(max_nbytes):
     if rc:
         raise Lc3GpuError(rc, "inspector_plan_info")
     return fpb.value, lds.value, slots.value
+
+
+# frame analysis (lc3gpu_analyze_mixed_views): the row lengths of d_bands and d_spec (LC3GPU_BANDS, LC3GPU_SPEC_LINES)
+BANDS, SPEC_LINES = 64, 400
+
+
+class Lc3Analyzer:
+    """lc3gpu_analyzer: the reconstructed spectrum, the 64 band energies and the total energy of every frame of a tick, for the very views
+    the tick passes to Lc3Decoder.decode_mixed_views and Lc3Inspector.inspect_mixed_views, without decoding to PCM.  descs = [(fs_hz,
+    frame_us, nbytes), ...] as for Lc3Decoder.mixed; max_views / max_frames = the most views one call may name and the most frames it may
+    hold.  Independent of every codec handle; bound to the device current at creation."""
+
+    def __init__(self, descs, max_views, max_frames):
+        self._L = load_library()
+        self.descs = [(int(d[0]), int(d[1]), int(d[2])) for d in descs]
+        self.num_channels = len(self.descs)
+        self.max_views, self.max_frames = int(max_views), int(max_frames)
+        h = ctypes.c_void_p()
+        rc = self._L.lc3gpu_analyzer_create(ctypes.byref(h), self.num_channels, _desc_array(self.descs), self.max_views, self.max_frames)
+        if rc:
+            raise Lc3GpuError(rc, "Lc3Analyzer::new")
+        self._h = h
+
+    @staticmethod
+    def _rows(buf, given, row, what):
+        """the extent of an output in rows of `row` float32: given, or from the buffer's size in bytes"""
+        if buf is None:
+            return 0
+        if given is not None:
+            return int(given)
+        if isinstance(buf, np.ndarray) or hasattr(buf, "element_size"):
+            size = buf.itemsize if isinstance(buf, np.ndarray) else buf.element_size()
+            return _numel(buf, what) * int(size) // (4 * row)
+        raise TypeError(what + ": pass the buffer's extent when the buffer is a bare pointer")
+
+    def analyze_mixed_views(self, views, d_in, d_energy=None, d_bands=None, d_spec=None, d_bad_frame=None, stream=None, in_bytes=None,
+                            n_energy=None, n_bands=None, n_spec=None, n_flags=None):
+        """one launch over all views: frame t of a view has its bytes at d_in[byte_off + t * byte_pitch], its flag at d_bad_frame[i] (when
+        given) with i = flag_off + t * flag_pitch; its total energy goes to d_energy[i] (float32; -1 for a frame the decoder would
+        conceal), its band energies to d_bands[i * 64 ..] and its spectrum to d_spec[i * 400 ..] (float32 rows; d_spec 16-byte aligned).
+        At least one of the three; the extents (floats, rows, rows) default to the buffers' sizes (lc3gpu_analyze_mixed_views)"""
+        v = _view_list(views)
+        ib = _numel(d_in, "in_bytes") if in_bytes is None else int(in_bytes)
+        nfl = 0 if d_bad_frame is None else (_numel(d_bad_frame, "n_flags") if n_flags is None else int(n_flags))
+        ne = self._rows(d_energy, n_energy, 1, "n_energy")
+        nbd = self._rows(d_bands, n_bands, BANDS, "n_bands")
+        nsp = self._rows(d_spec, n_spec, SPEC_LINES, "n_spec")
+        rc = self._L.lc3gpu_analyze_mixed_views(self._h, _ptr(v), int(v.shape[0]), _ptr(d_in), ib, _ptr(d_bad_frame), nfl, _ptr(d_energy), ne,
+                                                _ptr(d_bands), nbd, _ptr(d_spec), nsp, _ptr(stream))
+        if rc:
+            raise Lc3GpuError(rc, "analyze_mixed_views")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.lc3gpu_analyzer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def analyzer_plan_info(max_nbytes):
+    """-> (frames per workgroup, dynamic LDS bytes, upload ring slots, words of a frame's scratch column) of an analyzer call whose largest
+    frame size is max_nbytes: the plan's own figures, from the companion library (tests and tools)"""
+    load_library()  # (the main library first: it brings the companion in, and the one HIP runtime of the process)
+    C = ctypes.CDLL(_ANALYZER_LIB)
+    fpb, lds, slots, words = ctypes.c_int(), ctypes.c_size_t(), ctypes.c_int(), ctypes.c_int()
+    rc = C.lc3ana_plan_info(int(max_nbytes), ctypes.byref(fpb), ctypes.byref(lds), ctypes.byref(slots), ctypes.byref(words))
+    if rc:
+        raise Lc3GpuError(rc, "analyzer_plan_info")
+    return fpb.value, lds.value, slots.value, words.value
 
 
 class PinnedBuffer:

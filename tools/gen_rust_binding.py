@@ -18,7 +18,7 @@ HEADER = os.path.join(ROOT, "include", "lc3gpu.h")
 
 OPAQUE = {"lc3gpu_encoder": "Lc3GpuEncoder", "lc3gpu_decoder": "Lc3GpuDecoder", "lc3gpu_pipeline": "Lc3GpuPipeline",
           "lc3gpu_stream_desc": "Lc3GpuStreamDesc", "lc3gpu_frame_info": "Lc3GpuFrameInfo", "lc3gpu_item": "Lc3GpuItem", "lc3gpu_mc_item": "Lc3GpuMcItem",
-          "lc3gpu_view": "Lc3GpuView", "lc3gpu_inspector": "Lc3GpuInspector"}
+          "lc3gpu_view": "Lc3GpuView", "lc3gpu_inspector": "Lc3GpuInspector", "lc3gpu_analyzer": "Lc3GpuAnalyzer"}
 SCALAR = {"int": "i32", "unsigned": "u32", "unsigned int": "u32", "float": "f32", "double": "f64", "size_t": "usize",
           "int16_t": "i16", "uint16_t": "u16", "uint8_t": "u8", "int32_t": "i32", "uint32_t": "u32", "int64_t": "i64", "uint64_t": "u64",
           "unsigned long long": "u64", "char": "c_char", "void": "c_void"}
@@ -400,6 +400,44 @@ impl Drop for Lc3InspectorGpu {
     fn drop(&mut self) {
         unsafe {
             lc3gpu_inspector_destroy(self.h);
+        }
+    }
+}
+
+/// The analyzer (include/lc3gpu.h): the reconstructed spectrum, the 64 band energies and the total energy of every frame of a tick, read
+/// where the frames lie and written at the frames' flag indices -- for the very views the tick passes to `decode_mixed_views_device`,
+/// without decoding to PCM.  Independent of every codec handle and of the inspector.
+pub struct Lc3AnalyzerGpu {
+    h: *mut Lc3GpuAnalyzer,
+}
+impl Lc3AnalyzerGpu {
+    /// `descs`: the array the caller passes to lc3gpu_decoder_create_mixed; `max_views` / `max_frames`: the most views one call may name
+    /// and the most frames it may hold (one scratch column per frame is allocated here)
+    pub fn new(descs: &[Lc3GpuStreamDesc], max_views: usize, max_frames: usize) -> Result<Self, i32> {
+        let mut h = core::ptr::null_mut();
+        let rc = unsafe { lc3gpu_analyzer_create(&mut h, descs.len() as i32, descs.as_ptr(), max_views as i32, max_frames as i32) };
+        if rc == LC3GPU_OK { Ok(Self { h }) } else { Err(rc) }
+    }
+    /// One launch over all views: frame t of a view, with i = flag_off + t * flag_pitch, gets its energy at `d_energy[i]` (-1.0 for a frame
+    /// the decoder would conceal), its LC3GPU_BANDS band energies at `d_bands[i * 64 ..]` and its LC3GPU_SPEC_LINES lines at
+    /// `d_spec[i * 400 ..]`; any output may be null, not all three.
+    ///
+    /// # Safety
+    /// device allocations of at least `in_bytes` bytes, `n_flags` flags (or a null `d_bad_frame`), `n_energy` floats, `n_bands` rows of 64
+    /// floats and `n_spec` rows of 400 floats (16-byte aligned; each may be null) that outlive the call's work; every view is checked
+    /// against these extents on the host.  `views` is host memory and free again when the call returns.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn analyze_mixed_views_device(&mut self, views: &[Lc3GpuView], d_in: *const u8, in_bytes: usize, d_bad_frame: *const u8, n_flags: usize,
+                                             d_energy: *mut f32, n_energy: usize, d_bands: *mut f32, n_bands: usize, d_spec: *mut f32, n_spec: usize,
+                                             hip_stream: *mut c_void) -> i32 {
+        lc3gpu_analyze_mixed_views(self.h, views.as_ptr(), views.len() as i32, d_in, in_bytes, d_bad_frame, n_flags, d_energy, n_energy, d_bands, n_bands,
+                                   d_spec, n_spec, hip_stream)
+    }
+}
+impl Drop for Lc3AnalyzerGpu {
+    fn drop(&mut self) {
+        unsafe {
+            lc3gpu_analyzer_destroy(self.h);
         }
     }
 }
