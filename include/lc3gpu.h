@@ -648,6 +648,91 @@ int lc3gpu_analyze_mixed_views(lc3gpu_analyzer *an, const lc3gpu_view *views, in
                                float *d_bands, size_t n_bands,     /* n_bands rows of LC3GPU_BANDS floats, or NULL */
                                float *d_spec, size_t n_spec,       /* n_spec rows of LC3GPU_SPEC_LINES floats, or NULL */
                                void *hip_stream);
+/* Room mixes over two lists of VIEWS: the middle step of a mixing server's tick -- decode what every participant sent
+ * (lc3gpu_decode_mixed_views), mix per room, encode what every participant gets (lc3gpu_encode_mixed_views) -- on the tick's own view
+ * arrays, the PCM read where the decoder wrote it and written where the encoder reads it, in one launch: no gather or scatter pass runs
+ * around the call.  The reference has no mixer; the anchor is what a reference caller does between decode_frame and encode_frame
+ * (decoder/lc3_decoder.rs:217-234, encoder/lc3_encoder.rs:175-191): it sums the i16 samples it got in i32 and clamps to i16 as
+ * decoder/output_scaling.rs:24 clamps.  The definition is all-integer, so the result does not depend on the order of summation.
+ *   create    descs and n_streams are checked exactly as by lc3gpu_inspector_create: fs_hz one of the six rates (8 kHz included), frame_us
+ *             7500 or 10000 (LC3GPU_EINVAL otherwise), nbytes 1..400 (LC3GPU_ELENGTH otherwise); n_streams >= 1.  Only fs_hz and frame_us
+ *             are used afterwards.  max_views >= 1 bounds n_in + n_out of one call and sizes the pinned upload ring and its device twin
+ *             once (LC3GPU_EINVAL below 1).  The mixer is bound to the device that is current at creation, is not thread-safe and is
+ *             independent of every codec handle, of the inspector and of the analyzer.  No device: LC3GPU_ENODEVICE
+ *   views     in_views and out_views are HOST arrays and may be reused as soon as the call returns: the arrays the tick passes to
+ *             lc3gpu_decode_mixed_views and lc3gpu_encode_mixed_views.  Read: channel (index into the mixer's descriptors, giving the frame
+ *             length nf and the rate), n_frames, pcm_off, pcm_stride, pcm_pitch and reserved (0).  NOT read: nbytes, byte_off, byte_pitch,
+ *             flag_off, flag_pitch.  ins[i] belongs to in_views[i], outs[o] to out_views[o].  A mix carries no state: a channel and a
+ *             placement may be named by any number of input views, so one stream can feed two rooms.  Two outputs that write the same
+ *             sample are the caller's error: the content there is unspecified, every write is still inside the checked extents
+ *   bus       a bus is a room: 0 <= bus < max_views.  All views of a bus, inputs and outputs, have the same fs_hz and the same sample
+ *             count S = n_frames * nf: at one rate four 7.5 ms frames and three 10 ms frames mix; a 24 kHz / 10 ms and a 32 kHz / 7.5 ms
+ *             stream (240 samples per frame both) do not, nor do 44.1 kHz and 48 kHz
+ *   placement sample s of a view, 0 <= s < S, is d[pcm_off + (s / nf) * pitch + (s % nf) * pcm_stride] with pitch = pcm_pitch ? pcm_pitch
+ *             : nf * pcm_stride: exactly the views calls' rule
+ *   written   for every output o on bus b and every s, with in(i, s) the sample of input i:
+ *               term(i, s)  = ((int32)in(i, s) * gain_q14[i] + 8192) >> 14      (arithmetic shift: round to nearest, ties upward)
+ *               total(b, s) = sum of term(i, s) over the inputs i of bus b      (int32; 0 for a bus without inputs)
+ *               out(o, s)   = clamp(total(b, s) - (minus[o] >= 0 ? term(minus[o], s) : 0), -32768, 32767)
+ *             gain_q14 = 16384 is unity and gives term == in exactly.  minus is the index in in_views of the input this output does not
+ *             hear -- the participant's own, which makes the N-1 mix --, -1 for none.  Only the S samples of an output view are written:
+ *             everything between and around them is left as it was.  gain_q14 lies in -32768..32767, so |term| <= 65536; a bus holds at
+ *             most 16384 inputs, so |total| <= 2^30 and the subtraction cannot leave int32
+ *   checks    on the host before anything is queued; a refused call has launched nothing and written nothing:
+ *               channel outside [0, n_streams)                       LC3GPU_ECHANNEL
+ *               n_frames < 1                                         LC3GPU_ELENGTH
+ *               more than 2^31 - 1 samples in one view               LC3GPU_ELENGTH
+ *               any sample of any view outside [0, in_elems) /
+ *               [0, out_elems)                                       LC3GPU_ELENGTH
+ *               n_in + n_out > max_views                             LC3GPU_ELENGTH
+ *               more than 16384 inputs on one bus                    LC3GPU_ELENGTH
+ *               views of one bus with different S                    LC3GPU_ELENGTH
+ *               views of one bus with different fs_hz                LC3GPU_EINVAL
+ *               bus outside [0, max_views)                           LC3GPU_EINVAL
+ *               gain_q14 outside -32768..32767                       LC3GPU_EINVAL
+ *               minus outside [-1, n_in), or naming an input of
+ *               another bus                                          LC3GPU_EINVAL
+ *               pcm_stride outside 1..8                              LC3GPU_EINVAL
+ *               a negative pcm_off                                   LC3GPU_EINVAL
+ *               a non-zero pitch below nf * pcm_stride               LC3GPU_EINVAL
+ *               reserved != 0                                        LC3GPU_EINVAL
+ *               pcm_stride == 1 with an odd pcm_off, an odd pitch
+ *               or a base not 4-byte aligned                         LC3GPU_EINVAL
+ *               pcm_stride >= 2 with a base not 2-byte aligned       LC3GPU_EINVAL
+ *               [d_pcm_in, + 2 * in_elems) and [d_pcm_out,
+ *               + 2 * out_elems) overlapping                         LC3GPU_EINVAL
+ *               a null mx; a null array whose count is not 0; a
+ *               null PCM array whose views are not 0; negative counts LC3GPU_EINVAL
+ *               n_out == 0                                           LC3GPU_OK (nothing launched)
+ *               n_in == 0 with outputs                               LC3GPU_OK (the outputs are zeros)
+ *             the extent check works in unsigned 64-bit arithmetic that cannot wrap.  The two arrays may not overlap because a workgroup
+ *             must never overwrite what another still reads.  HIP errors: LC3GPU_EHIP
+ *   order     asynchronous on hip_stream, ordered as any kernel on that stream.  The host waits for the oldest of its own uploads only
+ *             when more calls are in flight than the ring has slots, as with the inspector
+ *   launches  ONE launch and ONE upload of O(views) bytes per call, whatever mix of rates, durations, frame counts and room sizes
+ * NOT provided (out of scope): resampling between rates, a gain per output, ramps across a tick, float or wider PCM, host-resident
+ * buffers, the pipeline object, uniform handles. */
+typedef struct lc3gpu_mixer lc3gpu_mixer;
+typedef struct lc3gpu_mix_in {
+    int32_t bus;      /* the room this input is heard in */
+    int32_t gain_q14; /* -32768..32767; 16384 = unity */
+} lc3gpu_mix_in;
+typedef struct lc3gpu_mix_out {
+    int32_t bus;   /* the room this output hears */
+    int32_t minus; /* index in in_views of the input it does not hear (its own); -1 = none */
+} lc3gpu_mix_out;
+#ifdef __cplusplus
+static_assert(sizeof(lc3gpu_mix_in) == 8, "lc3gpu_mix_in is 8 bytes");
+static_assert(sizeof(lc3gpu_mix_out) == 8, "lc3gpu_mix_out is 8 bytes");
+#else
+_Static_assert(sizeof(lc3gpu_mix_in) == 8, "lc3gpu_mix_in is 8 bytes");
+_Static_assert(sizeof(lc3gpu_mix_out) == 8, "lc3gpu_mix_out is 8 bytes");
+#endif
+int lc3gpu_mixer_create(lc3gpu_mixer **out, int n_streams, const lc3gpu_stream_desc *descs, int max_views);
+int lc3gpu_mixer_destroy(lc3gpu_mixer *mx);
+int lc3gpu_mix_mixed_views(lc3gpu_mixer *mx, const lc3gpu_view *in_views, const lc3gpu_mix_in *ins, int n_in, const int16_t *d_pcm_in,
+                           size_t in_elems, const lc3gpu_view *out_views, const lc3gpu_mix_out *outs, int n_out, int16_t *d_pcm_out,
+                           size_t out_elems, void *hip_stream);
 
 size_t lc3gpu_decoder_state_size(const lc3gpu_decoder *dec);
 int lc3gpu_decoder_state_save(lc3gpu_decoder *dec, void *host_dst, size_t nbytes);

@@ -308,6 +308,35 @@ private:
     lc3gpu_analyzer *h_ = nullptr;
 };
 
+// The mixer (lc3gpu_mix_mixed_views): the room mixes of a tick, the PCM read where Lc3Decoder::decode_mixed_views wrote it and written
+// where Lc3Encoder::encode_mixed_views reads it, in one launch; streams = the array of Lc3Decoder(streams) (only fs_hz and frame_us are
+// used), max_views the most input plus output views one call may name and the number of buses.  Independent of every codec handle, of the
+// inspector and of the analyzer
+class Lc3Mixer {
+public:
+    Lc3Mixer(const std::vector<lc3gpu_stream_desc> &streams, size_t max_views) {
+        int rc = lc3gpu_mixer_create(&h_, (int)streams.size(), streams.data(), (int)max_views);
+        if (rc) throw Error(rc, "Lc3Mixer::new");
+    }
+    ~Lc3Mixer() { lc3gpu_mixer_destroy(h_); }
+    Lc3Mixer(const Lc3Mixer &) = delete;
+    Lc3Mixer &operator=(const Lc3Mixer &) = delete;
+    // ins[i] belongs to in_views[i], outs[o] to out_views[o]: output o gets the clamped sum of its bus's inputs, each scaled by its gain_q14
+    // (16384 = unity), less the term of input outs[o].minus (-1: none).  d_pcm_in and d_pcm_out may not overlap
+    void mix_mixed_views(const std::vector<lc3gpu_view> &in_views, const std::vector<lc3gpu_mix_in> &ins, const int16_t *d_pcm_in, size_t in_elems,
+                         const std::vector<lc3gpu_view> &out_views, const std::vector<lc3gpu_mix_out> &outs, int16_t *d_pcm_out, size_t out_elems,
+                         void *hip_stream = nullptr) {
+        if (ins.size() != in_views.size() || outs.size() != out_views.size()) throw Error(LC3GPU_EINVAL, "mix_mixed_views");
+        int rc = lc3gpu_mix_mixed_views(h_, in_views.data(), ins.data(), (int)in_views.size(), d_pcm_in, in_elems, out_views.data(), outs.data(),
+                                        (int)out_views.size(), d_pcm_out, out_elems, hip_stream);
+        if (rc) throw Error(rc, "mix_mixed_views");
+    }
+    lc3gpu_mixer *handle() { return h_; }
+
+private:
+    lc3gpu_mixer *h_ = nullptr;
+};
+
 // ---- the reference's no_std / no-alloc API shape (lc3_encoder.rs:37-40,212-303, lc3_decoder.rs:56-60,247-310): the
 // number of channels is a compile-time constant instead of a constructor argument (`Lc3Encoder::<NUM_CH>::new(duration,
 // frequency, ..)`, `Lc3Encoder::<NUM_CH>::calc_working_buffer_lengths(duration, frequency)`; default 2 as in the

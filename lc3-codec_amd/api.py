@@ -23,7 +23,7 @@ _LIB = os.path.join(_HERE, "lib", os.environ.get("LC3GPU_LIB") or ("liblc3gpu_pr
 _SRC = os.path.join(_HERE, "csrc", "lc3gpu.hip")
 # host-only sources of the library on top of its own C ABI (the pipeline object): plain C++ beside the HIP translation units
 _HOST_SRCS = [os.path.join(_HERE, "csrc", "lc3gpu_pipeline.cpp"), os.path.join(_HERE, "csrc", "lc3gpu_inspector_api.cpp"),
-              os.path.join(_HERE, "csrc", "lc3gpu_analyzer_api.cpp")]
+              os.path.join(_HERE, "csrc", "lc3gpu_analyzer_api.cpp"), os.path.join(_HERE, "csrc", "lc3gpu_mixer_api.cpp")]
 # The companion library of the inspector (lc3gpu_inspect_mixed_views): device code of its own, beside whichever main library is built.  The
 # main library links it (run path $ORIGIN) and holds host-side entry points only, so its own kernels are what they were.
 _INSPECTOR_LIB = os.path.join(os.path.dirname(_LIB), "liblc3gpu_inspector.so")
@@ -34,6 +34,10 @@ _INSPECTOR_ONLY = ("lc3gpu_inspector.hip", "lc3_host_inspect_views.h")  # source
 _ANALYZER_LIB = os.path.join(os.path.dirname(_LIB), "liblc3gpu_analyzer.so")
 _ANALYZER_SRC = os.path.join(_HERE, "csrc", "lc3gpu_analyzer.hip")
 _ANALYZER_ONLY = ("lc3gpu_analyzer.hip", "lc3_host_analyze_views.h", "lc3_dev_dec_analyze.h")  # sources only the analyzer's unit sees
+# The companion library of the mixer (lc3gpu_mix_mixed_views), the third: one ordinary unit with its one kernel, built and linked the same way.
+_MIXER_LIB = os.path.join(os.path.dirname(_LIB), "liblc3gpu_mixer.so")
+_MIXER_SRC = os.path.join(_HERE, "csrc", "lc3gpu_mixer.hip")
+_MIXER_ONLY = ("lc3gpu_mixer.hip", "lc3_host_mix_views.h", "lc3_dev_mix.h")  # sources only the mixer's unit sees
 
 class Lc3GpuError(RuntimeError):
     def __init__(self, code, what=""):
@@ -82,6 +86,11 @@ def analyzer_library_path():
     return _ANALYZER_LIB
 
 
+def mixer_library_path():
+    """the companion library of the mixer (lc3gpu_mix_mixed_views), which the main library links"""
+    return _MIXER_LIB
+
+
 def _translation_units():
     """(kind, index) of every translation unit of the multi-unit build (csrc/lc3gpu.hip, "translation units"): the main unit (0: host
     side + the whole-source module's device code), the encoder kernels (1) and the decoder kernels (3) of every configuration view beyond
@@ -126,12 +135,13 @@ def build_native(force=False, verbose=False):
     when they differ; experiment builds need their own file name (LC3GPU_LIB) so that they never replace the default library.
     Every flavour links the inspector's companion library (csrc/lc3gpu_inspector.hip -> lib/liblc3gpu_inspector.so, one ordinary unit),
     which is built and stamped here first; its own sources are no part of what the main library's translation units are stamped with.
-    The analyzer's companion (csrc/lc3gpu_analyzer.hip -> lib/liblc3gpu_analyzer.so) is built, stamped and linked the same way."""
+    The analyzer's companion (csrc/lc3gpu_analyzer.hip -> lib/liblc3gpu_analyzer.so) and the mixer's (csrc/lc3gpu_mixer.hip ->
+    lib/liblc3gpu_mixer.so) are built, stamped and linked the same way."""
     srcs = [os.path.join(_HERE, "csrc", f) for f in os.listdir(os.path.join(_HERE, "csrc")) if f.endswith((".h", ".hip", ".cpp"))]
     srcs += [os.path.join(_ROOT, "include", "lc3gpu.h"), os.path.join(_ROOT, "tables", "lc3_tables.h")]
     src_hash = _sources_hash(srcs)  # taken BEFORE anything is compiled: what the objects below are guaranteed to be at least as old as
     # (the HIP translation units do not see the host-only sources: an edit there relinks the library without recompiling them)
-    dev_hash = _sources_hash([p_ for p_ in srcs if not p_.endswith(".cpp") and os.path.basename(p_) not in _INSPECTOR_ONLY + _ANALYZER_ONLY])
+    dev_hash = _sources_hash([p_ for p_ in srcs if not p_.endswith(".cpp") and os.path.basename(p_) not in _INSPECTOR_ONLY + _ANALYZER_ONLY + _MIXER_ONLY])
     extra = os.environ.get("LC3_HIPCC_EXTRA", "").split()  # compiler experiments
     extra_main = os.environ.get("LC3_HIPCC_EXTRA_MAIN", "").split()
     if (extra or extra_main) and not os.environ.get("LC3GPU_LIB"):
@@ -152,9 +162,11 @@ def build_native(force=False, verbose=False):
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function",
              "-Wno-missing-braces"]
     # the companions first (every flavour of the main library links the same ones): one ordinary unit each, stamped with the contents of
-    # the sources that unit can see (the inspector's stamp is what it was before the analyzer existed)
+    # the sources that unit can see (the inspector's and the analyzer's stamps are what they were before the mixer existed)
     force_link = False
-    for comp_lib, comp_src, hidden in ((_INSPECTOR_LIB, _INSPECTOR_SRC, _ANALYZER_ONLY), (_ANALYZER_LIB, _ANALYZER_SRC, ("lc3gpu_inspector.hip",))):
+    for comp_lib, comp_src, hidden in ((_INSPECTOR_LIB, _INSPECTOR_SRC, _ANALYZER_ONLY + _MIXER_ONLY),
+                                       (_ANALYZER_LIB, _ANALYZER_SRC, ("lc3gpu_inspector.hip",) + _MIXER_ONLY),
+                                       (_MIXER_LIB, _MIXER_SRC, ("lc3gpu_inspector.hip",) + _ANALYZER_ONLY)):
         comp_sig = "sources=%s\n" % _sources_hash([p_ for p_ in srcs if not p_.endswith(".cpp") and os.path.basename(p_) not in hidden])
         if force or not os.path.exists(comp_lib) or not stamped(comp_lib + ".stamp", comp_sig):
             tmp = comp_lib + ".tmp%d" % os.getpid()
@@ -172,7 +184,7 @@ def build_native(force=False, verbose=False):
             force_link = True
     if not force and not force_link and os.path.exists(_LIB) and stamped(stamp, sig):
         return _LIB
-    link_insp = ["-L" + os.path.dirname(_INSPECTOR_LIB), "-llc3gpu_inspector", "-llc3gpu_analyzer", "-Wl,-rpath,$ORIGIN"]
+    link_insp = ["-L" + os.path.dirname(_INSPECTOR_LIB), "-llc3gpu_inspector", "-llc3gpu_analyzer", "-llc3gpu_mixer", "-Wl,-rpath,$ORIGIN"]
     if single:
         cmd = ["hipcc"] + extra + (["-DLC3_PROFILE"] if _PROFILE else []) + flags + ["-shared", "-o", _LIB, _SRC] + _HOST_SRCS + link_insp
         if verbose:
@@ -318,6 +330,9 @@ def load_library():
     L.lc3gpu_analyzer_destroy.argtypes = [vp]
     L.lc3gpu_analyze_mixed_views.argtypes = [vp, vp, i, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp,
                                              ctypes.c_size_t, vp]
+    L.lc3gpu_mixer_create.argtypes = [ctypes.POINTER(vp), i, vp, i]
+    L.lc3gpu_mixer_destroy.argtypes = [vp]
+    L.lc3gpu_mix_mixed_views.argtypes = [vp, vp, vp, i, vp, ctypes.c_size_t, vp, vp, i, vp, ctypes.c_size_t, vp]
     L.lc3gpu_encoder_state_size.restype = ctypes.c_size_t
     L.lc3gpu_encoder_state_size.argtypes = [vp]
     L.lc3gpu_encoder_state_save.argtypes = [vp, vp, ctypes.c_size_t]
@@ -405,6 +420,7 @@ ABI_SYMBOLS = [
     "lc3gpu_encode_mixed_views", "lc3gpu_decode_mixed_views",
     "lc3gpu_inspector_create", "lc3gpu_inspector_destroy", "lc3gpu_inspect_mixed_views",
     "lc3gpu_analyzer_create", "lc3gpu_analyzer_destroy", "lc3gpu_analyze_mixed_views",
+    "lc3gpu_mixer_create", "lc3gpu_mixer_destroy", "lc3gpu_mix_mixed_views",
 ]
 
 # LC3GPU_SPEC_*: opt-in corrections of the reference's deviations from the LC3 specification (default 0 = reference behaviour)
@@ -1280,6 +1296,81 @@ def analyzer_plan_info(max_nbytes):
     if rc:
         raise Lc3GpuError(rc, "analyzer_plan_info")
     return fpb.value, lds.value, slots.value, words.value
+
+
+# room mixes (lc3gpu_mix_mixed_views): the entries of the two room tables (lc3gpu_mix_in, lc3gpu_mix_out, 8 bytes each) and unity gain
+MIX_IN_DTYPE = np.dtype([("bus", "<i4"), ("gain_q14", "<i4")])
+MIX_OUT_DTYPE = np.dtype([("bus", "<i4"), ("minus", "<i4")])
+MIX_UNITY = 16384
+
+
+def _mix_table(rows, dtype):
+    """a sequence of pairs, or an array of the table's dtype -> contiguous HOST array of it"""
+    if isinstance(rows, np.ndarray) and rows.dtype == dtype:
+        return np.ascontiguousarray(rows.reshape(-1))
+    rows = list(rows)
+    out = np.zeros(len(rows), dtype)
+    for k, r in enumerate(rows):
+        out[k] = (int(r[0]), int(r[1]))
+    return out
+
+
+class Lc3Mixer:
+    """lc3gpu_mixer: the room mixes of a tick, the PCM read where Lc3Decoder.decode_mixed_views wrote it and written where
+    Lc3Encoder.encode_mixed_views reads it, in one launch.  descs = [(fs_hz, frame_us, nbytes), ...] as for Lc3Decoder.mixed (only the
+    rate and the duration are used); max_views = the most input plus output views one call may name, and the number of buses.
+    Independent of every codec handle, of the inspector and of the analyzer; bound to the device current at creation."""
+
+    def __init__(self, descs, max_views):
+        self._L = load_library()
+        self.descs = [(int(d[0]), int(d[1]), int(d[2])) for d in descs]
+        self.num_channels = len(self.descs)
+        self.max_views = int(max_views)
+        h = ctypes.c_void_p()
+        rc = self._L.lc3gpu_mixer_create(ctypes.byref(h), self.num_channels, _desc_array(self.descs), self.max_views)
+        if rc:
+            raise Lc3GpuError(rc, "Lc3Mixer::new")
+        self._h = h
+
+    def mix_mixed_views(self, in_views, ins, d_pcm_in, out_views, outs, d_pcm_out, stream=None, in_elems=None, out_elems=None):
+        """one launch over all rooms.  ins[i] = (bus, gain_q14) belongs to in_views[i], outs[o] = (bus, minus) to out_views[o]; output o
+        gets, sample by sample, the clamped sum of ((in * gain_q14 + 8192) >> 14) over the inputs of its bus, less that term of input
+        `minus` (-1: none).  d_pcm_in / d_pcm_out: int16 device buffers that do not overlap; the extents (elements) default to the
+        buffers' sizes (lc3gpu_mix_mixed_views)"""
+        vi, vo = _view_list(in_views), _view_list(out_views)
+        ti, to = _mix_table(ins, MIX_IN_DTYPE), _mix_table(outs, MIX_OUT_DTYPE)
+        if ti.shape[0] != vi.shape[0] or to.shape[0] != vo.shape[0]:
+            raise ValueError("one (bus, gain_q14) per input view and one (bus, minus) per output view")
+        ie = (0 if d_pcm_in is None else _numel(d_pcm_in, "in_elems")) if in_elems is None else int(in_elems)
+        oe = (0 if d_pcm_out is None else _numel(d_pcm_out, "out_elems")) if out_elems is None else int(out_elems)
+        rc = self._L.lc3gpu_mix_mixed_views(self._h, _ptr(vi) if vi.shape[0] else None, _ptr(ti) if ti.shape[0] else None, int(vi.shape[0]),
+                                            _ptr(d_pcm_in), ie, _ptr(vo) if vo.shape[0] else None, _ptr(to) if to.shape[0] else None,
+                                            int(vo.shape[0]), _ptr(d_pcm_out), oe, _ptr(stream))
+        if rc:
+            raise Lc3GpuError(rc, "mix_mixed_views")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.lc3gpu_mixer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def mixer_plan_info():
+    """-> (samples of a bus per workgroup, lanes per workgroup, upload ring slots) of a mixer call: the plan's own figures, from the
+    companion library (tests and tools)"""
+    load_library()  # (the main library first: it brings the companion in, and the one HIP runtime of the process)
+    C = ctypes.CDLL(_MIXER_LIB)
+    spw, lanes, slots = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    rc = C.lc3mix_plan_info(ctypes.byref(spw), ctypes.byref(lanes), ctypes.byref(slots))
+    if rc:
+        raise Lc3GpuError(rc, "mixer_plan_info")
+    return spw.value, lanes.value, slots.value
 
 
 class PinnedBuffer:

@@ -18,7 +18,8 @@ HEADER = os.path.join(ROOT, "include", "lc3gpu.h")
 
 OPAQUE = {"lc3gpu_encoder": "Lc3GpuEncoder", "lc3gpu_decoder": "Lc3GpuDecoder", "lc3gpu_pipeline": "Lc3GpuPipeline",
           "lc3gpu_stream_desc": "Lc3GpuStreamDesc", "lc3gpu_frame_info": "Lc3GpuFrameInfo", "lc3gpu_item": "Lc3GpuItem", "lc3gpu_mc_item": "Lc3GpuMcItem",
-          "lc3gpu_view": "Lc3GpuView", "lc3gpu_inspector": "Lc3GpuInspector", "lc3gpu_analyzer": "Lc3GpuAnalyzer"}
+          "lc3gpu_view": "Lc3GpuView", "lc3gpu_inspector": "Lc3GpuInspector", "lc3gpu_analyzer": "Lc3GpuAnalyzer",
+          "lc3gpu_mixer": "Lc3GpuMixer", "lc3gpu_mix_in": "Lc3GpuMixIn", "lc3gpu_mix_out": "Lc3GpuMixOut"}
 SCALAR = {"int": "i32", "unsigned": "u32", "unsigned int": "u32", "float": "f32", "double": "f64", "size_t": "usize",
           "int16_t": "i16", "uint16_t": "u16", "uint8_t": "u8", "int32_t": "i32", "uint32_t": "u32", "int64_t": "i64", "uint64_t": "u64",
           "unsigned long long": "u64", "char": "c_char", "void": "c_void"}
@@ -442,6 +443,43 @@ impl Drop for Lc3AnalyzerGpu {
     }
 }
 
+/// The mixer (include/lc3gpu.h): the room mixes of a tick, the PCM read where `decode_mixed_views_device` wrote it and written where
+/// `encode_mixed_views_device` reads it, in one launch.  Independent of every codec handle, of the inspector and of the analyzer.
+pub struct Lc3MixerGpu {
+    h: *mut Lc3GpuMixer,
+}
+impl Lc3MixerGpu {
+    /// `descs`: the array the caller passes to lc3gpu_decoder_create_mixed (only fs_hz and frame_us are used); `max_views`: the most
+    /// input plus output views one call may name, and the number of buses
+    pub fn new(descs: &[Lc3GpuStreamDesc], max_views: usize) -> Result<Self, i32> {
+        let mut h = core::ptr::null_mut();
+        let rc = unsafe { lc3gpu_mixer_create(&mut h, descs.len() as i32, descs.as_ptr(), max_views as i32) };
+        if rc == LC3GPU_OK { Ok(Self { h }) } else { Err(rc) }
+    }
+    /// One launch over all rooms: output o gets, sample by sample, the clamped sum of its bus's inputs (each scaled by its gain_q14,
+    /// rounded to nearest) less the term of input `outs[o].minus`.  `ins[i]` belongs to `in_views[i]`, `outs[o]` to `out_views[o]`.
+    ///
+    /// # Safety
+    /// device allocations of at least `in_elems` and `out_elems` elements that do not overlap and outlive the call's work; every view is
+    /// checked against these extents on the host.  The four slices are host memory and free again when the call returns.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn mix_mixed_views_device(&mut self, in_views: &[Lc3GpuView], ins: &[Lc3GpuMixIn], d_pcm_in: *const i16, in_elems: usize,
+                                         out_views: &[Lc3GpuView], outs: &[Lc3GpuMixOut], d_pcm_out: *mut i16, out_elems: usize,
+                                         hip_stream: *mut c_void) -> i32 {
+        assert_eq!(in_views.len(), ins.len());
+        assert_eq!(out_views.len(), outs.len());
+        lc3gpu_mix_mixed_views(self.h, in_views.as_ptr(), ins.as_ptr(), in_views.len() as i32, d_pcm_in, in_elems, out_views.as_ptr(),
+                               outs.as_ptr(), out_views.len() as i32, d_pcm_out, out_elems, hip_stream)
+    }
+}
+impl Drop for Lc3MixerGpu {
+    fn drop(&mut self) {
+        unsafe {
+            lc3gpu_mixer_destroy(self.h);
+        }
+    }
+}
+
 /// Encode + decode of many channels in the arrangement that measured fastest (include/lc3gpu.h, "pipeline"): device buffers, asynchronous.
 pub struct Lc3PipelineGpu {
     h: *mut Lc3GpuPipeline,
@@ -485,7 +523,7 @@ def generate():
         "",
     ]
     for c, r in sorted(OPAQUE.items()):
-        if c in ("lc3gpu_stream_desc", "lc3gpu_frame_info", "lc3gpu_item", "lc3gpu_mc_item", "lc3gpu_view"):
+        if c in ("lc3gpu_stream_desc", "lc3gpu_frame_info", "lc3gpu_item", "lc3gpu_mc_item", "lc3gpu_view", "lc3gpu_mix_in", "lc3gpu_mix_out"):
             continue
         lines += ["#[repr(C)]", "pub struct %s {" % r, "    _private: [u8; 0],", "}"]
     lines += ["/// one stream of a mixed-configuration handle (lc3gpu_stream_desc)", "#[repr(C)]", "#[derive(Clone, Copy, Debug)]",
@@ -504,6 +542,12 @@ def generate():
               "    pub nbytes: i32,", "    pub pcm_stride: i32,", "    pub pcm_off: i64,", "    pub byte_off: i64,", "    pub flag_off: i64,",
               "    pub pcm_pitch: i32,", "    pub byte_pitch: i32,", "    pub flag_pitch: i32,", "    pub reserved: [i32; 3],", "}",
               "const _: () = assert!(core::mem::size_of::<Lc3GpuView>() == 64);"]
+    lines += ["/// one input of lc3gpu_mix_mixed_views (lc3gpu_mix_in, 8 bytes): the room it is heard in and its gain (16384 = unity)",
+              "#[repr(C)]", "#[derive(Clone, Copy, Debug, Default)]", "pub struct Lc3GpuMixIn {", "    pub bus: i32,", "    pub gain_q14: i32,", "}",
+              "const _: () = assert!(core::mem::size_of::<Lc3GpuMixIn>() == 8);"]
+    lines += ["/// one output of lc3gpu_mix_mixed_views (lc3gpu_mix_out, 8 bytes): the room it hears and the input it does not hear (-1 = none)",
+              "#[repr(C)]", "#[derive(Clone, Copy, Debug, Default)]", "pub struct Lc3GpuMixOut {", "    pub bus: i32,", "    pub minus: i32,", "}",
+              "const _: () = assert!(core::mem::size_of::<Lc3GpuMixOut>() == 8);"]
     lines += ["/// one frame's record of lc3gpu_inspect (lc3gpu_frame_info, 128 bytes): status LC3GPU_FRAME_*, the side information",
               "/// (decoder/side_info.rs:20-31) and the arithmetic data (decoder/arithmetic_codec.rs:99-107)", "#[repr(C)]",
               "#[derive(Clone, Copy, Debug, Default)]", "pub struct Lc3GpuFrameInfo {"]
