@@ -749,6 +749,11 @@ int lc3gpu_decoder_plc_events(lc3gpu_decoder *dec, uint64_t *out);
  * A caller need not poll: the handle's next batch call returns LC3GPU_EPAIR (once) when a pair half of an earlier call gave up. */
 int lc3gpu_encoder_pair_timeouts(lc3gpu_encoder *enc, uint64_t *out);
 int lc3gpu_decoder_pair_timeouts(lc3gpu_decoder *dec, uint64_t *out);
+/* A look at the flag behind LC3GPU_EPAIR that changes nothing: 1 if the handle's next batch call would return LC3GPU_EPAIR, else 0
+ * (read from pinned host memory: no synchronisation, no wait).  For a caller that drives several handles as one unit and must know
+ * that all of them can take a call before the first one launches (the pipeline object does). */
+int lc3gpu_encoder_pair_pending(const lc3gpu_encoder *enc);
+int lc3gpu_decoder_pair_pending(const lc3gpu_decoder *dec);
 /* tests only: make the device do what a pair half that gives up does (count + host flag), so that the LC3GPU_EPAIR path can be exercised */
 int lc3gpu_encoder_debug_pair_giveup(lc3gpu_encoder *enc);
 int lc3gpu_decoder_debug_pair_giveup(lc3gpu_decoder *dec);
@@ -792,16 +797,39 @@ int lc3gpu_host_free(void *p);
  *   lc3gpu_pipeline_mark     records `hip_event` (a hipEvent_t of the caller's) on the LAST group's stream behind its latest work: a
  *                            progress mark / timing point that costs the pipeline nothing -- `join` puts event waits on a further stream, and
  *                            a waiting stream can hold up a pipeline stream that shares its hardware queue (measured: -10 % with a join
- *                            after every submission).  The groups are not tied to each other: the mark says nothing about the other groups
+ *                            after every submission).  The groups are not tied to each other: the mark says nothing about the other groups.
+ *                            "Latest work" is the encoder's and the decoder's: after a round trip the decoder stream is behind both and
+ *                            the mark is a bare event record; where the group's decoder stream is not behind its encoder's latest work
+ *                            (an lc3gpu_pipeline_encode after a decode, halves on unrelated buffers) the decoder stream first waits for
+ *                            it, unless it has completed -- the one case in which a mark queues a wait on a pipeline stream
  *   lc3gpu_pipeline_group    the channel range and the handles of a group (borrowed: state blobs, PLC / health counters, timing,
  *                            stage events; never destroy them, never call their batch functions while the pipeline has work in flight)
- *   lc3gpu_pipeline_reset    every channel back to the freshly constructed state from the next submission on (no wait)
- * Errors as the batch calls (LC3GPU_EPAIR included).
+ *   lc3gpu_pipeline_reset    every channel back to the freshly constructed state from the next submission on (no wait; the decoders of a
+ *                            MIXED pipeline carry the reset out at their next decode, which synchronises the device once per group)
+ * What the pipeline orders: the BYTE buffers.  An encoder never overwrites bytes that a decoder of an earlier submission still reads or
+ * that another encoder still writes, a decoder never reads bytes before the encoder that writes them has finished -- whichever group
+ * queued the earlier work, also when the base pointer, n_frames or nbytes change between submissions into the same memory (a group's
+ * slice of a buffer depends on all three; a submission whose geometry does not fit the ones before it puts every stream's next work
+ * behind the other groups' latest work once, on the device).  Up to four byte buffers of one n_frames and nbytes in rotation cost nothing.
+ * What the caller orders: the PCM buffers, d_bad_frame, and whatever its own streams do.  d_pcm must be complete when the submission
+ * that reads it is queued, or be produced on a stream that lc3gpu_pipeline_follow names right before that submission; d_pcm_out may be
+ * consumed after lc3gpu_pipeline_wait or on a stream behind lc3gpu_pipeline_join, and the submission that overwrites it while such a
+ * consumer may still read goes behind a follow of that stream.  A transcoding chain (d_pcm_out of one submission as d_pcm of a later
+ * one) needs join + follow through a stream of the caller's, or a wait, between the two; so does an output buffer that an encoder in
+ * flight reads.  An output buffer written again with another n_frames (the groups' slices move) needs a wait first.
+ * Errors as the batch calls (nbytes 20..400 where the call encodes, 1..400 for a decode alone; d_pcm and d_pcm_out 4-byte aligned), and
+ * all or nothing: the arguments and every group's pair flag are looked at before the first group launches, so a call that refuses its
+ * arguments, or returns LC3GPU_EPAIR for a flag that was up when the call began, has queued nothing on any group and may be repeated;
+ * with flags up on several handles there is one refusal each.  The device raises a flag from work in flight: one that rises DURING a
+ * call is reported by the call after it, or -- if it rises after the look and before that group's own turn -- by this one with
+ * earlier groups already launched (no such window when nothing is in flight, i.e. after lc3gpu_pipeline_wait).  After LC3GPU_EHIP
+ * some groups may have launched and others not: the pipeline must be reset (lc3gpu_pipeline_reset) before further use.
  * Mixed configurations (lc3gpu_pipeline_create_mixed, BASELINE config 4 through the pipeline): streams of different rates, durations and frame
  * sizes, descriptors and ragged buffers as for lc3gpu_*_create_mixed / lc3gpu_encode_mixed (8 kHz streams are refused: a pipeline encodes and
  * decodes); group g takes the descriptors [group_first[g], group_first[g + 1]) (group_first[0] = 0, ascending, n_groups entries; NULL: equal
- * shares of the list) -- order the list so that every group holds a share of every configuration.  The *_mixed calls take the place of
- * submit / encode / decode (LC3GPU_EINVAL for the other kind); everything else is common. */
+ * shares of the list; with boundaries given, n_groups is theirs: 0 or more than n_streams is LC3GPU_EINVAL) -- order the list so that every
+ * group holds a share of every configuration.  The *_mixed calls take the place of submit / encode / decode (LC3GPU_EINVAL for the
+ * other kind); everything else is common. */
 typedef struct lc3gpu_pipeline lc3gpu_pipeline;
 int lc3gpu_pipeline_create(lc3gpu_pipeline **out, int num_channels, int frame_us, int fs_hz, int n_groups);
 int lc3gpu_pipeline_create_mixed(lc3gpu_pipeline **out, int n_streams, const lc3gpu_stream_desc *descs, int n_groups, const int *group_first);

@@ -130,6 +130,12 @@ public:
         if (rc) throw Error(rc, "pair_timeouts");
         return v;
     }
+    // the handle's next batch call would return LC3GPU_EPAIR (looked at, not lowered)
+    bool pair_pending() const {
+        int rc = lc3gpu_encoder_pair_pending(h_);
+        if (rc < 0) throw Error(rc, "pair_pending");
+        return rc != 0;
+    }
     lc3gpu_encoder *handle() { return h_; }
 
 private:
@@ -238,6 +244,12 @@ public:
         int rc = lc3gpu_decoder_pair_timeouts(h_, &v);
         if (rc) throw Error(rc, "pair_timeouts");
         return v;
+    }
+    // the handle's next batch call would return LC3GPU_EPAIR (looked at, not lowered)
+    bool pair_pending() const {
+        int rc = lc3gpu_decoder_pair_pending(h_);
+        if (rc < 0) throw Error(rc, "pair_pending");
+        return rc != 0;
     }
     lc3gpu_decoder *handle() { return h_; }
 

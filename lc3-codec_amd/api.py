@@ -370,6 +370,8 @@ def load_library():
     L.lc3gpu_decoder_bind_stream.argtypes = [vp, vp, i]
     L.lc3gpu_encoder_debug_pair_giveup.argtypes = [vp]
     L.lc3gpu_decoder_debug_pair_giveup.argtypes = [vp]
+    L.lc3gpu_encoder_pair_pending.argtypes = [vp]
+    L.lc3gpu_decoder_pair_pending.argtypes = [vp]
     L.lc3gpu_encode_host.argtypes = [vp, vp, vp, i, i]
     L.lc3gpu_decode_host.argtypes = [vp, vp, vp, vp, i, i]
     L.lc3gpu_host_alloc.argtypes = [ctypes.POINTER(vp), ctypes.c_size_t]
@@ -407,7 +409,7 @@ ABI_SYMBOLS = [
     "lc3gpu_decoder_timing_kernels", "lc3gpu_decode_frame_debug", "lc3gpu_decoder_synth_debug", "lc3gpu_selftest_math", "lc3gpu_encode_layout", "lc3gpu_decode_layout", "lc3gpu_encoder_create_mixed", "lc3gpu_decoder_create_mixed", "lc3gpu_encode_mixed",
     "lc3gpu_decode_mixed", "lc3gpu_encoder_create_spec", "lc3gpu_encoder_create_mixed_spec", "lc3gpu_clock_probe",
     "lc3gpu_encoder_stage_event", "lc3gpu_decoder_stage_event", "lc3gpu_encoder_pair_timeouts", "lc3gpu_decoder_pair_timeouts",
-    "lc3gpu_encoder_debug_pair_giveup", "lc3gpu_decoder_debug_pair_giveup", "lc3gpu_encoder_bind_stream", "lc3gpu_decoder_bind_stream", "lc3gpu_encode_host", "lc3gpu_decode_host", "lc3gpu_host_alloc",
+    "lc3gpu_encoder_debug_pair_giveup", "lc3gpu_decoder_debug_pair_giveup", "lc3gpu_encoder_pair_pending", "lc3gpu_decoder_pair_pending", "lc3gpu_encoder_bind_stream", "lc3gpu_decoder_bind_stream", "lc3gpu_encode_host", "lc3gpu_decode_host", "lc3gpu_host_alloc",
     "lc3gpu_host_free", "lc3gpu_pipeline_create", "lc3gpu_pipeline_create_mixed", "lc3gpu_pipeline_submit_mixed", "lc3gpu_pipeline_encode_mixed",
     "lc3gpu_pipeline_decode_mixed", "lc3gpu_pipeline_destroy", "lc3gpu_pipeline_reset", "lc3gpu_pipeline_submit",
     "lc3gpu_pipeline_encode", "lc3gpu_pipeline_decode", "lc3gpu_pipeline_wait", "lc3gpu_pipeline_join", "lc3gpu_pipeline_follow", "lc3gpu_pipeline_mark",
@@ -835,6 +837,13 @@ class Lc3Encoder:
         if rc:
             raise Lc3EncoderError(rc, "debug_pair_giveup")
 
+    def pair_pending(self):
+        """True if the handle's next batch call would return LC3GPU_EPAIR; looks at the flag and leaves it up (lc3gpu_encoder_pair_pending)"""
+        rc = self._L.lc3gpu_encoder_pair_pending(self._h)
+        if rc < 0:
+            raise Lc3EncoderError(rc, "pair_pending")
+        return bool(rc)
+
     def pair_timeouts(self):
         """producer / consumer pair halves of the packer that ever gave up on their partner (include/lc3gpu.h); 0 unless a wave died"""
         v = ctypes.c_uint64()
@@ -1104,6 +1113,13 @@ class Lc3Decoder:
         rc = self._L.lc3gpu_decoder_debug_pair_giveup(self._h)
         if rc:
             raise Lc3DecoderError(rc, "debug_pair_giveup")
+
+    def pair_pending(self):
+        """True if the handle's next batch call would return LC3GPU_EPAIR; looks at the flag and leaves it up (lc3gpu_decoder_pair_pending)"""
+        rc = self._L.lc3gpu_decoder_pair_pending(self._h)
+        if rc < 0:
+            raise Lc3DecoderError(rc, "pair_pending")
+        return bool(rc)
 
     def pair_timeouts(self):
         """producer / consumer pair halves of the parser that ever gave up on their partner (include/lc3gpu.h); 0 unless a wave died"""

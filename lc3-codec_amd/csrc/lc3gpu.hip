@@ -6013,6 +6013,15 @@ int lc3gpu_decoder_pair_timeouts(lc3gpu_decoder *d, uint64_t *out) {
     LC3_ON_DEVICE(d);
     return pair_timeouts_read(*d, out);
 }
+// the flag order_begin reports as LC3GPU_EPAIR, looked at and left as it is (one word of pinned host memory: no wait, no device call)
+int lc3gpu_encoder_pair_pending(const lc3gpu_encoder *e) {
+    if (!e) return LC3GPU_EINVAL;
+    return e->h_pc_flag && *e->h_pc_flag ? 1 : 0;
+}
+int lc3gpu_decoder_pair_pending(const lc3gpu_decoder *d) {
+    if (!d) return LC3GPU_EINVAL;
+    return d->h_pc_flag && *d->h_pc_flag ? 1 : 0;
+}
 
 // per-kernel timing (HIP events on the launch stream).  enable = 1 starts recording every batch launch, reading
 // synchronises and returns the per-kernel totals since the last read.

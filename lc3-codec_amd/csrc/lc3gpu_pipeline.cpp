@@ -17,6 +17,7 @@
 // Buffers are planar (LC3GPU_LAYOUT_PLANAR): a group's channels are a contiguous slice of every buffer.
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -39,9 +40,14 @@ struct Group {
     const uint8_t *bytes_lo[2] = {nullptr, nullptr}, *bytes_hi[2] = {nullptr, nullptr};
     // the byte range the encoder of that submission WRITES and a decoder of the same or a later submission may read
     const uint8_t *ebytes_lo[2] = {nullptr, nullptr}, *ebytes_hi[2] = {nullptr, nullptr};
-    // the PCM range the decoder of that submission WRITES (a later encoder may read it: a transcoding chain)
+    // (PCM buffers are not tracked: the caller orders them, see include/lc3gpu.h)
     int last_enc = -1, last_dec = -1;  // slot of the latest encoder / decoder work (for wait / join)
     unsigned long long n_enc = 0, n_dec = 0;  // pieces of work queued per role (a role's slot = its count & 1)
+    // the latest decoder work is ordered behind the latest encoder work (it waited for it, or the host saw it completed): the decoder
+    // stream alone then stands for "the group's latest work" (lc3gpu_pipeline_mark)
+    bool dec_covers_enc = false;
+    // the geometry epoch (lc3gpu_pipeline::epoch) up to which each stream has been ordered behind the OTHER groups' work
+    unsigned long long enc_epoch = 0, dec_epoch = 0;
     // mixed-configuration pipelines (ragged buffers, streams in descriptor order): per FRAME of a submission, the int16 samples and the
     // bytes of the streams before this group, and of this group's own streams
     size_t pcm_before = 0, bytes_before = 0, pcm_own = 0, bytes_own = 0;
@@ -58,6 +64,15 @@ struct lc3gpu_pipeline {
     hipEvent_t ev_follow = nullptr;
     bool follow_pending = false;
     int last_hip = 0;
+    // Hazards are tracked per group, and that is enough while a group's slice of the byte buffers stays where it is.  The slice depends on
+    // the submission's geometry -- base pointer, n_frames, nbytes --: the geometries of the current EPOCH are mutually compatible (the
+    // same n_frames and nbytes; the same base, or whole buffers that do not touch), so within an epoch a group's slice can only overlap
+    // slices of the same group.  A submission that fits no such set opens a new epoch, and the first work of every stream in a new epoch
+    // goes behind the other groups' latest work (pipeline_step).  Pointer comparisons on the host only: the steady state queues and asks
+    // nothing for it.
+    int geo_n_frames = 0, geo_nbytes = 0, geo_n = 0;
+    const uint8_t *geo_lo[4] = {nullptr, nullptr, nullptr, nullptr}, *geo_hi[4] = {nullptr, nullptr, nullptr, nullptr};
+    unsigned long long epoch = 0;
 };
 
 namespace {
@@ -221,6 +236,8 @@ int lc3gpu_pipeline_create(lc3gpu_pipeline **out, int num_channels, int frame_us
 int lc3gpu_pipeline_create_mixed(lc3gpu_pipeline **out, int n_streams, const lc3gpu_stream_desc *descs, int n_groups, const int *group_first) {
     if (!out || n_streams <= 0 || !descs || n_groups < 0 || n_groups > 8) return LC3GPU_EINVAL;
     *out = nullptr;
+    // (given boundaries are n_groups entries of the caller's: a default or a clamped count would read or reinterpret them)
+    if (group_first && (n_groups == 0 || n_groups > n_streams)) return LC3GPU_EINVAL;
     if (lc3gpu_device_count() <= 0) return LC3GPU_ENODEVICE;
     if (n_groups == 0) n_groups = 2;
     if (n_groups > n_streams) n_groups = n_streams;
@@ -286,34 +303,54 @@ int lc3gpu_pipeline_group(lc3gpu_pipeline *p, int group, int *first_channel, int
 
 int lc3gpu_pipeline_last_hip_error(const lc3gpu_pipeline *p) { return p ? p->last_hip : 0; }
 
+// An event that has already completed orders nothing, and a wait for it would still cost the stream a barrier packet (~5 us of queue
+// time each; four of them per submission measured 1.7 % of the step): the host asks first.  A caller that stays a couple of submissions
+// ahead of the device -- a service ticking every 10 ms -- then queues none for the byte buffers; one that runs far ahead queues them all.
+static int wait_unless_done(lc3gpu_pipeline *p, hipStream_t s, hipEvent_t ev) {
+    if (hipEventQuery(ev) == hipSuccess) return LC3GPU_OK;
+    (void)hipGetLastError();  // (hipErrorNotReady is not an error)
+    PL_HIP(p, hipStreamWaitEvent(s, ev, 0));
+    return LC3GPU_OK;
+}
+
 // Hazards between the two streams of a group.  Each role keeps the records of its two most recent submissions (slot = the role's own
 // count & 1): the byte range it read (decoder) or wrote (encoder) and an event behind its work.  A new piece of work waits for the
 // other role's records it overlaps; records that have been dropped are all OLDER than both live ones, so when nothing live overlaps and
 // something has been dropped, waiting for the older live record orders the work behind every dropped one as well (a caller rotating three
 // byte buffers, halves submitted alone in any order).  In the round trip with two alternating byte buffers this is exactly one wait per
 // role and submission: the encoder of submission k behind the decoder of k - 2, the decoder behind its own encoder.
+// *behind_newest: the work is ordered behind the other role's latest record (it waits for it, or the host saw it completed)
 static int wait_for_other_role(lc3gpu_pipeline *p, hipStream_t s, const uint8_t *lo, const uint8_t *hi, const hipEvent_t (&ev)[2], const bool (&rec)[2],
-                               const uint8_t *const (&r_lo)[2], const uint8_t *const (&r_hi)[2], unsigned long long count) {
+                               const uint8_t *const (&r_lo)[2], const uint8_t *const (&r_hi)[2], unsigned long long count, bool *behind_newest) {
+    *behind_newest = false;
     if (count == 0) return LC3GPU_OK;
     const int newer = (int)((count - 1) & 1ull), older = newer ^ 1;
-    // An event that has already completed orders nothing, and a wait for it would still cost the stream a barrier packet (~5 us of queue
-    // time each; four of them per submission measured 1.7 % of the step): the host asks first.  A caller that stays a couple of submissions
-    // ahead of the device -- a service ticking every 10 ms -- then queues none for the byte buffers; one that runs far ahead queues them all.
-    auto wait = [&](int i) -> int {
-        if (hipEventQuery(ev[i]) == hipSuccess) return LC3GPU_OK;
-        (void)hipGetLastError();  // (hipErrorNotReady is not an error)
-        PL_HIP(p, hipStreamWaitEvent(s, ev[i], 0));
-        return LC3GPU_OK;
-    };
     bool any = false;
     for (int i : {newer, older})
         if (rec[i] && overlaps(lo, hi, r_lo[i], r_hi[i])) {
-            const int rc = wait(i);
+            const int rc = wait_unless_done(p, s, ev[i]);
             if (rc) return rc;
             any = true;
-            if (i == newer) break;  // (the newer record's event is behind the older one's on the same stream)
+            if (i == newer) {  // (the newer record's event is behind the older one's on the same stream)
+                *behind_newest = true;
+                break;
+            }
         }
-    if (!any && count > 2 && rec[older]) return wait(older);
+    if (!any && count > 2 && rec[older]) return wait_unless_done(p, s, ev[older]);
+    return LC3GPU_OK;
+}
+
+// The first work of a stream in a new geometry epoch (lc3gpu_pipeline::geo_*): behind the latest work of the OTHER groups that can touch
+// the same bytes -- an encoder behind their encoders (it overwrites what they wrote) and their decoders (it overwrites what they read), a
+// decoder behind their encoders.  A stream's latest event is behind everything the stream ever held, dropped records included.
+static int catch_up_with_other_groups(lc3gpu_pipeline *p, const Group &q, bool is_enc) {
+    for (const Group &o : p->groups) {
+        if (&o == &q) continue;
+        int rc = LC3GPU_OK;
+        if (o.last_enc >= 0) rc = wait_unless_done(p, is_enc ? q.s_enc : q.s_dec, o.enc_done[o.last_enc]);
+        if (rc == LC3GPU_OK && is_enc && o.last_dec >= 0) rc = wait_unless_done(p, q.s_enc, o.dec_done[o.last_dec]);
+        if (rc) return rc;
+    }
     return LC3GPU_OK;
 }
 
@@ -323,8 +360,50 @@ static int pipeline_step(lc3gpu_pipeline *p, int what, const int16_t *d_pcm, uin
     if (!p || !d_bytes || ((what & 1) && !d_pcm) || ((what & 2) && !d_pcm_out)) return LC3GPU_EINVAL;
     if (n_frames <= 0) return LC3GPU_ELENGTH;
     if (p->mixed != (nbytes < 0)) return LC3GPU_EINVAL;  // (the mixed entry points pass nbytes = -1: frame sizes are the descriptors')
+    // what every handle would refuse, refused here before any group launches (as encode_launch / decode_launch of lc3gpu.hip: an encoder
+    // takes 20..400 bytes per frame, a decoder 1..400; planar PCM is read and written as 32-bit words, and every group's offset keeps
+    // the base pointer's alignment)
+    if (!p->mixed && (nbytes < ((what & 1) ? 20 : 1) || nbytes > 400)) return LC3GPU_ELENGTH;
+    if (((what & 1) && ((uintptr_t)d_pcm & 3u) != 0) || ((what & 2) && ((uintptr_t)d_pcm_out & 3u) != 0)) return LC3GPU_EINVAL;
     DeviceGuard dg(p->device);
     int rc = LC3GPU_OK;
+    // All or nothing: a call queues nothing unless every group can take it.  The one refusal a handle makes that no argument check
+    // foresees is its pair flag (LC3GPU_EPAIR): a group whose flag is up gets its call -- which returns the code, lowers the flag and
+    // launches nothing -- before any group has launched, so that the caller may repeat the submission as the code's contract says.
+    for (Group &q : p->groups) {
+        if ((what & 1) && lc3gpu_encoder_pair_pending(q.enc) > 0) {
+            rc = p->mixed ? lc3gpu_encode_mixed(q.enc, d_pcm, d_bytes, n_frames, q.s_enc) : lc3gpu_encode(q.enc, d_pcm, d_bytes, nbytes, n_frames, q.s_enc);
+            return rc ? rc : LC3GPU_EPAIR;
+        }
+        if ((what & 2) && lc3gpu_decoder_pair_pending(q.dec) > 0) {
+            rc = p->mixed ? lc3gpu_decode_mixed(q.dec, d_bytes, nullptr, d_pcm_out, n_frames, q.s_dec)
+                          : lc3gpu_decode(q.dec, d_bytes, nullptr, d_pcm_out, nbytes, n_frames, q.s_dec);
+            return rc ? rc : LC3GPU_EPAIR;
+        }
+    }
+    {  // the geometry of this submission against those of the current epoch (see lc3gpu_pipeline::geo_*)
+        const Group &last = p->groups.back();
+        const uint8_t *lo = d_bytes;
+        const uint8_t *hi = lo + (p->mixed ? (last.bytes_before + last.bytes_own) : (size_t)p->num_channels * (size_t)nbytes) * (size_t)n_frames;
+        bool fits = p->geo_n == 0 || (n_frames == p->geo_n_frames && nbytes == p->geo_nbytes);
+        bool known = false;
+        for (int i = 0; i < p->geo_n && fits && !known; i++) {
+            if (lo == p->geo_lo[i]) known = true;
+            else if (overlaps(lo, hi, p->geo_lo[i], p->geo_hi[i])) fits = false;
+        }
+        if (fits && !known && p->geo_n == 4) fits = false;  // (more buffers than are remembered: start over rather than forget one)
+        if (!fits) {
+            p->epoch++;
+            p->geo_n = 0;
+        }
+        if (!known || !fits) {
+            p->geo_lo[p->geo_n] = lo;
+            p->geo_hi[p->geo_n] = hi;
+            p->geo_n++;
+            p->geo_n_frames = n_frames;
+            p->geo_nbytes = nbytes;
+        }
+    }
     for (Group &q : p->groups) {
         // the group's slice of every buffer: uniform [channel][frame][..] planar; mixed ragged, streams in descriptor order
         const size_t f0 = (size_t)q.first * (size_t)n_frames;
@@ -333,9 +412,14 @@ static int pipeline_step(lc3gpu_pipeline *p, int what, const int16_t *d_pcm, uin
         const size_t bytes_len = p->mixed ? q.bytes_own * (size_t)n_frames : (size_t)q.n * (size_t)n_frames * (size_t)nbytes;
         uint8_t *bytes = d_bytes + bytes_off;
         const uint8_t *bytes_end = bytes + bytes_len;
+        bool behind_newest = false;
         if (what & 1) {
+            if (q.enc_epoch != p->epoch) {
+                if ((rc = catch_up_with_other_groups(p, q, true)) != 0) return rc;
+                q.enc_epoch = p->epoch;
+            }
             // the encoder may not overwrite bytes a decoder still reads
-            if ((rc = wait_for_other_role(p, q.s_enc, bytes, bytes_end, q.dec_done, q.dec_rec, q.bytes_lo, q.bytes_hi, q.n_dec)) != 0) return rc;
+            if ((rc = wait_for_other_role(p, q.s_enc, bytes, bytes_end, q.dec_done, q.dec_rec, q.bytes_lo, q.bytes_hi, q.n_dec, &behind_newest)) != 0) return rc;
             if ((rc = follow_wait(p, q.s_enc)) != 0) return rc;
             rc = p->mixed ? lc3gpu_encode_mixed(q.enc, d_pcm + pcm_off, bytes, n_frames, q.s_enc)
                           : lc3gpu_encode(q.enc, d_pcm + pcm_off, bytes, nbytes, n_frames, q.s_enc);
@@ -347,10 +431,15 @@ static int pipeline_step(lc3gpu_pipeline *p, int what, const int16_t *d_pcm, uin
             q.ebytes_hi[b] = bytes_end;
             q.last_enc = b;
             q.n_enc++;
+            q.dec_covers_enc = false;
         }
         if (what & 2) {
+            if (q.dec_epoch != p->epoch) {
+                if ((rc = catch_up_with_other_groups(p, q, false)) != 0) return rc;
+                q.dec_epoch = p->epoch;
+            }
             // the decoder reads what an encoder in flight writes: this submission's own (a round trip) or an earlier lc3gpu_pipeline_encode's
-            if ((rc = wait_for_other_role(p, q.s_dec, bytes, bytes_end, q.enc_done, q.enc_rec, q.ebytes_lo, q.ebytes_hi, q.n_enc)) != 0) return rc;
+            if ((rc = wait_for_other_role(p, q.s_dec, bytes, bytes_end, q.enc_done, q.enc_rec, q.ebytes_lo, q.ebytes_hi, q.n_enc, &behind_newest)) != 0) return rc;
             if ((rc = follow_wait(p, q.s_dec)) != 0) return rc;
             const uint8_t *bad = d_bad ? d_bad + f0 : nullptr;
             rc = p->mixed ? lc3gpu_decode_mixed(q.dec, bytes, bad, d_pcm_out + pcm_off, n_frames, q.s_dec)
@@ -363,6 +452,7 @@ static int pipeline_step(lc3gpu_pipeline *p, int what, const int16_t *d_pcm, uin
             q.bytes_hi[b] = bytes_end;
             q.last_dec = b;
             q.n_dec++;
+            q.dec_covers_enc = behind_newest;
         }
     }
     p->follow_pending = false;
@@ -413,7 +503,15 @@ int lc3gpu_pipeline_join(lc3gpu_pipeline *p, void *hip_stream) {
 int lc3gpu_pipeline_mark(lc3gpu_pipeline *p, void *hip_event) {
     if (!p || !hip_event) return LC3GPU_EINVAL;
     DeviceGuard dg(p->device);
-    const Group &q = p->groups.back();
+    Group &q = p->groups.back();
+    // One event can stand on one stream.  After a round trip the decoder stream is behind the encoder's latest work as well; where it is
+    // not (an encode alone after a decode, halves on unrelated buffers), it is put there first -- the one case in which a mark costs
+    // the pipeline a wait.
+    if (q.last_enc >= 0 && q.last_dec >= 0 && !q.dec_covers_enc) {
+        const int rc = wait_unless_done(p, q.s_dec, q.enc_done[q.last_enc]);
+        if (rc) return rc;
+        q.dec_covers_enc = true;
+    }
     PL_HIP(p, hipEventRecord((hipEvent_t)hip_event, q.last_dec >= 0 ? q.s_dec : q.s_enc));
     return LC3GPU_OK;
 }

@@ -148,3 +148,15 @@ def test_translation_units_match_the_generated_views():
         out = os.path.join(d, "views.h")
         subprocess.check_call([sys.executable, os.path.join(root, "tools", "gen_views.py"), out])
         assert open(out, "rb").read() == open(hdr, "rb").read()
+
+
+def test_the_pair_flag_peeks_are_carried_through_every_binding(L):
+    """lc3gpu_{encoder,decoder}_pair_pending (what lets the pipeline refuse a submission before any group launches): header, library,
+    Python binding, C++ facade, Rust binding; a null handle is refused, no device needed"""
+    hpp = open(os.path.join(ROOT, "include", "lc3gpu.hpp")).read()
+    rs = open(os.path.join(ROOT, "bindings", "lc3gpu.rs")).read()
+    for name in ("lc3gpu_encoder_pair_pending", "lc3gpu_decoder_pair_pending"):
+        assert name in header_symbols() and name in api.ABI_SYMBOLS and name in hpp and "pub fn %s(" % name in rs
+        assert getattr(L, name)(None) == -1  # LC3GPU_EINVAL
+    assert hpp.count("bool pair_pending() const") == 2
+    assert callable(pkg.Lc3Encoder.pair_pending) and callable(pkg.Lc3Decoder.pair_pending)
