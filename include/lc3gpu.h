@@ -733,6 +733,89 @@ int lc3gpu_mixer_destroy(lc3gpu_mixer *mx);
 int lc3gpu_mix_mixed_views(lc3gpu_mixer *mx, const lc3gpu_view *in_views, const lc3gpu_mix_in *ins, int n_in, const int16_t *d_pcm_in,
                            size_t in_elems, const lc3gpu_view *out_views, const lc3gpu_mix_out *outs, int n_out, int16_t *d_pcm_out,
                            size_t out_elems, void *hip_stream);
+/* Rate conversion over two lists of VIEWS: the step a room with a 16 kHz headset and a 48 kHz laptop needs on both sides of its mix --
+ * decode (lc3gpu_decode_mixed_views), resample up, mix (lc3gpu_mix_mixed_views), resample down, encode (lc3gpu_encode_mixed_views) -- on
+ * the tick's own view arrays, the PCM read where one array says and written where a second says, in one launch.  The reference has no
+ * resampler between streams (its only one is the encoder's LTPF analysis); the definition below is all-integer, its result does not
+ * depend on the order of summation, and tables/lc3_resample_tables.h (tools/gen_resample_tables.py) is part of it.
+ *   create    frame_us is 7500 or 10000, fs_in_hz and fs_out_hz are each one of the six rates (LC3GPU_EINVAL otherwise).  fs_in_hz ==
+ *             fs_out_hz is allowed for all six and is an exact copy: no delay, no state.  fs_in_hz != fs_out_hz with either side at 44100
+ *             is LC3GPU_EUNSUPPORTED: an LC3 44.1 kHz frame is not 10 ms long, so such streams tick at another pace.  n_channels >= 1.
+ *             max_views >= 1 bounds n_views of one call and sizes the pinned upload ring and its device twin once (LC3GPU_EINVAL below
+ *             1).  The resampler is bound to the device that is current at creation, is not thread-safe and is independent of every codec
+ *             handle, of the inspector, of the analyzer and of the mixer.  No device: LC3GPU_ENODEVICE
+ *   views     in_views and out_views are HOST arrays and may be reused as soon as the call returns; in_views[i] and out_views[i] belong
+ *             together.  Read from both: channel (index into the resampler's descriptors), n_frames, pcm_off, pcm_stride, pcm_pitch and
+ *             reserved (0).  channel and n_frames must be equal in both (LC3GPU_EINVAL otherwise).  NOT read: nbytes, byte_off,
+ *             byte_pitch, flag_off, flag_pitch: in_views can be the very array the tick gave lc3gpu_decode_mixed_views.  The resampler
+ *             carries state, so a channel may be named once per call: twice is LC3GPU_ECHANNEL
+ *   placement sample s of a view is d[pcm_off + (s / nf) * pitch + (s % nf) * pcm_stride] with pitch = pcm_pitch ? pcm_pitch : nf *
+ *             pcm_stride: exactly the views calls' rule, with nf = nf_in, the frame length of (fs_in_hz, frame_us), for the input view and
+ *             nf = nf_out, that of (fs_out_hz, frame_us), for the output view
+ *   written   with g = gcd(fs_in_hz, fs_out_hz), L = fs_out_hz / g, M = fs_in_hz / g (twelve ratios, L and M in 1..6), S_in = n_frames *
+ *             nf_in, S_out = n_frames * nf_out (S_out * M == S_in * L), T the ratio's taps per phase and c[p][j] its table; x[k], 0 <= k <
+ *             S_in, the view's input in time order and x[k], -(T - 1) <= k < 0, the channel's history (zeros when fresh):
+ *               for m in 0 .. S_out - 1:  u = m * M;  p = u % L;  b = u / L
+ *                   acc(m) = sum over j in 0 .. T - 1 of c[p][j] * x[b - j]            (int32)
+ *                   out(m) = clamp((acc(m) + 16384) >> 15, -32768, 32767)              (arithmetic shift)
+ *               new history = the last T - 1 samples of (old history ++ x)
+ *             Only the S_out samples of an output view are written: everything between and around them is left as it was.  A call always
+ *             starts at phase 0, so frames may be split over calls and over views' n_frames in any way without changing one output
+ *             sample.  The group delay is 8 samples of the lower of the two rates.  Every phase of every table sums to exactly 32768 (a
+ *             constant stays that constant) and has sum |c| <= 65535 (60988 at most), so |acc| < 2^31 - 16384 and nothing wraps
+ *   table     per ratio Q = max(L, M), N = 16 Q + 1, the prototype in float64 h[n] = L * 2 fc * sinc(2 fc (n - 8 Q)) * kaiser(N, beta =
+ *             6.0)[n] with fc = 0.92 * 0.5 / Q; T = ceil(N / L); phase p, tap j is h[p + L j] (0 beyond N); each phase is scaled to sum
+ *             1, times 32768, rounded to nearest, and the rounding residual is added to the phase's tap of largest magnitude.  The
+ *             COMMITTED table is the definition
+ *   state     a listed channel advances; a channel not listed keeps its history byte for byte.  lc3gpu_resampler_reset (all channels) and
+ *             lc3gpu_resampler_reset_channels (LC3GPU_ECHANNEL for an index out of range, and then none is reset) wait for nothing and
+ *             launch nothing: the named channels read a zero history inside their next launch.  A refused call has launched nothing,
+ *             written nothing, advanced no channel and consumed no pending reset
+ *   checks    on the host before anything is queued, for both views of every pair:
+ *               channel outside [0, n_channels)                      LC3GPU_ECHANNEL
+ *               a channel named twice in one call                    LC3GPU_ECHANNEL
+ *               n_frames < 1                                         LC3GPU_ELENGTH
+ *               more than 2^31 - 1 samples in one view               LC3GPU_ELENGTH
+ *               any sample of any view outside [0, in_elems) /
+ *               [0, out_elems)                                       LC3GPU_ELENGTH
+ *               n_views > max_views                                  LC3GPU_ELENGTH
+ *               more than 2^31 - 1 workgroups in the plan            LC3GPU_ELENGTH
+ *               channel or n_frames differing within a pair          LC3GPU_EINVAL
+ *               pcm_stride outside 1..8                              LC3GPU_EINVAL
+ *               a negative pcm_off                                   LC3GPU_EINVAL
+ *               a non-zero pitch below nf * pcm_stride               LC3GPU_EINVAL
+ *               reserved != 0                                        LC3GPU_EINVAL
+ *               pcm_stride == 1 with an odd pcm_off, an odd pitch
+ *               or a base not 4-byte aligned                         LC3GPU_EINVAL
+ *               pcm_stride >= 2 with a base not 2-byte aligned       LC3GPU_EINVAL
+ *               [d_pcm_in, + 2 * in_elems) and [d_pcm_out,
+ *               + 2 * out_elems) overlapping                         LC3GPU_EINVAL
+ *               a null rs; a null array with n_views > 0; n_views < 0 LC3GPU_EINVAL
+ *               n_views == 0                                         LC3GPU_OK (nothing launched)
+ *             the extent check works in unsigned 64-bit arithmetic that cannot wrap.  HIP errors: LC3GPU_EHIP
+ *   order     asynchronous on hip_stream.  Calls of one resampler share its histories: a call on another stream than the previous one's
+ *             is ordered behind it by an event wait on the device, as the analyzer orders its calls.  The host waits for the oldest of
+ *             its own uploads only when more calls are in flight than the ring has slots
+ *   launches  ONE launch and ONE upload of O(views) bytes per call, whatever mix of ratios, durations and frame counts
+ * NOT provided (out of scope): 44.1 kHz conversion, arbitrary ratios, state blobs, a channel twice in a call, float or wider PCM,
+ * host-resident buffers, the pipeline object, uniform handles. */
+typedef struct lc3gpu_rate_desc {
+    int fs_in_hz;
+    int fs_out_hz;
+    int frame_us;
+} lc3gpu_rate_desc; /* 12 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(lc3gpu_rate_desc) == 12, "lc3gpu_rate_desc is 12 bytes");
+#else
+_Static_assert(sizeof(lc3gpu_rate_desc) == 12, "lc3gpu_rate_desc is 12 bytes");
+#endif
+typedef struct lc3gpu_resampler lc3gpu_resampler;
+int lc3gpu_resampler_create(lc3gpu_resampler **out, int n_channels, const lc3gpu_rate_desc *descs, int max_views);
+int lc3gpu_resampler_destroy(lc3gpu_resampler *rs);
+int lc3gpu_resampler_reset(lc3gpu_resampler *rs); /* all channels */
+int lc3gpu_resampler_reset_channels(lc3gpu_resampler *rs, const int32_t *channels, int n);
+int lc3gpu_resample_mixed_views(lc3gpu_resampler *rs, const lc3gpu_view *in_views, const int16_t *d_pcm_in, size_t in_elems,
+                                const lc3gpu_view *out_views, int16_t *d_pcm_out, size_t out_elems, int n_views, void *hip_stream);
 
 size_t lc3gpu_decoder_state_size(const lc3gpu_decoder *dec);
 int lc3gpu_decoder_state_save(lc3gpu_decoder *dec, void *host_dst, size_t nbytes);

@@ -349,6 +349,42 @@ private:
     lc3gpu_mixer *h_ = nullptr;
 };
 
+// The resampler (lc3gpu_resample_mixed_views): the rate conversions of a tick -- up before the mix, down after it --, the PCM read where
+// one view array says and written where a second says, in one launch, with a FIR history per channel; channels = one (fs_in_hz, fs_out_hz,
+// frame_us) each, max_views the most pairs of views one call may name.  Independent of every codec handle and of the three other companions
+class Lc3Resampler {
+public:
+    Lc3Resampler(const std::vector<lc3gpu_rate_desc> &channels, size_t max_views) {
+        int rc = lc3gpu_resampler_create(&h_, (int)channels.size(), channels.data(), (int)max_views);
+        if (rc) throw Error(rc, "Lc3Resampler::new");
+    }
+    ~Lc3Resampler() { lc3gpu_resampler_destroy(h_); }
+    Lc3Resampler(const Lc3Resampler &) = delete;
+    Lc3Resampler &operator=(const Lc3Resampler &) = delete;
+    // in_views[i] and out_views[i] belong together (same channel, same n_frames; a channel once per call).  d_pcm_in and d_pcm_out may not
+    // overlap.  Every listed channel's history advances
+    void resample_mixed_views(const std::vector<lc3gpu_view> &in_views, const int16_t *d_pcm_in, size_t in_elems, const std::vector<lc3gpu_view> &out_views,
+                              int16_t *d_pcm_out, size_t out_elems, void *hip_stream = nullptr) {
+        if (in_views.size() != out_views.size()) throw Error(LC3GPU_EINVAL, "resample_mixed_views");
+        int rc = lc3gpu_resample_mixed_views(h_, in_views.data(), d_pcm_in, in_elems, out_views.data(), d_pcm_out, out_elems, (int)in_views.size(),
+                                             hip_stream);
+        if (rc) throw Error(rc, "resample_mixed_views");
+    }
+    // the channels read a zero history in their next call; nothing waits, nothing is launched
+    void reset() {
+        int rc = lc3gpu_resampler_reset(h_);
+        if (rc) throw Error(rc, "resampler_reset");
+    }
+    void reset_channels(const std::vector<int32_t> &channels) {
+        int rc = lc3gpu_resampler_reset_channels(h_, channels.data(), (int)channels.size());
+        if (rc) throw Error(rc, "resampler_reset_channels");
+    }
+    lc3gpu_resampler *handle() { return h_; }
+
+private:
+    lc3gpu_resampler *h_ = nullptr;
+};
+
 // ---- the reference's no_std / no-alloc API shape (lc3_encoder.rs:37-40,212-303, lc3_decoder.rs:56-60,247-310): the
 // number of channels is a compile-time constant instead of a constructor argument (`Lc3Encoder::<NUM_CH>::new(duration,
 // frequency, ..)`, `Lc3Encoder::<NUM_CH>::calc_working_buffer_lengths(duration, frequency)`; default 2 as in the

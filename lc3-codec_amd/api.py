@@ -23,7 +23,8 @@ _LIB = os.path.join(_HERE, "lib", os.environ.get("LC3GPU_LIB") or ("liblc3gpu_pr
 _SRC = os.path.join(_HERE, "csrc", "lc3gpu.hip")
 # host-only sources of the library on top of its own C ABI (the pipeline object): plain C++ beside the HIP translation units
 _HOST_SRCS = [os.path.join(_HERE, "csrc", "lc3gpu_pipeline.cpp"), os.path.join(_HERE, "csrc", "lc3gpu_inspector_api.cpp"),
-              os.path.join(_HERE, "csrc", "lc3gpu_analyzer_api.cpp"), os.path.join(_HERE, "csrc", "lc3gpu_mixer_api.cpp")]
+              os.path.join(_HERE, "csrc", "lc3gpu_analyzer_api.cpp"), os.path.join(_HERE, "csrc", "lc3gpu_mixer_api.cpp"),
+              os.path.join(_HERE, "csrc", "lc3gpu_resampler_api.cpp")]
 # The companion library of the inspector (lc3gpu_inspect_mixed_views): device code of its own, beside whichever main library is built.  The
 # main library links it (run path $ORIGIN) and holds host-side entry points only, so its own kernels are what they were.
 _INSPECTOR_LIB = os.path.join(os.path.dirname(_LIB), "liblc3gpu_inspector.so")
@@ -38,6 +39,11 @@ _ANALYZER_ONLY = ("lc3gpu_analyzer.hip", "lc3_host_analyze_views.h", "lc3_dev_de
 _MIXER_LIB = os.path.join(os.path.dirname(_LIB), "liblc3gpu_mixer.so")
 _MIXER_SRC = os.path.join(_HERE, "csrc", "lc3gpu_mixer.hip")
 _MIXER_ONLY = ("lc3gpu_mixer.hip", "lc3_host_mix_views.h", "lc3_dev_mix.h")  # sources only the mixer's unit sees
+# The companion library of the resampler (lc3gpu_resample_mixed_views), the fourth: one ordinary unit with its one kernel and its own
+# coefficient table (tables/lc3_resample_tables.h), built and linked the same way.
+_RESAMPLER_LIB = os.path.join(os.path.dirname(_LIB), "liblc3gpu_resampler.so")
+_RESAMPLER_SRC = os.path.join(_HERE, "csrc", "lc3gpu_resampler.hip")
+_RESAMPLER_ONLY = ("lc3gpu_resampler.hip", "lc3_host_resample_views.h", "lc3_dev_resample.h", "lc3_resample_tables.h")  # only the resampler's unit sees
 
 class Lc3GpuError(RuntimeError):
     def __init__(self, code, what=""):
@@ -91,6 +97,11 @@ def mixer_library_path():
     return _MIXER_LIB
 
 
+def resampler_library_path():
+    """the companion library of the resampler (lc3gpu_resample_mixed_views), which the main library links"""
+    return _RESAMPLER_LIB
+
+
 def _translation_units():
     """(kind, index) of every translation unit of the multi-unit build (csrc/lc3gpu.hip, "translation units"): the main unit (0: host
     side + the whole-source module's device code), the encoder kernels (1) and the decoder kernels (3) of every configuration view beyond
@@ -136,12 +147,14 @@ def build_native(force=False, verbose=False):
     Every flavour links the inspector's companion library (csrc/lc3gpu_inspector.hip -> lib/liblc3gpu_inspector.so, one ordinary unit),
     which is built and stamped here first; its own sources are no part of what the main library's translation units are stamped with.
     The analyzer's companion (csrc/lc3gpu_analyzer.hip -> lib/liblc3gpu_analyzer.so) and the mixer's (csrc/lc3gpu_mixer.hip ->
-    lib/liblc3gpu_mixer.so) are built, stamped and linked the same way."""
+    lib/liblc3gpu_mixer.so) are built, stamped and linked the same way, and so is the resampler's (csrc/lc3gpu_resampler.hip with
+    tables/lc3_resample_tables.h -> lib/liblc3gpu_resampler.so)."""
     srcs = [os.path.join(_HERE, "csrc", f) for f in os.listdir(os.path.join(_HERE, "csrc")) if f.endswith((".h", ".hip", ".cpp"))]
-    srcs += [os.path.join(_ROOT, "include", "lc3gpu.h"), os.path.join(_ROOT, "tables", "lc3_tables.h")]
+    srcs += [os.path.join(_ROOT, "include", "lc3gpu.h"), os.path.join(_ROOT, "tables", "lc3_tables.h"),
+             os.path.join(_ROOT, "tables", "lc3_resample_tables.h")]
     src_hash = _sources_hash(srcs)  # taken BEFORE anything is compiled: what the objects below are guaranteed to be at least as old as
     # (the HIP translation units do not see the host-only sources: an edit there relinks the library without recompiling them)
-    dev_hash = _sources_hash([p_ for p_ in srcs if not p_.endswith(".cpp") and os.path.basename(p_) not in _INSPECTOR_ONLY + _ANALYZER_ONLY + _MIXER_ONLY])
+    dev_hash = _sources_hash([p_ for p_ in srcs if not p_.endswith(".cpp") and os.path.basename(p_) not in _INSPECTOR_ONLY + _ANALYZER_ONLY + _MIXER_ONLY + _RESAMPLER_ONLY])
     extra = os.environ.get("LC3_HIPCC_EXTRA", "").split()  # compiler experiments
     extra_main = os.environ.get("LC3_HIPCC_EXTRA_MAIN", "").split()
     if (extra or extra_main) and not os.environ.get("LC3GPU_LIB"):
@@ -162,11 +175,13 @@ def build_native(force=False, verbose=False):
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function",
              "-Wno-missing-braces"]
     # the companions first (every flavour of the main library links the same ones): one ordinary unit each, stamped with the contents of
-    # the sources that unit can see (the inspector's and the analyzer's stamps are what they were before the mixer existed)
+    # the sources that unit can see (the three earlier companions' stamps are what they were before the resampler existed: its sources
+    # are hidden from them)
     force_link = False
-    for comp_lib, comp_src, hidden in ((_INSPECTOR_LIB, _INSPECTOR_SRC, _ANALYZER_ONLY + _MIXER_ONLY),
-                                       (_ANALYZER_LIB, _ANALYZER_SRC, ("lc3gpu_inspector.hip",) + _MIXER_ONLY),
-                                       (_MIXER_LIB, _MIXER_SRC, ("lc3gpu_inspector.hip",) + _ANALYZER_ONLY)):
+    for comp_lib, comp_src, hidden in ((_INSPECTOR_LIB, _INSPECTOR_SRC, _ANALYZER_ONLY + _MIXER_ONLY + _RESAMPLER_ONLY),
+                                       (_ANALYZER_LIB, _ANALYZER_SRC, ("lc3gpu_inspector.hip",) + _MIXER_ONLY + _RESAMPLER_ONLY),
+                                       (_MIXER_LIB, _MIXER_SRC, ("lc3gpu_inspector.hip",) + _ANALYZER_ONLY + _RESAMPLER_ONLY),
+                                       (_RESAMPLER_LIB, _RESAMPLER_SRC, ("lc3gpu_inspector.hip",) + _ANALYZER_ONLY + _MIXER_ONLY)):
         comp_sig = "sources=%s\n" % _sources_hash([p_ for p_ in srcs if not p_.endswith(".cpp") and os.path.basename(p_) not in hidden])
         if force or not os.path.exists(comp_lib) or not stamped(comp_lib + ".stamp", comp_sig):
             tmp = comp_lib + ".tmp%d" % os.getpid()
@@ -184,7 +199,8 @@ def build_native(force=False, verbose=False):
             force_link = True
     if not force and not force_link and os.path.exists(_LIB) and stamped(stamp, sig):
         return _LIB
-    link_insp = ["-L" + os.path.dirname(_INSPECTOR_LIB), "-llc3gpu_inspector", "-llc3gpu_analyzer", "-llc3gpu_mixer", "-Wl,-rpath,$ORIGIN"]
+    link_insp = ["-L" + os.path.dirname(_INSPECTOR_LIB), "-llc3gpu_inspector", "-llc3gpu_analyzer", "-llc3gpu_mixer", "-llc3gpu_resampler",
+                 "-Wl,-rpath,$ORIGIN"]
     if single:
         cmd = ["hipcc"] + extra + (["-DLC3_PROFILE"] if _PROFILE else []) + flags + ["-shared", "-o", _LIB, _SRC] + _HOST_SRCS + link_insp
         if verbose:
@@ -333,6 +349,11 @@ def load_library():
     L.lc3gpu_mixer_create.argtypes = [ctypes.POINTER(vp), i, vp, i]
     L.lc3gpu_mixer_destroy.argtypes = [vp]
     L.lc3gpu_mix_mixed_views.argtypes = [vp, vp, vp, i, vp, ctypes.c_size_t, vp, vp, i, vp, ctypes.c_size_t, vp]
+    L.lc3gpu_resampler_create.argtypes = [ctypes.POINTER(vp), i, vp, i]
+    L.lc3gpu_resampler_destroy.argtypes = [vp]
+    L.lc3gpu_resampler_reset.argtypes = [vp]
+    L.lc3gpu_resampler_reset_channels.argtypes = [vp, vp, i]
+    L.lc3gpu_resample_mixed_views.argtypes = [vp, vp, vp, ctypes.c_size_t, vp, vp, ctypes.c_size_t, i, vp]
     L.lc3gpu_encoder_state_size.restype = ctypes.c_size_t
     L.lc3gpu_encoder_state_size.argtypes = [vp]
     L.lc3gpu_encoder_state_save.argtypes = [vp, vp, ctypes.c_size_t]
@@ -423,6 +444,8 @@ ABI_SYMBOLS = [
     "lc3gpu_inspector_create", "lc3gpu_inspector_destroy", "lc3gpu_inspect_mixed_views",
     "lc3gpu_analyzer_create", "lc3gpu_analyzer_destroy", "lc3gpu_analyze_mixed_views",
     "lc3gpu_mixer_create", "lc3gpu_mixer_destroy", "lc3gpu_mix_mixed_views",
+    "lc3gpu_resampler_create", "lc3gpu_resampler_destroy", "lc3gpu_resampler_reset", "lc3gpu_resampler_reset_channels",
+    "lc3gpu_resample_mixed_views",
 ]
 
 # LC3GPU_SPEC_*: opt-in corrections of the reference's deviations from the LC3 specification (default 0 = reference behaviour)
@@ -1387,6 +1410,82 @@ def mixer_plan_info():
     if rc:
         raise Lc3GpuError(rc, "mixer_plan_info")
     return spw.value, lanes.value, slots.value
+
+
+# rate conversion (lc3gpu_resample_mixed_views): lc3gpu_rate_desc, 12 bytes
+RATE_DESC_DTYPE = np.dtype([("fs_in_hz", "<i4"), ("fs_out_hz", "<i4"), ("frame_us", "<i4")])
+
+
+class Lc3Resampler:
+    """lc3gpu_resampler: the rate conversions of a tick, the PCM read where one view array says and written where a second says, in one
+    launch, with a FIR history per channel.  descs = [(fs_in_hz, fs_out_hz, frame_us), ...]; max_views = the most pairs of views one
+    call may name.  Independent of every codec handle and of the three other companions; bound to the device current at creation."""
+
+    def __init__(self, descs, max_views):
+        self._L = load_library()
+        self.descs = [(int(d[0]), int(d[1]), int(d[2])) for d in descs]
+        self.num_channels = len(self.descs)
+        self.max_views = int(max_views)
+        arr = np.zeros(max(1, self.num_channels), RATE_DESC_DTYPE)
+        for k, d in enumerate(self.descs):
+            arr[k] = d
+        h = ctypes.c_void_p()
+        rc = self._L.lc3gpu_resampler_create(ctypes.byref(h), self.num_channels, _ptr(arr), self.max_views)
+        if rc:
+            raise Lc3GpuError(rc, "Lc3Resampler::new")
+        self._h = h
+
+    def resample_mixed_views(self, in_views, d_pcm_in, out_views, d_pcm_out, stream=None, in_elems=None, out_elems=None):
+        """one launch over all listed channels.  in_views[i] and out_views[i] belong together (same channel, same n_frames; a channel
+        once per call); every output sample is the clamped, rounded int32 FIR sum of include/lc3gpu.h over the view's input and the
+        channel's history, which advances.  d_pcm_in / d_pcm_out: int16 device buffers that do not overlap; the extents (elements)
+        default to the buffers' sizes (lc3gpu_resample_mixed_views)"""
+        vi, vo = _view_list(in_views), _view_list(out_views)
+        if vi.shape[0] != vo.shape[0]:
+            raise ValueError("one output view per input view")
+        ie = (0 if d_pcm_in is None else _numel(d_pcm_in, "in_elems")) if in_elems is None else int(in_elems)
+        oe = (0 if d_pcm_out is None else _numel(d_pcm_out, "out_elems")) if out_elems is None else int(out_elems)
+        n = int(vi.shape[0])
+        rc = self._L.lc3gpu_resample_mixed_views(self._h, _ptr(vi) if n else None, _ptr(d_pcm_in), ie, _ptr(vo) if n else None, _ptr(d_pcm_out),
+                                                 oe, n, _ptr(stream))
+        if rc:
+            raise Lc3GpuError(rc, "resample_mixed_views")
+
+    def reset(self):
+        """every channel reads a zero history in its next call; waits for nothing, launches nothing (lc3gpu_resampler_reset)"""
+        rc = self._L.lc3gpu_resampler_reset(self._h)
+        if rc:
+            raise Lc3GpuError(rc, "resampler_reset")
+
+    def reset_channels(self, channels):
+        """the named channels read a zero history in their next call (lc3gpu_resampler_reset_channels)"""
+        ch = np.ascontiguousarray(np.asarray(channels, np.int32).reshape(-1))
+        rc = self._L.lc3gpu_resampler_reset_channels(self._h, _ptr(ch) if ch.size else None, int(ch.size))
+        if rc:
+            raise Lc3GpuError(rc, "resampler_reset_channels")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.lc3gpu_resampler_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def resampler_plan_info():
+    """-> (output samples of a view per workgroup, lanes per workgroup, upload ring slots, samples of a history buffer) of a resampler
+    call: the plan's own figures, from the companion library (tests and tools)"""
+    load_library()  # (the main library first: it brings the companion in, and the one HIP runtime of the process)
+    C = ctypes.CDLL(_RESAMPLER_LIB)
+    spw, lanes, slots, hist = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    rc = C.lc3rs_plan_info(ctypes.byref(spw), ctypes.byref(lanes), ctypes.byref(slots), ctypes.byref(hist))
+    if rc:
+        raise Lc3GpuError(rc, "resampler_plan_info")
+    return spw.value, lanes.value, slots.value, hist.value
 
 
 class PinnedBuffer:

@@ -19,7 +19,8 @@ HEADER = os.path.join(ROOT, "include", "lc3gpu.h")
 OPAQUE = {"lc3gpu_encoder": "Lc3GpuEncoder", "lc3gpu_decoder": "Lc3GpuDecoder", "lc3gpu_pipeline": "Lc3GpuPipeline",
           "lc3gpu_stream_desc": "Lc3GpuStreamDesc", "lc3gpu_frame_info": "Lc3GpuFrameInfo", "lc3gpu_item": "Lc3GpuItem", "lc3gpu_mc_item": "Lc3GpuMcItem",
           "lc3gpu_view": "Lc3GpuView", "lc3gpu_inspector": "Lc3GpuInspector", "lc3gpu_analyzer": "Lc3GpuAnalyzer",
-          "lc3gpu_mixer": "Lc3GpuMixer", "lc3gpu_mix_in": "Lc3GpuMixIn", "lc3gpu_mix_out": "Lc3GpuMixOut"}
+          "lc3gpu_mixer": "Lc3GpuMixer", "lc3gpu_mix_in": "Lc3GpuMixIn", "lc3gpu_mix_out": "Lc3GpuMixOut",
+          "lc3gpu_resampler": "Lc3GpuResampler", "lc3gpu_rate_desc": "Lc3GpuRateDesc"}
 SCALAR = {"int": "i32", "unsigned": "u32", "unsigned int": "u32", "float": "f32", "double": "f64", "size_t": "usize",
           "int16_t": "i16", "uint16_t": "u16", "uint8_t": "u8", "int32_t": "i32", "uint32_t": "u32", "int64_t": "i64", "uint64_t": "u64",
           "unsigned long long": "u64", "char": "c_char", "void": "c_void"}
@@ -480,6 +481,48 @@ impl Drop for Lc3MixerGpu {
     }
 }
 
+/// The resampler (include/lc3gpu.h): the rate conversions of a tick, the PCM read where one view array says and written where a second
+/// says, in one launch, a FIR history per channel.  Independent of every codec handle and of the three other companions.
+pub struct Lc3ResamplerGpu {
+    h: *mut Lc3GpuResampler,
+}
+impl Lc3ResamplerGpu {
+    /// `descs`: one (fs_in_hz, fs_out_hz, frame_us) per channel; `max_views`: the most pairs of views one call may name
+    pub fn new(descs: &[Lc3GpuRateDesc], max_views: usize) -> Result<Self, i32> {
+        let mut h = core::ptr::null_mut();
+        let rc = unsafe { lc3gpu_resampler_create(&mut h, descs.len() as i32, descs.as_ptr(), max_views as i32) };
+        if rc == LC3GPU_OK { Ok(Self { h }) } else { Err(rc) }
+    }
+    /// Every channel reads a zero history in its next call; waits for nothing, launches nothing.
+    pub fn reset(&mut self) -> i32 {
+        unsafe { lc3gpu_resampler_reset(self.h) }
+    }
+    /// The named channels read a zero history in their next call.
+    pub fn reset_channels(&mut self, channels: &[i32]) -> i32 {
+        unsafe { lc3gpu_resampler_reset_channels(self.h, channels.as_ptr(), channels.len() as i32) }
+    }
+    /// One launch over all listed channels: `in_views[i]` and `out_views[i]` belong together (same channel, same n_frames, a channel once
+    /// per call); every output sample is the clamped, rounded int32 FIR sum over the view's input and the channel's history.
+    ///
+    /// # Safety
+    /// device allocations of at least `in_elems` and `out_elems` elements that do not overlap and outlive the call's work; every view is
+    /// checked against these extents on the host.  The two slices are host memory and free again when the call returns.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn resample_mixed_views_device(&mut self, in_views: &[Lc3GpuView], d_pcm_in: *const i16, in_elems: usize, out_views: &[Lc3GpuView],
+                                              d_pcm_out: *mut i16, out_elems: usize, hip_stream: *mut c_void) -> i32 {
+        assert_eq!(in_views.len(), out_views.len());
+        lc3gpu_resample_mixed_views(self.h, in_views.as_ptr(), d_pcm_in, in_elems, out_views.as_ptr(), d_pcm_out, out_elems,
+                                    in_views.len() as i32, hip_stream)
+    }
+}
+impl Drop for Lc3ResamplerGpu {
+    fn drop(&mut self) {
+        unsafe {
+            lc3gpu_resampler_destroy(self.h);
+        }
+    }
+}
+
 /// Encode + decode of many channels in the arrangement that measured fastest (include/lc3gpu.h, "pipeline"): device buffers, asynchronous.
 pub struct Lc3PipelineGpu {
     h: *mut Lc3GpuPipeline,
@@ -523,7 +566,8 @@ def generate():
         "",
     ]
     for c, r in sorted(OPAQUE.items()):
-        if c in ("lc3gpu_stream_desc", "lc3gpu_frame_info", "lc3gpu_item", "lc3gpu_mc_item", "lc3gpu_view", "lc3gpu_mix_in", "lc3gpu_mix_out"):
+        if c in ("lc3gpu_stream_desc", "lc3gpu_frame_info", "lc3gpu_item", "lc3gpu_mc_item", "lc3gpu_view", "lc3gpu_mix_in", "lc3gpu_mix_out",
+                 "lc3gpu_rate_desc"):
             continue
         lines += ["#[repr(C)]", "pub struct %s {" % r, "    _private: [u8; 0],", "}"]
     lines += ["/// one stream of a mixed-configuration handle (lc3gpu_stream_desc)", "#[repr(C)]", "#[derive(Clone, Copy, Debug)]",
@@ -548,6 +592,9 @@ def generate():
     lines += ["/// one output of lc3gpu_mix_mixed_views (lc3gpu_mix_out, 8 bytes): the room it hears and the input it does not hear (-1 = none)",
               "#[repr(C)]", "#[derive(Clone, Copy, Debug, Default)]", "pub struct Lc3GpuMixOut {", "    pub bus: i32,", "    pub minus: i32,", "}",
               "const _: () = assert!(core::mem::size_of::<Lc3GpuMixOut>() == 8);"]
+    lines += ["/// one channel of lc3gpu_resampler_create (lc3gpu_rate_desc, 12 bytes): the rate it comes at, the rate it leaves at, the duration",
+              "#[repr(C)]", "#[derive(Clone, Copy, Debug, Default)]", "pub struct Lc3GpuRateDesc {", "    pub fs_in_hz: i32,", "    pub fs_out_hz: i32,",
+              "    pub frame_us: i32,", "}", "const _: () = assert!(core::mem::size_of::<Lc3GpuRateDesc>() == 12);"]
     lines += ["/// one frame's record of lc3gpu_inspect (lc3gpu_frame_info, 128 bytes): status LC3GPU_FRAME_*, the side information",
               "/// (decoder/side_info.rs:20-31) and the arithmetic data (decoder/arithmetic_codec.rs:99-107)", "#[repr(C)]",
               "#[derive(Clone, Copy, Debug, Default)]", "pub struct Lc3GpuFrameInfo {"]
