@@ -816,6 +816,114 @@ int lc3gpu_resampler_reset(lc3gpu_resampler *rs); /* all channels */
 int lc3gpu_resampler_reset_channels(lc3gpu_resampler *rs, const int32_t *channels, int n);
 int lc3gpu_resample_mixed_views(lc3gpu_resampler *rs, const lc3gpu_view *in_views, const int16_t *d_pcm_in, size_t in_elems,
                                 const lc3gpu_view *out_views, int16_t *d_pcm_out, size_t out_elems, int n_views, void *hip_stream);
+/* PCM levels over a list of VIEWS: what decides WHAT a tick mixes -- who is speaking, whether a capture clips, whether a room's mix hits
+ * the clamp of lc3gpu_mix_mixed_views -- measured on the tick's own view arrays, the PCM read where one array says it lies, with a smoothed
+ * level and a hang-over carried from tick to tick so that a speaker is not dropped between words.  lc3gpu_analyze_mixed_views measures
+ * coded frames before the decode; this call sees PCM that was never coded (capture buffers), PCM that is no longer what was coded (mixes,
+ * resampled streams) and what carries over from one tick to the next.  The reference has no meter; the definition below is all-integer, so
+ * the result does not depend on the order of summation.
+ *   create    fs_hz is one of the six rates (8 kHz and 44.1 kHz included), frame_us is 7500 or 10000, attack_q15 and release_q15 lie in
+ *             0..32768, threshold in 0..2^30, hang_frames in 0..65535 (LC3GPU_EINVAL otherwise).  n_channels >= 1.  max_views >= 1 bounds
+ *             n_views of one call and sizes the pinned upload ring and its device twin once (LC3GPU_EINVAL below 1).  The descriptors are
+ *             checked before a device is looked for.  The meter is bound to the device that is current at creation, is not thread-safe
+ *             and is independent of every other object.  No device: LC3GPU_ENODEVICE
+ *   views     views is a HOST array and may be reused as soon as the call returns.  Read: channel (index into the meter's descriptors),
+ *             n_frames, pcm_off, pcm_stride, pcm_pitch, flag_off, flag_pitch and reserved (0).  NOT read: nbytes, byte_off, byte_pitch.
+ *             So the array can be the very array the tick gave lc3gpu_decode_mixed_views, or the one it will give
+ *             lc3gpu_encode_mixed_views, whose flag_off that call ignores and this one uses.  The meter carries state, so a channel may be
+ *             named once per call: twice is LC3GPU_ECHANNEL
+ *   placement sample n of frame t of a view is d_pcm[pcm_off + t * pitch + n * pcm_stride] with pitch = pcm_pitch ? pcm_pitch : nf *
+ *             pcm_stride: exactly the views calls' rule, nf the frame length of (fs_hz, frame_us).  Frame t's outputs are d_active[flag_off
+ *             + t * fp] and d_levels[flag_off + t * fp] with fp = flag_pitch ? flag_pitch : 1.  At least one output must be given.  Only a
+ *             frame's own byte and record are written: everything between and around them is left as it was
+ *   written   for frame t of a view, in order t = 0, 1, ...: x[0 .. nf) its samples, x[-1] the sample before it in the channel's stream (the
+ *             last sample of frame t - 1 of the view, or for t = 0 the state's last), env0 and hang0 the state before the frame:
+ *               sum_sq = sum of x[n]^2 (int64)      sum = sum of x[n]      min, max
+ *               n_clipped = the number of n with x[n] == 32767 or x[n] == -32768
+ *               n_cross   = the number of n in 0 .. nf - 1 with (x[n] < 0) != (x[n - 1] < 0)
+ *               ms  = sum_sq / nf                                 (floor; <= 2^30)
+ *               d   = ms - env0;  k = d > 0 ? attack_q15 : release_q15
+ *               env = env0 + ((d * k + 16384) >> 15)              (int64, arithmetic shift)
+ *               if env >= threshold:  hang = hang_frames, active = 1
+ *               else if hang0 > 0:    hang = hang0 - 1,   active = 1
+ *               else:                 hang = 0,           active = 0
+ *               state after the frame: last = x[nf - 1], env, hang
+ *             sum_sq <= 480 * 2^30 < 2^39, |sum| <= 15 728 640, |d * k| <= 2^45, and env always lies between env0 and ms inclusive, so it
+ *             stays in 0..2^30 (checked with Python integers over two million random and corner triples).  A coefficient of 32768 reaches
+ *             ms exactly, a coefficient of 0 never moves.  Because x[-1] and the recurrence run through the state, frames may be split
+ *             over calls and over views' n_frames in any way without changing one record
+ *   state     a fresh channel has last = 0, env = 0, hang = 0.  A listed channel advances; a channel not listed keeps its state.
+ *             lc3gpu_meter_reset (all channels) and lc3gpu_meter_reset_channels (LC3GPU_ECHANNEL for an index out of range, and then none
+ *             is reset) wait for nothing and launch nothing: the named channels read a fresh state inside their next launch.  A refused
+ *             call has launched nothing, written nothing, advanced no channel and consumed no pending reset
+ *   checks    on the host before anything is queued:
+ *               channel outside [0, n_channels)                      LC3GPU_ECHANNEL
+ *               a channel named twice in one call                    LC3GPU_ECHANNEL
+ *               n_frames < 1                                         LC3GPU_ELENGTH
+ *               more than 2^31 - 1 samples in one view               LC3GPU_ELENGTH
+ *               any sample of any view outside [0, pcm_elems)        LC3GPU_ELENGTH
+ *               any output index of any frame outside [0, n_active)
+ *               / [0, n_levels) of a GIVEN output                    LC3GPU_ELENGTH
+ *               n_views > max_views                                  LC3GPU_ELENGTH
+ *               pcm_stride outside 1..8                              LC3GPU_EINVAL
+ *               a negative pcm_off or flag_off                       LC3GPU_EINVAL
+ *               a non-zero pitch below nf * pcm_stride               LC3GPU_EINVAL
+ *               flag_pitch < 0                                       LC3GPU_EINVAL
+ *               reserved != 0                                        LC3GPU_EINVAL
+ *               pcm_stride == 1 with an odd pcm_off, an odd pitch
+ *               or a base not 4-byte aligned                         LC3GPU_EINVAL
+ *               pcm_stride >= 2 with a base not 2-byte aligned       LC3GPU_EINVAL
+ *               both outputs NULL                                    LC3GPU_EINVAL
+ *               d_levels not 16-byte aligned                         LC3GPU_EINVAL
+ *               an output's address range overlapping d_pcm's or
+ *               the other output's                                   LC3GPU_EINVAL
+ *               a null mt; null views or d_pcm with n_views > 0;
+ *               n_views < 0                                          LC3GPU_EINVAL
+ *               n_views == 0                                         LC3GPU_OK (nothing launched)
+ *             the extent check works in unsigned 64-bit arithmetic that cannot wrap.  HIP errors: LC3GPU_EHIP
+ *   order     asynchronous on hip_stream.  Calls of one meter share its states: a call on another stream than the previous one's is
+ *             ordered behind it by an event wait on the device, as the resampler orders its calls.  The host waits for the oldest of its
+ *             own uploads only when more calls are in flight than the ring has slots
+ *   launches  ONE launch and ONE upload of O(views) bytes per call, whatever mix of rates, durations, strides and frame counts.  One wave
+ *             walks one view: a view of thousands of frames is one serial wave, which is correct, not tuned
+ * NOT provided (out of scope): state blobs, a channel twice in a call, float or wider PCM, loudness weighting (K-weighting, LUFS),
+ * per-sample envelopes, host-resident buffers, the pipeline object, uniform handles. */
+typedef struct lc3gpu_meter_desc {
+    int fs_hz;            /* one of the six rates */
+    int frame_us;         /* 7500 or 10000 */
+    int32_t attack_q15;   /* 0..32768: share of the way the envelope rises towards a louder frame */
+    int32_t release_q15;  /* 0..32768: share of the way it falls towards a quieter one */
+    uint32_t threshold;   /* 0..2^30, in the envelope's unit (mean square of int16 samples) */
+    int32_t hang_frames;  /* 0..65535: frames the gate stays open after the envelope fell below threshold */
+} lc3gpu_meter_desc; /* 24 bytes */
+typedef struct lc3gpu_level {
+    int64_t sum_sq;       /* sum of x*x over the frame */
+    uint32_t env;         /* the envelope after this frame */
+    int32_t sum;          /* sum of x (DC) */
+    int16_t min, max;
+    uint16_t n_clipped;   /* samples equal to 32767 or -32768 */
+    uint16_t n_cross;     /* sign changes, the one into the frame's first sample included */
+    uint16_t hang;        /* the hang-over counter after this frame */
+    uint8_t active;       /* 1 or 0 */
+    uint8_t reserved0;    /* 0 */
+    uint32_t reserved1;   /* 0 */
+} lc3gpu_level; /* 32 bytes, one per frame */
+#ifdef __cplusplus
+static_assert(sizeof(lc3gpu_meter_desc) == 24, "lc3gpu_meter_desc is 24 bytes");
+static_assert(sizeof(lc3gpu_level) == 32, "lc3gpu_level is 32 bytes");
+#else
+_Static_assert(sizeof(lc3gpu_meter_desc) == 24, "lc3gpu_meter_desc is 24 bytes");
+_Static_assert(sizeof(lc3gpu_level) == 32, "lc3gpu_level is 32 bytes");
+#endif
+typedef struct lc3gpu_meter lc3gpu_meter;
+int lc3gpu_meter_create(lc3gpu_meter **out, int n_channels, const lc3gpu_meter_desc *descs, int max_views);
+int lc3gpu_meter_destroy(lc3gpu_meter *mt);
+int lc3gpu_meter_reset(lc3gpu_meter *mt); /* all channels */
+int lc3gpu_meter_reset_channels(lc3gpu_meter *mt, const int32_t *channels, int n);
+int lc3gpu_measure_mixed_views(lc3gpu_meter *mt, const lc3gpu_view *views, int n_views, const int16_t *d_pcm, size_t pcm_elems,
+                               uint8_t *d_active, size_t n_active,      /* one byte per output index, or NULL */
+                               lc3gpu_level *d_levels, size_t n_levels, /* one record per output index, or NULL */
+                               void *hip_stream);
 
 size_t lc3gpu_decoder_state_size(const lc3gpu_decoder *dec);
 int lc3gpu_decoder_state_save(lc3gpu_decoder *dec, void *host_dst, size_t nbytes);

@@ -385,6 +385,40 @@ private:
     lc3gpu_resampler *h_ = nullptr;
 };
 
+// The meter (lc3gpu_measure_mixed_views): the PCM levels and the speech gate of a tick, the PCM read where one view array says it lies, in
+// one launch, with a small state per channel (last sample, envelope, hang-over); channels = one lc3gpu_meter_desc each, max_views the most
+// views one call may name.  Independent of every other object
+class Lc3Meter {
+public:
+    Lc3Meter(const std::vector<lc3gpu_meter_desc> &channels, size_t max_views) {
+        int rc = lc3gpu_meter_create(&h_, (int)channels.size(), channels.data(), (int)max_views);
+        if (rc) throw Error(rc, "Lc3Meter::new");
+    }
+    ~Lc3Meter() { lc3gpu_meter_destroy(h_); }
+    Lc3Meter(const Lc3Meter &) = delete;
+    Lc3Meter &operator=(const Lc3Meter &) = delete;
+    // frame t of a view gets its activity byte and its record at index flag_off + t * flag_pitch; either output may be null, not both; a
+    // channel once per call.  Every listed channel's state advances
+    void measure_mixed_views(const std::vector<lc3gpu_view> &views, const int16_t *d_pcm, size_t pcm_elems, uint8_t *d_active, size_t n_active,
+                             lc3gpu_level *d_levels, size_t n_levels, void *hip_stream = nullptr) {
+        int rc = lc3gpu_measure_mixed_views(h_, views.data(), (int)views.size(), d_pcm, pcm_elems, d_active, n_active, d_levels, n_levels, hip_stream);
+        if (rc) throw Error(rc, "measure_mixed_views");
+    }
+    // the channels start from last = 0, env = 0, hang = 0 in their next call; nothing waits, nothing is launched
+    void reset() {
+        int rc = lc3gpu_meter_reset(h_);
+        if (rc) throw Error(rc, "meter_reset");
+    }
+    void reset_channels(const std::vector<int32_t> &channels) {
+        int rc = lc3gpu_meter_reset_channels(h_, channels.data(), (int)channels.size());
+        if (rc) throw Error(rc, "meter_reset_channels");
+    }
+    lc3gpu_meter *handle() { return h_; }
+
+private:
+    lc3gpu_meter *h_ = nullptr;
+};
+
 // ---- the reference's no_std / no-alloc API shape (lc3_encoder.rs:37-40,212-303, lc3_decoder.rs:56-60,247-310): the
 // number of channels is a compile-time constant instead of a constructor argument (`Lc3Encoder::<NUM_CH>::new(duration,
 // frequency, ..)`, `Lc3Encoder::<NUM_CH>::calc_working_buffer_lengths(duration, frequency)`; default 2 as in the

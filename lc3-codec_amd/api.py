@@ -24,7 +24,7 @@ _SRC = os.path.join(_HERE, "csrc", "lc3gpu.hip")
 # host-only sources of the library on top of its own C ABI (the pipeline object): plain C++ beside the HIP translation units
 _HOST_SRCS = [os.path.join(_HERE, "csrc", "lc3gpu_pipeline.cpp"), os.path.join(_HERE, "csrc", "lc3gpu_inspector_api.cpp"),
               os.path.join(_HERE, "csrc", "lc3gpu_analyzer_api.cpp"), os.path.join(_HERE, "csrc", "lc3gpu_mixer_api.cpp"),
-              os.path.join(_HERE, "csrc", "lc3gpu_resampler_api.cpp")]
+              os.path.join(_HERE, "csrc", "lc3gpu_resampler_api.cpp"), os.path.join(_HERE, "csrc", "lc3gpu_meter_api.cpp")]
 # The companion library of the inspector (lc3gpu_inspect_mixed_views): device code of its own, beside whichever main library is built.  The
 # main library links it (run path $ORIGIN) and holds host-side entry points only, so its own kernels are what they were.
 _INSPECTOR_LIB = os.path.join(os.path.dirname(_LIB), "liblc3gpu_inspector.so")
@@ -44,6 +44,11 @@ _MIXER_ONLY = ("lc3gpu_mixer.hip", "lc3_host_mix_views.h", "lc3_dev_mix.h")  # s
 _RESAMPLER_LIB = os.path.join(os.path.dirname(_LIB), "liblc3gpu_resampler.so")
 _RESAMPLER_SRC = os.path.join(_HERE, "csrc", "lc3gpu_resampler.hip")
 _RESAMPLER_ONLY = ("lc3gpu_resampler.hip", "lc3_host_resample_views.h", "lc3_dev_resample.h", "lc3_resample_tables.h")  # only the resampler's unit sees
+# The companion library of the meter (lc3gpu_measure_mixed_views), the fifth: one ordinary unit with its one kernel, built and linked the
+# same way.
+_METER_LIB = os.path.join(os.path.dirname(_LIB), "liblc3gpu_meter.so")
+_METER_SRC = os.path.join(_HERE, "csrc", "lc3gpu_meter.hip")
+_METER_ONLY = ("lc3gpu_meter.hip", "lc3_host_measure_views.h", "lc3_dev_level.h")  # sources only the meter's unit sees
 
 class Lc3GpuError(RuntimeError):
     def __init__(self, code, what=""):
@@ -102,6 +107,11 @@ def resampler_library_path():
     return _RESAMPLER_LIB
 
 
+def meter_library_path():
+    """the companion library of the meter (lc3gpu_measure_mixed_views), which the main library links"""
+    return _METER_LIB
+
+
 def _translation_units():
     """(kind, index) of every translation unit of the multi-unit build (csrc/lc3gpu.hip, "translation units"): the main unit (0: host
     side + the whole-source module's device code), the encoder kernels (1) and the decoder kernels (3) of every configuration view beyond
@@ -148,13 +158,13 @@ def build_native(force=False, verbose=False):
     which is built and stamped here first; its own sources are no part of what the main library's translation units are stamped with.
     The analyzer's companion (csrc/lc3gpu_analyzer.hip -> lib/liblc3gpu_analyzer.so) and the mixer's (csrc/lc3gpu_mixer.hip ->
     lib/liblc3gpu_mixer.so) are built, stamped and linked the same way, and so is the resampler's (csrc/lc3gpu_resampler.hip with
-    tables/lc3_resample_tables.h -> lib/liblc3gpu_resampler.so)."""
+    tables/lc3_resample_tables.h -> lib/liblc3gpu_resampler.so) and the meter's (csrc/lc3gpu_meter.hip -> lib/liblc3gpu_meter.so)."""
     srcs = [os.path.join(_HERE, "csrc", f) for f in os.listdir(os.path.join(_HERE, "csrc")) if f.endswith((".h", ".hip", ".cpp"))]
     srcs += [os.path.join(_ROOT, "include", "lc3gpu.h"), os.path.join(_ROOT, "tables", "lc3_tables.h"),
              os.path.join(_ROOT, "tables", "lc3_resample_tables.h")]
     src_hash = _sources_hash(srcs)  # taken BEFORE anything is compiled: what the objects below are guaranteed to be at least as old as
     # (the HIP translation units do not see the host-only sources: an edit there relinks the library without recompiling them)
-    dev_hash = _sources_hash([p_ for p_ in srcs if not p_.endswith(".cpp") and os.path.basename(p_) not in _INSPECTOR_ONLY + _ANALYZER_ONLY + _MIXER_ONLY + _RESAMPLER_ONLY])
+    dev_hash = _sources_hash([p_ for p_ in srcs if not p_.endswith(".cpp") and os.path.basename(p_) not in _INSPECTOR_ONLY + _ANALYZER_ONLY + _MIXER_ONLY + _RESAMPLER_ONLY + _METER_ONLY])
     extra = os.environ.get("LC3_HIPCC_EXTRA", "").split()  # compiler experiments
     extra_main = os.environ.get("LC3_HIPCC_EXTRA_MAIN", "").split()
     if (extra or extra_main) and not os.environ.get("LC3GPU_LIB"):
@@ -175,13 +185,14 @@ def build_native(force=False, verbose=False):
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function",
              "-Wno-missing-braces"]
     # the companions first (every flavour of the main library links the same ones): one ordinary unit each, stamped with the contents of
-    # the sources that unit can see (the three earlier companions' stamps are what they were before the resampler existed: its sources
-    # are hidden from them)
+    # the sources that unit can see (the earlier companions' stamps are what they were before the resampler and the meter existed: their
+    # sources are hidden from them)
     force_link = False
-    for comp_lib, comp_src, hidden in ((_INSPECTOR_LIB, _INSPECTOR_SRC, _ANALYZER_ONLY + _MIXER_ONLY + _RESAMPLER_ONLY),
-                                       (_ANALYZER_LIB, _ANALYZER_SRC, ("lc3gpu_inspector.hip",) + _MIXER_ONLY + _RESAMPLER_ONLY),
-                                       (_MIXER_LIB, _MIXER_SRC, ("lc3gpu_inspector.hip",) + _ANALYZER_ONLY + _RESAMPLER_ONLY),
-                                       (_RESAMPLER_LIB, _RESAMPLER_SRC, ("lc3gpu_inspector.hip",) + _ANALYZER_ONLY + _MIXER_ONLY)):
+    for comp_lib, comp_src, hidden in ((_INSPECTOR_LIB, _INSPECTOR_SRC, _ANALYZER_ONLY + _MIXER_ONLY + _RESAMPLER_ONLY + _METER_ONLY),
+                                       (_ANALYZER_LIB, _ANALYZER_SRC, ("lc3gpu_inspector.hip",) + _MIXER_ONLY + _RESAMPLER_ONLY + _METER_ONLY),
+                                       (_MIXER_LIB, _MIXER_SRC, ("lc3gpu_inspector.hip",) + _ANALYZER_ONLY + _RESAMPLER_ONLY + _METER_ONLY),
+                                       (_RESAMPLER_LIB, _RESAMPLER_SRC, ("lc3gpu_inspector.hip",) + _ANALYZER_ONLY + _MIXER_ONLY + _METER_ONLY),
+                                       (_METER_LIB, _METER_SRC, ("lc3gpu_inspector.hip",) + _ANALYZER_ONLY + _MIXER_ONLY + _RESAMPLER_ONLY)):
         comp_sig = "sources=%s\n" % _sources_hash([p_ for p_ in srcs if not p_.endswith(".cpp") and os.path.basename(p_) not in hidden])
         if force or not os.path.exists(comp_lib) or not stamped(comp_lib + ".stamp", comp_sig):
             tmp = comp_lib + ".tmp%d" % os.getpid()
@@ -200,7 +211,7 @@ def build_native(force=False, verbose=False):
     if not force and not force_link and os.path.exists(_LIB) and stamped(stamp, sig):
         return _LIB
     link_insp = ["-L" + os.path.dirname(_INSPECTOR_LIB), "-llc3gpu_inspector", "-llc3gpu_analyzer", "-llc3gpu_mixer", "-llc3gpu_resampler",
-                 "-Wl,-rpath,$ORIGIN"]
+                 "-llc3gpu_meter", "-Wl,-rpath,$ORIGIN"]
     if single:
         cmd = ["hipcc"] + extra + (["-DLC3_PROFILE"] if _PROFILE else []) + flags + ["-shared", "-o", _LIB, _SRC] + _HOST_SRCS + link_insp
         if verbose:
@@ -354,6 +365,11 @@ def load_library():
     L.lc3gpu_resampler_reset.argtypes = [vp]
     L.lc3gpu_resampler_reset_channels.argtypes = [vp, vp, i]
     L.lc3gpu_resample_mixed_views.argtypes = [vp, vp, vp, ctypes.c_size_t, vp, vp, ctypes.c_size_t, i, vp]
+    L.lc3gpu_meter_create.argtypes = [ctypes.POINTER(vp), i, vp, i]
+    L.lc3gpu_meter_destroy.argtypes = [vp]
+    L.lc3gpu_meter_reset.argtypes = [vp]
+    L.lc3gpu_meter_reset_channels.argtypes = [vp, vp, i]
+    L.lc3gpu_measure_mixed_views.argtypes = [vp, vp, i, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp]
     L.lc3gpu_encoder_state_size.restype = ctypes.c_size_t
     L.lc3gpu_encoder_state_size.argtypes = [vp]
     L.lc3gpu_encoder_state_save.argtypes = [vp, vp, ctypes.c_size_t]
@@ -446,6 +462,7 @@ ABI_SYMBOLS = [
     "lc3gpu_mixer_create", "lc3gpu_mixer_destroy", "lc3gpu_mix_mixed_views",
     "lc3gpu_resampler_create", "lc3gpu_resampler_destroy", "lc3gpu_resampler_reset", "lc3gpu_resampler_reset_channels",
     "lc3gpu_resample_mixed_views",
+    "lc3gpu_meter_create", "lc3gpu_meter_destroy", "lc3gpu_meter_reset", "lc3gpu_meter_reset_channels", "lc3gpu_measure_mixed_views",
 ]
 
 # LC3GPU_SPEC_*: opt-in corrections of the reference's deviations from the LC3 specification (default 0 = reference behaviour)
@@ -1486,6 +1503,92 @@ def resampler_plan_info():
     if rc:
         raise Lc3GpuError(rc, "resampler_plan_info")
     return spw.value, lanes.value, slots.value, hist.value
+
+
+# PCM levels (lc3gpu_measure_mixed_views): lc3gpu_meter_desc, 24 bytes, and the record of one frame, lc3gpu_level, 32 bytes
+METER_DESC_DTYPE = np.dtype([("fs_hz", "<i4"), ("frame_us", "<i4"), ("attack_q15", "<i4"), ("release_q15", "<i4"), ("threshold", "<u4"),
+                             ("hang_frames", "<i4")])
+LEVEL_DTYPE = np.dtype([("sum_sq", "<i8"), ("env", "<u4"), ("sum", "<i4"), ("min", "<i2"), ("max", "<i2"), ("n_clipped", "<u2"), ("n_cross", "<u2"),
+                        ("hang", "<u2"), ("active", "u1"), ("reserved0", "u1"), ("reserved1", "<u4")])
+assert METER_DESC_DTYPE.itemsize == 24 and LEVEL_DTYPE.itemsize == 32
+
+
+class Lc3Meter:
+    """lc3gpu_meter: the PCM levels and the speech gate of a tick, the PCM read where one view array says it lies, in one launch, with a
+    small state per channel (last sample, envelope, hang-over) carried from call to call.  descs = [(fs_hz, frame_us, attack_q15,
+    release_q15, threshold, hang_frames), ...]; max_views = the most views one call may name.  Independent of every other object; bound to
+    the device current at creation."""
+
+    def __init__(self, descs, max_views):
+        self._L = load_library()
+        self.descs = [tuple(int(x) for x in d) for d in descs]
+        self.num_channels = len(self.descs)
+        self.max_views = int(max_views)
+        arr = np.zeros(max(1, self.num_channels), METER_DESC_DTYPE)
+        for k, d in enumerate(self.descs):
+            arr[k] = d
+        h = ctypes.c_void_p()
+        rc = self._L.lc3gpu_meter_create(ctypes.byref(h), self.num_channels, _ptr(arr), self.max_views)
+        if rc:
+            raise Lc3GpuError(rc, "Lc3Meter::new")
+        self._h = h
+
+    def measure_mixed_views(self, views, d_pcm, d_active=None, d_levels=None, stream=None, pcm_elems=None, n_active=None, n_levels=None):
+        """one launch over all listed channels (a channel once per call).  Frame t of a view gets, at index flag_off + t * flag_pitch, its
+        activity byte in d_active (uint8) and its 32-byte record in d_levels (LEVEL_DTYPE, 16-byte aligned); either may be None, not both.
+        d_pcm: an int16 device buffer that overlaps neither output.  The extents default to the buffers' sizes: elements of d_pcm, bytes
+        of d_active, and for d_levels its bytes / 32 (lc3gpu_measure_mixed_views)"""
+        v = _view_list(views)
+        pe = (0 if d_pcm is None else _numel(d_pcm, "pcm_elems")) if pcm_elems is None else int(pcm_elems)
+        na = (0 if d_active is None else _numel(d_active, "n_active")) if n_active is None else int(n_active)
+        if n_levels is None:
+            nl = 0
+            if d_levels is not None:
+                item = d_levels.element_size() if hasattr(d_levels, "element_size") else (d_levels.itemsize if isinstance(d_levels, np.ndarray) else 0)
+                nl = _numel(d_levels, "n_levels") * int(item) // LEVEL_DTYPE.itemsize
+        else:
+            nl = int(n_levels)
+        n = int(v.shape[0])
+        rc = self._L.lc3gpu_measure_mixed_views(self._h, _ptr(v) if n else None, n, _ptr(d_pcm), pe, _ptr(d_active), na, _ptr(d_levels), nl,
+                                                _ptr(stream))
+        if rc:
+            raise Lc3GpuError(rc, "measure_mixed_views")
+
+    def reset(self):
+        """every channel starts from last = 0, env = 0, hang = 0 in its next call; waits for nothing, launches nothing (lc3gpu_meter_reset)"""
+        rc = self._L.lc3gpu_meter_reset(self._h)
+        if rc:
+            raise Lc3GpuError(rc, "meter_reset")
+
+    def reset_channels(self, channels):
+        """the named channels start fresh in their next call (lc3gpu_meter_reset_channels)"""
+        ch = np.ascontiguousarray(np.asarray(channels, np.int32).reshape(-1))
+        rc = self._L.lc3gpu_meter_reset_channels(self._h, _ptr(ch) if ch.size else None, int(ch.size))
+        if rc:
+            raise Lc3GpuError(rc, "meter_reset_channels")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.lc3gpu_meter_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def meter_plan_info():
+    """-> (waves = views of a workgroup, lanes per workgroup, upload ring slots, bytes of a channel's state on the device) of a meter call:
+    the plan's own figures, from the companion library (tests and tools)"""
+    load_library()  # (the main library first: it brings the companion in, and the one HIP runtime of the process)
+    C = ctypes.CDLL(_METER_LIB)
+    wpw, lanes, slots, sb = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    rc = C.lc3mtr_plan_info(ctypes.byref(wpw), ctypes.byref(lanes), ctypes.byref(slots), ctypes.byref(sb))
+    if rc:
+        raise Lc3GpuError(rc, "meter_plan_info")
+    return wpw.value, lanes.value, slots.value, sb.value
 
 
 class PinnedBuffer:

@@ -20,7 +20,8 @@ OPAQUE = {"lc3gpu_encoder": "Lc3GpuEncoder", "lc3gpu_decoder": "Lc3GpuDecoder", 
           "lc3gpu_stream_desc": "Lc3GpuStreamDesc", "lc3gpu_frame_info": "Lc3GpuFrameInfo", "lc3gpu_item": "Lc3GpuItem", "lc3gpu_mc_item": "Lc3GpuMcItem",
           "lc3gpu_view": "Lc3GpuView", "lc3gpu_inspector": "Lc3GpuInspector", "lc3gpu_analyzer": "Lc3GpuAnalyzer",
           "lc3gpu_mixer": "Lc3GpuMixer", "lc3gpu_mix_in": "Lc3GpuMixIn", "lc3gpu_mix_out": "Lc3GpuMixOut",
-          "lc3gpu_resampler": "Lc3GpuResampler", "lc3gpu_rate_desc": "Lc3GpuRateDesc"}
+          "lc3gpu_resampler": "Lc3GpuResampler", "lc3gpu_rate_desc": "Lc3GpuRateDesc",
+          "lc3gpu_meter": "Lc3GpuMeter", "lc3gpu_meter_desc": "Lc3GpuMeterDesc", "lc3gpu_level": "Lc3GpuLevel"}
 SCALAR = {"int": "i32", "unsigned": "u32", "unsigned int": "u32", "float": "f32", "double": "f64", "size_t": "usize",
           "int16_t": "i16", "uint16_t": "u16", "uint8_t": "u8", "int32_t": "i32", "uint32_t": "u32", "int64_t": "i64", "uint64_t": "u64",
           "unsigned long long": "u64", "char": "c_char", "void": "c_void"}
@@ -523,6 +524,47 @@ impl Drop for Lc3ResamplerGpu {
     }
 }
 
+/// The meter (include/lc3gpu.h): the PCM levels and the speech gate of a tick, the PCM read where one view array says it lies, in one
+/// launch, a small state per channel carried from call to call.  Independent of every other object.
+pub struct Lc3MeterGpu {
+    h: *mut Lc3GpuMeter,
+}
+impl Lc3MeterGpu {
+    /// `descs`: one descriptor per channel; `max_views`: the most views one call may name
+    pub fn new(descs: &[Lc3GpuMeterDesc], max_views: usize) -> Result<Self, i32> {
+        let mut h = core::ptr::null_mut();
+        let rc = unsafe { lc3gpu_meter_create(&mut h, descs.len() as i32, descs.as_ptr(), max_views as i32) };
+        if rc == LC3GPU_OK { Ok(Self { h }) } else { Err(rc) }
+    }
+    /// Every channel starts from last = 0, env = 0, hang = 0 in its next call; waits for nothing, launches nothing.
+    pub fn reset(&mut self) -> i32 {
+        unsafe { lc3gpu_meter_reset(self.h) }
+    }
+    /// The named channels start fresh in their next call.
+    pub fn reset_channels(&mut self, channels: &[i32]) -> i32 {
+        unsafe { lc3gpu_meter_reset_channels(self.h, channels.as_ptr(), channels.len() as i32) }
+    }
+    /// One launch over all listed channels (a channel once per call): frame t of a view gets its activity byte at `d_active[flag_off + t *
+    /// flag_pitch]` and its 32-byte record at `d_levels[...]` of the same index; either output may be null, not both.
+    ///
+    /// # Safety
+    /// device allocations of at least `pcm_elems` elements, `n_active` bytes and `n_levels` records (16-byte aligned; either output may be
+    /// null) that do not overlap and outlive the call's work; every view is checked against these extents on the host.  `views` is host
+    /// memory and free again when the call returns.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn measure_mixed_views_device(&mut self, views: &[Lc3GpuView], d_pcm: *const i16, pcm_elems: usize, d_active: *mut u8, n_active: usize,
+                                             d_levels: *mut Lc3GpuLevel, n_levels: usize, hip_stream: *mut c_void) -> i32 {
+        lc3gpu_measure_mixed_views(self.h, views.as_ptr(), views.len() as i32, d_pcm, pcm_elems, d_active, n_active, d_levels, n_levels, hip_stream)
+    }
+}
+impl Drop for Lc3MeterGpu {
+    fn drop(&mut self) {
+        unsafe {
+            lc3gpu_meter_destroy(self.h);
+        }
+    }
+}
+
 /// Encode + decode of many channels in the arrangement that measured fastest (include/lc3gpu.h, "pipeline"): device buffers, asynchronous.
 pub struct Lc3PipelineGpu {
     h: *mut Lc3GpuPipeline,
@@ -567,7 +609,7 @@ def generate():
     ]
     for c, r in sorted(OPAQUE.items()):
         if c in ("lc3gpu_stream_desc", "lc3gpu_frame_info", "lc3gpu_item", "lc3gpu_mc_item", "lc3gpu_view", "lc3gpu_mix_in", "lc3gpu_mix_out",
-                 "lc3gpu_rate_desc"):
+                 "lc3gpu_rate_desc", "lc3gpu_meter_desc", "lc3gpu_level"):
             continue
         lines += ["#[repr(C)]", "pub struct %s {" % r, "    _private: [u8; 0],", "}"]
     lines += ["/// one stream of a mixed-configuration handle (lc3gpu_stream_desc)", "#[repr(C)]", "#[derive(Clone, Copy, Debug)]",
@@ -595,6 +637,14 @@ def generate():
     lines += ["/// one channel of lc3gpu_resampler_create (lc3gpu_rate_desc, 12 bytes): the rate it comes at, the rate it leaves at, the duration",
               "#[repr(C)]", "#[derive(Clone, Copy, Debug, Default)]", "pub struct Lc3GpuRateDesc {", "    pub fs_in_hz: i32,", "    pub fs_out_hz: i32,",
               "    pub frame_us: i32,", "}", "const _: () = assert!(core::mem::size_of::<Lc3GpuRateDesc>() == 12);"]
+    lines += ["/// one channel of lc3gpu_meter_create (lc3gpu_meter_desc, 24 bytes): rate, duration, the envelope's two coefficients (Q15), the gate's",
+              "/// threshold (mean square of i16 samples, 0..2^30) and its hang-over in frames", "#[repr(C)]", "#[derive(Clone, Copy, Debug, Default)]",
+              "pub struct Lc3GpuMeterDesc {", "    pub fs_hz: i32,", "    pub frame_us: i32,", "    pub attack_q15: i32,", "    pub release_q15: i32,",
+              "    pub threshold: u32,", "    pub hang_frames: i32,", "}", "const _: () = assert!(core::mem::size_of::<Lc3GpuMeterDesc>() == 24);"]
+    lines += ["/// one frame's record of lc3gpu_measure_mixed_views (lc3gpu_level, 32 bytes)", "#[repr(C)]", "#[derive(Clone, Copy, Debug, Default)]",
+              "pub struct Lc3GpuLevel {", "    pub sum_sq: i64,", "    pub env: u32,", "    pub sum: i32,", "    pub min: i16,", "    pub max: i16,",
+              "    pub n_clipped: u16,", "    pub n_cross: u16,", "    pub hang: u16,", "    pub active: u8,", "    pub reserved0: u8,",
+              "    pub reserved1: u32,", "}", "const _: () = assert!(core::mem::size_of::<Lc3GpuLevel>() == 32);"]
     lines += ["/// one frame's record of lc3gpu_inspect (lc3gpu_frame_info, 128 bytes): status LC3GPU_FRAME_*, the side information",
               "/// (decoder/side_info.rs:20-31) and the arithmetic data (decoder/arithmetic_codec.rs:99-107)", "#[repr(C)]",
               "#[derive(Clone, Copy, Debug, Default)]", "pub struct Lc3GpuFrameInfo {"]
