@@ -21,34 +21,22 @@ _PROFILE = os.environ.get("LC3GPU_PROFILE", "0") == "1"
 # LC3_HIPCC_EXTRA="-DLC3_RECON_WAVES=6"); the default is the one build() produces
 _LIB = os.path.join(_HERE, "lib", os.environ.get("LC3GPU_LIB") or ("liblc3gpu_prof.so" if _PROFILE else "liblc3gpu.so"))
 _SRC = os.path.join(_HERE, "csrc", "lc3gpu.hip")
-# host-only sources of the library on top of its own C ABI (the pipeline object): plain C++ beside the HIP translation units
-_HOST_SRCS = [os.path.join(_HERE, "csrc", "lc3gpu_pipeline.cpp"), os.path.join(_HERE, "csrc", "lc3gpu_inspector_api.cpp"),
-              os.path.join(_HERE, "csrc", "lc3gpu_analyzer_api.cpp"), os.path.join(_HERE, "csrc", "lc3gpu_mixer_api.cpp"),
-              os.path.join(_HERE, "csrc", "lc3gpu_resampler_api.cpp"), os.path.join(_HERE, "csrc", "lc3gpu_meter_api.cpp")]
-# The companion library of the inspector (lc3gpu_inspect_mixed_views): device code of its own, beside whichever main library is built.  The
-# main library links it (run path $ORIGIN) and holds host-side entry points only, so its own kernels are what they were.
-_INSPECTOR_LIB = os.path.join(os.path.dirname(_LIB), "liblc3gpu_inspector.so")
-_INSPECTOR_SRC = os.path.join(_HERE, "csrc", "lc3gpu_inspector.hip")
-_INSPECTOR_ONLY = ("lc3gpu_inspector.hip", "lc3_host_inspect_views.h")  # sources no unit of the main library sees
-# The companion library of the analyzer (lc3gpu_analyze_mixed_views), the second of its kind: one ordinary unit, its kernel and its scratch
-# columns beside the main library, which links it the same way.
-_ANALYZER_LIB = os.path.join(os.path.dirname(_LIB), "liblc3gpu_analyzer.so")
-_ANALYZER_SRC = os.path.join(_HERE, "csrc", "lc3gpu_analyzer.hip")
-_ANALYZER_ONLY = ("lc3gpu_analyzer.hip", "lc3_host_analyze_views.h", "lc3_dev_dec_analyze.h")  # sources only the analyzer's unit sees
-# The companion library of the mixer (lc3gpu_mix_mixed_views), the third: one ordinary unit with its one kernel, built and linked the same way.
-_MIXER_LIB = os.path.join(os.path.dirname(_LIB), "liblc3gpu_mixer.so")
-_MIXER_SRC = os.path.join(_HERE, "csrc", "lc3gpu_mixer.hip")
-_MIXER_ONLY = ("lc3gpu_mixer.hip", "lc3_host_mix_views.h", "lc3_dev_mix.h")  # sources only the mixer's unit sees
-# The companion library of the resampler (lc3gpu_resample_mixed_views), the fourth: one ordinary unit with its one kernel and its own
-# coefficient table (tables/lc3_resample_tables.h), built and linked the same way.
-_RESAMPLER_LIB = os.path.join(os.path.dirname(_LIB), "liblc3gpu_resampler.so")
-_RESAMPLER_SRC = os.path.join(_HERE, "csrc", "lc3gpu_resampler.hip")
-_RESAMPLER_ONLY = ("lc3gpu_resampler.hip", "lc3_host_resample_views.h", "lc3_dev_resample.h", "lc3_resample_tables.h")  # only the resampler's unit sees
-# The companion library of the meter (lc3gpu_measure_mixed_views), the fifth: one ordinary unit with its one kernel, built and linked the
-# same way.
-_METER_LIB = os.path.join(os.path.dirname(_LIB), "liblc3gpu_meter.so")
-_METER_SRC = os.path.join(_HERE, "csrc", "lc3gpu_meter.hip")
-_METER_ONLY = ("lc3gpu_meter.hip", "lc3_host_measure_views.h", "lc3_dev_level.h")  # sources only the meter's unit sees
+# The companion libraries: device code of their own (one ordinary unit with one kernel each, csrc/lc3gpu_<name>.hip ->
+# lib/liblc3gpu_<name>.so) beside whichever main library is built.  The main library links them (run path $ORIGIN) and holds their
+# host-side entry points only (csrc/lc3gpu_<name>_api.cpp), so its own kernels are what they were.  name -> the sources that only this
+# companion's unit sees, beside its .hip; a new companion is one entry here.
+_COMPANIONS = {
+    "inspector": (),
+    "analyzer": ("lc3_host_analyze_views.h", "lc3_dev_dec_analyze.h"),
+    "mixer": ("lc3_host_mix_views.h", "lc3_dev_mix.h"),
+    "resampler": ("lc3_host_resample_views.h", "lc3_dev_resample.h", "lc3_resample_tables.h"),
+    "meter": ("lc3_host_measure_views.h", "lc3_dev_level.h"),
+}
+# sources the companions share and no unit of the main library sees: the views' check and plan, the upload ring
+_COMPANION_SHARED = ("lc3_host_inspect_views.h", "lc3_host_ring.h")
+# host-only sources of the library on top of its own C ABI (the pipeline object, the companions' entry points): plain C++ beside the HIP
+# translation units
+_HOST_SRCS = [os.path.join(_HERE, "csrc", "lc3gpu_pipeline.cpp")] + [os.path.join(_HERE, "csrc", "lc3gpu_%s_api.cpp" % _n) for _n in _COMPANIONS]
 
 class Lc3GpuError(RuntimeError):
     def __init__(self, code, what=""):
@@ -87,29 +75,61 @@ def library_path():
     return _LIB
 
 
+def companion_library_path(name):
+    """the companion library of that name (a key of _COMPANIONS), which the main library links: beside the main library"""
+    if name not in _COMPANIONS:
+        raise KeyError(name)
+    return os.path.join(os.path.dirname(_LIB), "liblc3gpu_%s.so" % name)
+
+
 def inspector_library_path():
-    """the companion library of the inspector (lc3gpu_inspect_mixed_views), which the main library links"""
-    return _INSPECTOR_LIB
+    """the companion library of the inspector (lc3gpu_inspect_mixed_views)"""
+    return companion_library_path("inspector")
 
 
 def analyzer_library_path():
-    """the companion library of the analyzer (lc3gpu_analyze_mixed_views), which the main library links"""
-    return _ANALYZER_LIB
+    """the companion library of the analyzer (lc3gpu_analyze_mixed_views)"""
+    return companion_library_path("analyzer")
 
 
 def mixer_library_path():
-    """the companion library of the mixer (lc3gpu_mix_mixed_views), which the main library links"""
-    return _MIXER_LIB
+    """the companion library of the mixer (lc3gpu_mix_mixed_views)"""
+    return companion_library_path("mixer")
 
 
 def resampler_library_path():
-    """the companion library of the resampler (lc3gpu_resample_mixed_views), which the main library links"""
-    return _RESAMPLER_LIB
+    """the companion library of the resampler (lc3gpu_resample_mixed_views)"""
+    return companion_library_path("resampler")
 
 
 def meter_library_path():
-    """the companion library of the meter (lc3gpu_measure_mixed_views), which the main library links"""
-    return _METER_LIB
+    """the companion library of the meter (lc3gpu_measure_mixed_views)"""
+    return companion_library_path("meter")
+
+
+def companion_own(name):
+    """the file names of the sources that only this companion's unit sees: its .hip and its entry of the table"""
+    return ("lc3gpu_%s.hip" % name,) + _COMPANIONS[name]
+
+
+def _device_sources():
+    """every source a HIP translation unit of any library could see: the headers and units under csrc/, the public header, the tables"""
+    csrc = os.path.join(_HERE, "csrc")
+    return [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".h", ".hip"))] + [
+        os.path.join(_ROOT, "include", "lc3gpu.h"), os.path.join(_ROOT, "tables", "lc3_tables.h"), os.path.join(_ROOT, "tables", "lc3_resample_tables.h")]
+
+
+def companion_sources(name):
+    """the files a companion's stamp hashes -- what its unit can see: its own sources, the ones the companions share and the common device
+    headers; none of another companion's own"""
+    hidden = {f for other in _COMPANIONS if other != name for f in companion_own(other)}
+    return [p_ for p_ in _device_sources() if os.path.basename(p_) not in hidden]
+
+
+def main_sources():
+    """the files the stamps of the main library's translation units hash: no companion's own sources and none of the shared ones"""
+    hidden = {f for name in _COMPANIONS for f in companion_own(name)} | set(_COMPANION_SHARED)
+    return [p_ for p_ in _device_sources() if os.path.basename(p_) not in hidden]
 
 
 def _translation_units():
@@ -154,17 +174,14 @@ def build_native(force=False, verbose=False):
     LC3_HIPCC_EXTRA_MAIN="-D..." (timing experiments on the headline kernels): the multi-unit build with those flags on the MAIN unit only;
     the other units' objects are the production ones.  A library remembers the switches it was built with (<lib>.stamp) and is rebuilt
     when they differ; experiment builds need their own file name (LC3GPU_LIB) so that they never replace the default library.
-    Every flavour links the inspector's companion library (csrc/lc3gpu_inspector.hip -> lib/liblc3gpu_inspector.so, one ordinary unit),
-    which is built and stamped here first; its own sources are no part of what the main library's translation units are stamped with.
-    The analyzer's companion (csrc/lc3gpu_analyzer.hip -> lib/liblc3gpu_analyzer.so) and the mixer's (csrc/lc3gpu_mixer.hip ->
-    lib/liblc3gpu_mixer.so) are built, stamped and linked the same way, and so is the resampler's (csrc/lc3gpu_resampler.hip with
-    tables/lc3_resample_tables.h -> lib/liblc3gpu_resampler.so) and the meter's (csrc/lc3gpu_meter.hip -> lib/liblc3gpu_meter.so)."""
-    srcs = [os.path.join(_HERE, "csrc", f) for f in os.listdir(os.path.join(_HERE, "csrc")) if f.endswith((".h", ".hip", ".cpp"))]
-    srcs += [os.path.join(_ROOT, "include", "lc3gpu.h"), os.path.join(_ROOT, "tables", "lc3_tables.h"),
-             os.path.join(_ROOT, "tables", "lc3_resample_tables.h")]
+    Every flavour links every companion library of the table (_COMPANIONS: csrc/lc3gpu_<name>.hip -> lib/liblc3gpu_<name>.so, one ordinary
+    unit each), which are built and stamped here first, each with the sources its unit can see (companion_sources); their own and their
+    shared sources are no part of what the main library's translation units are stamped with (main_sources)."""
+    csrc = os.path.join(_HERE, "csrc")
+    srcs = _device_sources() + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".cpp")]
     src_hash = _sources_hash(srcs)  # taken BEFORE anything is compiled: what the objects below are guaranteed to be at least as old as
     # (the HIP translation units do not see the host-only sources: an edit there relinks the library without recompiling them)
-    dev_hash = _sources_hash([p_ for p_ in srcs if not p_.endswith(".cpp") and os.path.basename(p_) not in _INSPECTOR_ONLY + _ANALYZER_ONLY + _MIXER_ONLY + _RESAMPLER_ONLY + _METER_ONLY])
+    dev_hash = _sources_hash(main_sources())
     extra = os.environ.get("LC3_HIPCC_EXTRA", "").split()  # compiler experiments
     extra_main = os.environ.get("LC3_HIPCC_EXTRA_MAIN", "").split()
     if (extra or extra_main) and not os.environ.get("LC3GPU_LIB"):
@@ -185,18 +202,14 @@ def build_native(force=False, verbose=False):
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function",
              "-Wno-missing-braces"]
     # the companions first (every flavour of the main library links the same ones): one ordinary unit each, stamped with the contents of
-    # the sources that unit can see (the earlier companions' stamps are what they were before the resampler and the meter existed: their
-    # sources are hidden from them)
+    # the sources that unit can see (a companion's stamp does not change when another one is added: its sources are hidden from it)
     force_link = False
-    for comp_lib, comp_src, hidden in ((_INSPECTOR_LIB, _INSPECTOR_SRC, _ANALYZER_ONLY + _MIXER_ONLY + _RESAMPLER_ONLY + _METER_ONLY),
-                                       (_ANALYZER_LIB, _ANALYZER_SRC, ("lc3gpu_inspector.hip",) + _MIXER_ONLY + _RESAMPLER_ONLY + _METER_ONLY),
-                                       (_MIXER_LIB, _MIXER_SRC, ("lc3gpu_inspector.hip",) + _ANALYZER_ONLY + _RESAMPLER_ONLY + _METER_ONLY),
-                                       (_RESAMPLER_LIB, _RESAMPLER_SRC, ("lc3gpu_inspector.hip",) + _ANALYZER_ONLY + _MIXER_ONLY + _METER_ONLY),
-                                       (_METER_LIB, _METER_SRC, ("lc3gpu_inspector.hip",) + _ANALYZER_ONLY + _MIXER_ONLY + _RESAMPLER_ONLY)):
-        comp_sig = "sources=%s\n" % _sources_hash([p_ for p_ in srcs if not p_.endswith(".cpp") and os.path.basename(p_) not in hidden])
+    for name in _COMPANIONS:
+        comp_lib = companion_library_path(name)
+        comp_sig = "sources=%s\n" % _sources_hash(companion_sources(name))
         if force or not os.path.exists(comp_lib) or not stamped(comp_lib + ".stamp", comp_sig):
             tmp = comp_lib + ".tmp%d" % os.getpid()
-            cmd = ["hipcc"] + flags + ["-shared", "-o", tmp, comp_src]
+            cmd = ["hipcc"] + flags + ["-shared", "-o", tmp, os.path.join(csrc, "lc3gpu_%s.hip" % name)]
             if verbose:
                 print(" ".join(cmd))
             try:
@@ -210,8 +223,7 @@ def build_native(force=False, verbose=False):
             force_link = True
     if not force and not force_link and os.path.exists(_LIB) and stamped(stamp, sig):
         return _LIB
-    link_insp = ["-L" + os.path.dirname(_INSPECTOR_LIB), "-llc3gpu_inspector", "-llc3gpu_analyzer", "-llc3gpu_mixer", "-llc3gpu_resampler",
-                 "-llc3gpu_meter", "-Wl,-rpath,$ORIGIN"]
+    link_insp = ["-L" + os.path.dirname(_LIB)] + ["-llc3gpu_" + name for name in _COMPANIONS] + ["-Wl,-rpath,$ORIGIN"]
     if single:
         cmd = ["hipcc"] + extra + (["-DLC3_PROFILE"] if _PROFILE else []) + flags + ["-shared", "-o", _LIB, _SRC] + _HOST_SRCS + link_insp
         if verbose:
@@ -670,6 +682,19 @@ def _numel(x, what):
         return int(x.numel())
     if isinstance(x, np.ndarray):
         return int(x.size)
+    raise TypeError("%s: pass the buffer's extent when the buffer is a bare pointer" % what)
+
+
+def _records(buf, given, record_bytes, what):
+    """the extent of an output in records of record_bytes: 0 without the output, else `given`, else from the size in bytes of the torch
+    tensor or numpy array (whatever its element type); a bare pointer needs it given"""
+    if buf is None:
+        return 0
+    if given is not None:
+        return int(given)
+    if isinstance(buf, np.ndarray) or hasattr(buf, "element_size"):
+        size = buf.itemsize if isinstance(buf, np.ndarray) else buf.element_size()
+        return _numel(buf, what) * int(size) // record_bytes
     raise TypeError("%s: pass the buffer's extent when the buffer is a bare pointer" % what)
 
 
@@ -1216,21 +1241,85 @@ class Lc3Decoder:
             pass
 
 
-class Lc3Inspector:
+class _Companion:
+    """what the handle classes of the companion libraries share: the handle of lc3gpu_<_NAME>_create, the descriptors, close / __del__, and
+    "call, or raise with the call's name".  A subclass names its object (_NAME), may give its descriptor array a dtype of its own (_DESC_DTYPE;
+    default: lc3gpu_stream_desc), and its __init__ passes _create what its create takes beyond descs and max_views"""
+    _NAME = None
+    _DESC_DTYPE = None
+
+    @staticmethod
+    def _desc(d):
+        return int(d[0]), int(d[1]), int(d[2])
+
+    def _create(self, descs, max_views, *more):
+        self._L = load_library()
+        self.descs = [self._desc(d) for d in descs]
+        self.num_channels = len(self.descs)
+        self.max_views = int(max_views)
+        if self._DESC_DTYPE is None:
+            arr = _desc_array(self.descs)
+        else:
+            table = np.zeros(max(1, self.num_channels), self._DESC_DTYPE)
+            for k, d in enumerate(self.descs):
+                table[k] = d
+            arr = _ptr(table)
+        h = ctypes.c_void_p()
+        rc = getattr(self._L, "lc3gpu_%s_create" % self._NAME)(ctypes.byref(h), self.num_channels, arr, self.max_views, *more)
+        if rc:
+            raise Lc3GpuError(rc, type(self).__name__ + "::new")
+        self._h = h
+
+    def _call(self, fn, *args):
+        """lc3gpu_<fn>(handle, *args), or Lc3GpuError(rc, fn)"""
+        rc = getattr(self._L, "lc3gpu_" + fn)(self._h, *args)
+        if rc:
+            raise Lc3GpuError(rc, fn)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(self._L, "lc3gpu_%s_destroy" % self._NAME)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _ChannelStates(_Companion):
+    """a companion with a state per channel on the device: reset and reset_channels (lc3gpu_<_NAME>_reset, lc3gpu_<_NAME>_reset_channels)"""
+
+    def reset(self):
+        """every channel starts fresh in its next call -- a zero history, or last = 0, env = 0, hang = 0; waits for nothing, launches nothing"""
+        self._call(self._NAME + "_reset")
+
+    def reset_channels(self, channels):
+        """the named channels start fresh in their next call"""
+        ch = np.ascontiguousarray(np.asarray(channels, np.int32).reshape(-1))
+        self._call(self._NAME + "_reset_channels", _ptr(ch) if ch.size else None, int(ch.size))
+
+
+def _companion_plan_info(name, fn, types, *args):
+    """the values <fn>(*args, &out...) of the companion library `name` writes, one per ctypes type of `types`: the plan's own figures, from
+    the companion itself (tests and tools)"""
+    load_library()  # (the main library first: it brings the companion in, and the one HIP runtime of the process)
+    out = [t() for t in types]
+    rc = getattr(ctypes.CDLL(companion_library_path(name)), fn)(*args, *[ctypes.byref(o) for o in out])
+    if rc:
+        raise Lc3GpuError(rc, name + "_plan_info")
+    return tuple(o.value for o in out)
+
+
+class Lc3Inspector(_Companion):
     """lc3gpu_inspector: the status and the side information of every frame of a tick, for the very views the tick passes to
     Lc3Decoder.decode_mixed_views.  descs = [(fs_hz, frame_us, nbytes), ...] as for Lc3Decoder.mixed; max_views = the most views one call
     may name.  Independent of every codec handle; bound to the device current at creation."""
+    _NAME = "inspector"
 
     def __init__(self, descs, max_views):
-        self._L = load_library()
-        self.descs = [(int(d[0]), int(d[1]), int(d[2])) for d in descs]
-        self.num_channels = len(self.descs)
-        self.max_views = int(max_views)
-        h = ctypes.c_void_p()
-        rc = self._L.lc3gpu_inspector_create(ctypes.byref(h), self.num_channels, _desc_array(self.descs), self.max_views)
-        if rc:
-            raise Lc3GpuError(rc, "Lc3Inspector::new")
-        self._h = h
+        self._create(descs, max_views)
 
     def inspect_mixed_views(self, views, d_in, d_status=None, d_info=None, d_bad_frame=None, stream=None, in_bytes=None, n_status=None, n_info=None,
                             n_flags=None):
@@ -1242,76 +1331,31 @@ class Lc3Inspector:
         ib = _numel(d_in, "in_bytes") if in_bytes is None else int(in_bytes)
         nfl = 0 if d_bad_frame is None else (_numel(d_bad_frame, "n_flags") if n_flags is None else int(n_flags))
         nst = 0 if d_status is None else (_numel(d_status, "n_status") if n_status is None else int(n_status))
-        if d_info is None:
-            nin = 0
-        elif n_info is not None:
-            nin = int(n_info)
-        elif isinstance(d_info, np.ndarray) or hasattr(d_info, "element_size"):
-            size = d_info.itemsize if isinstance(d_info, np.ndarray) else d_info.element_size()
-            nin = _numel(d_info, "n_info") * int(size) // FRAME_INFO_DTYPE.itemsize
-        else:
-            raise TypeError("n_info: pass the buffer's extent when the buffer is a bare pointer")
-        rc = self._L.lc3gpu_inspect_mixed_views(self._h, _ptr(v), int(v.shape[0]), _ptr(d_in), ib, _ptr(d_bad_frame), nfl, _ptr(d_status), nst,
-                                                _ptr(d_info), nin, _ptr(stream))
-        if rc:
-            raise Lc3GpuError(rc, "inspect_mixed_views")
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.lc3gpu_inspector_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        nin = _records(d_info, n_info, FRAME_INFO_DTYPE.itemsize, "n_info")
+        self._call("inspect_mixed_views", _ptr(v), int(v.shape[0]), _ptr(d_in), ib, _ptr(d_bad_frame), nfl, _ptr(d_status), nst, _ptr(d_info), nin,
+                   _ptr(stream))
 
 
 def inspector_plan_info(max_nbytes):
-    """-> (frames per workgroup, dynamic LDS bytes, upload ring slots) of an inspector call whose largest frame size is max_nbytes: the
-    plan's own figures, from the companion library (tests and tools)"""
-    load_library()  # (the main library first: it brings the companion in, and the one HIP runtime of the process)
-    C = ctypes.CDLL(_INSPECTOR_LIB)
-    fpb, lds, slots = ctypes.c_int(), ctypes.c_size_t(), ctypes.c_int()
-    rc = C.lc3insp_plan_info(int(max_nbytes), ctypes.byref(fpb), ctypes.byref(lds), ctypes.byref(slots))
-    if rc:
-        raise Lc3GpuError(rc, "inspector_plan_info")
-    return fpb.value, lds.value, slots.value
+    """-> (frames per workgroup, dynamic LDS bytes, upload ring slots) of an inspector call whose largest frame size is max_nbytes"""
+    return _companion_plan_info("inspector", "lc3insp_plan_info", (ctypes.c_int, ctypes.c_size_t, ctypes.c_int), int(max_nbytes))
 
 
 # frame analysis (lc3gpu_analyze_mixed_views): the row lengths of d_bands and d_spec (LC3GPU_BANDS, LC3GPU_SPEC_LINES)
 BANDS, SPEC_LINES = 64, 400
 
 
-class Lc3Analyzer:
+class Lc3Analyzer(_Companion):
     """lc3gpu_analyzer: the reconstructed spectrum, the 64 band energies and the total energy of every frame of a tick, for the very views
     the tick passes to Lc3Decoder.decode_mixed_views and Lc3Inspector.inspect_mixed_views, without decoding to PCM.  descs = [(fs_hz,
     frame_us, nbytes), ...] as for Lc3Decoder.mixed; max_views / max_frames = the most views one call may name and the most frames it may
     hold.  Independent of every codec handle; bound to the device current at creation."""
 
-    def __init__(self, descs, max_views, max_frames):
-        self._L = load_library()
-        self.descs = [(int(d[0]), int(d[1]), int(d[2])) for d in descs]
-        self.num_channels = len(self.descs)
-        self.max_views, self.max_frames = int(max_views), int(max_frames)
-        h = ctypes.c_void_p()
-        rc = self._L.lc3gpu_analyzer_create(ctypes.byref(h), self.num_channels, _desc_array(self.descs), self.max_views, self.max_frames)
-        if rc:
-            raise Lc3GpuError(rc, "Lc3Analyzer::new")
-        self._h = h
+    _NAME = "analyzer"
 
-    @staticmethod
-    def _rows(buf, given, row, what):
-        """the extent of an output in rows of `row` float32: given, or from the buffer's size in bytes"""
-        if buf is None:
-            return 0
-        if given is not None:
-            return int(given)
-        if isinstance(buf, np.ndarray) or hasattr(buf, "element_size"):
-            size = buf.itemsize if isinstance(buf, np.ndarray) else buf.element_size()
-            return _numel(buf, what) * int(size) // (4 * row)
-        raise TypeError(what + ": pass the buffer's extent when the buffer is a bare pointer")
+    def __init__(self, descs, max_views, max_frames):
+        self.max_frames = int(max_frames)
+        self._create(descs, max_views, self.max_frames)
 
     def analyze_mixed_views(self, views, d_in, d_energy=None, d_bands=None, d_spec=None, d_bad_frame=None, stream=None, in_bytes=None,
                             n_energy=None, n_bands=None, n_spec=None, n_flags=None):
@@ -1322,36 +1366,17 @@ class Lc3Analyzer:
         v = _view_list(views)
         ib = _numel(d_in, "in_bytes") if in_bytes is None else int(in_bytes)
         nfl = 0 if d_bad_frame is None else (_numel(d_bad_frame, "n_flags") if n_flags is None else int(n_flags))
-        ne = self._rows(d_energy, n_energy, 1, "n_energy")
-        nbd = self._rows(d_bands, n_bands, BANDS, "n_bands")
-        nsp = self._rows(d_spec, n_spec, SPEC_LINES, "n_spec")
-        rc = self._L.lc3gpu_analyze_mixed_views(self._h, _ptr(v), int(v.shape[0]), _ptr(d_in), ib, _ptr(d_bad_frame), nfl, _ptr(d_energy), ne,
-                                                _ptr(d_bands), nbd, _ptr(d_spec), nsp, _ptr(stream))
-        if rc:
-            raise Lc3GpuError(rc, "analyze_mixed_views")
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.lc3gpu_analyzer_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        ne = _records(d_energy, n_energy, 4, "n_energy")  # (float32 rows of 1, 64 and 400)
+        nbd = _records(d_bands, n_bands, 4 * BANDS, "n_bands")
+        nsp = _records(d_spec, n_spec, 4 * SPEC_LINES, "n_spec")
+        self._call("analyze_mixed_views", _ptr(v), int(v.shape[0]), _ptr(d_in), ib, _ptr(d_bad_frame), nfl, _ptr(d_energy), ne, _ptr(d_bands), nbd,
+                   _ptr(d_spec), nsp, _ptr(stream))
 
 
 def analyzer_plan_info(max_nbytes):
     """-> (frames per workgroup, dynamic LDS bytes, upload ring slots, words of a frame's scratch column) of an analyzer call whose largest
-    frame size is max_nbytes: the plan's own figures, from the companion library (tests and tools)"""
-    load_library()  # (the main library first: it brings the companion in, and the one HIP runtime of the process)
-    C = ctypes.CDLL(_ANALYZER_LIB)
-    fpb, lds, slots, words = ctypes.c_int(), ctypes.c_size_t(), ctypes.c_int(), ctypes.c_int()
-    rc = C.lc3ana_plan_info(int(max_nbytes), ctypes.byref(fpb), ctypes.byref(lds), ctypes.byref(slots), ctypes.byref(words))
-    if rc:
-        raise Lc3GpuError(rc, "analyzer_plan_info")
-    return fpb.value, lds.value, slots.value, words.value
+    frame size is max_nbytes"""
+    return _companion_plan_info("analyzer", "lc3ana_plan_info", (ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_int), int(max_nbytes))
 
 
 # room mixes (lc3gpu_mix_mixed_views): the entries of the two room tables (lc3gpu_mix_in, lc3gpu_mix_out, 8 bytes each) and unity gain
@@ -1371,22 +1396,16 @@ def _mix_table(rows, dtype):
     return out
 
 
-class Lc3Mixer:
+class Lc3Mixer(_Companion):
     """lc3gpu_mixer: the room mixes of a tick, the PCM read where Lc3Decoder.decode_mixed_views wrote it and written where
     Lc3Encoder.encode_mixed_views reads it, in one launch.  descs = [(fs_hz, frame_us, nbytes), ...] as for Lc3Decoder.mixed (only the
     rate and the duration are used); max_views = the most input plus output views one call may name, and the number of buses.
     Independent of every codec handle, of the inspector and of the analyzer; bound to the device current at creation."""
 
+    _NAME = "mixer"
+
     def __init__(self, descs, max_views):
-        self._L = load_library()
-        self.descs = [(int(d[0]), int(d[1]), int(d[2])) for d in descs]
-        self.num_channels = len(self.descs)
-        self.max_views = int(max_views)
-        h = ctypes.c_void_p()
-        rc = self._L.lc3gpu_mixer_create(ctypes.byref(h), self.num_channels, _desc_array(self.descs), self.max_views)
-        if rc:
-            raise Lc3GpuError(rc, "Lc3Mixer::new")
-        self._h = h
+        self._create(descs, max_views)
 
     def mix_mixed_views(self, in_views, ins, d_pcm_in, out_views, outs, d_pcm_out, stream=None, in_elems=None, out_elems=None):
         """one launch over all rooms.  ins[i] = (bus, gain_q14) belongs to in_views[i], outs[o] = (bus, minus) to out_views[o]; output o
@@ -1399,58 +1418,28 @@ class Lc3Mixer:
             raise ValueError("one (bus, gain_q14) per input view and one (bus, minus) per output view")
         ie = (0 if d_pcm_in is None else _numel(d_pcm_in, "in_elems")) if in_elems is None else int(in_elems)
         oe = (0 if d_pcm_out is None else _numel(d_pcm_out, "out_elems")) if out_elems is None else int(out_elems)
-        rc = self._L.lc3gpu_mix_mixed_views(self._h, _ptr(vi) if vi.shape[0] else None, _ptr(ti) if ti.shape[0] else None, int(vi.shape[0]),
-                                            _ptr(d_pcm_in), ie, _ptr(vo) if vo.shape[0] else None, _ptr(to) if to.shape[0] else None,
-                                            int(vo.shape[0]), _ptr(d_pcm_out), oe, _ptr(stream))
-        if rc:
-            raise Lc3GpuError(rc, "mix_mixed_views")
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.lc3gpu_mixer_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._call("mix_mixed_views", _ptr(vi) if vi.shape[0] else None, _ptr(ti) if ti.shape[0] else None, int(vi.shape[0]), _ptr(d_pcm_in), ie,
+                   _ptr(vo) if vo.shape[0] else None, _ptr(to) if to.shape[0] else None, int(vo.shape[0]), _ptr(d_pcm_out), oe, _ptr(stream))
 
 
 def mixer_plan_info():
-    """-> (samples of a bus per workgroup, lanes per workgroup, upload ring slots) of a mixer call: the plan's own figures, from the
-    companion library (tests and tools)"""
-    load_library()  # (the main library first: it brings the companion in, and the one HIP runtime of the process)
-    C = ctypes.CDLL(_MIXER_LIB)
-    spw, lanes, slots = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    rc = C.lc3mix_plan_info(ctypes.byref(spw), ctypes.byref(lanes), ctypes.byref(slots))
-    if rc:
-        raise Lc3GpuError(rc, "mixer_plan_info")
-    return spw.value, lanes.value, slots.value
+    """-> (samples of a bus per workgroup, lanes per workgroup, upload ring slots) of a mixer call"""
+    return _companion_plan_info("mixer", "lc3mix_plan_info", (ctypes.c_int,) * 3)
 
 
 # rate conversion (lc3gpu_resample_mixed_views): lc3gpu_rate_desc, 12 bytes
 RATE_DESC_DTYPE = np.dtype([("fs_in_hz", "<i4"), ("fs_out_hz", "<i4"), ("frame_us", "<i4")])
 
 
-class Lc3Resampler:
+class Lc3Resampler(_ChannelStates):
     """lc3gpu_resampler: the rate conversions of a tick, the PCM read where one view array says and written where a second says, in one
     launch, with a FIR history per channel.  descs = [(fs_in_hz, fs_out_hz, frame_us), ...]; max_views = the most pairs of views one
     call may name.  Independent of every codec handle and of the three other companions; bound to the device current at creation."""
 
+    _NAME, _DESC_DTYPE = "resampler", RATE_DESC_DTYPE
+
     def __init__(self, descs, max_views):
-        self._L = load_library()
-        self.descs = [(int(d[0]), int(d[1]), int(d[2])) for d in descs]
-        self.num_channels = len(self.descs)
-        self.max_views = int(max_views)
-        arr = np.zeros(max(1, self.num_channels), RATE_DESC_DTYPE)
-        for k, d in enumerate(self.descs):
-            arr[k] = d
-        h = ctypes.c_void_p()
-        rc = self._L.lc3gpu_resampler_create(ctypes.byref(h), self.num_channels, _ptr(arr), self.max_views)
-        if rc:
-            raise Lc3GpuError(rc, "Lc3Resampler::new")
-        self._h = h
+        self._create(descs, max_views)
 
     def resample_mixed_views(self, in_views, d_pcm_in, out_views, d_pcm_out, stream=None, in_elems=None, out_elems=None):
         """one launch over all listed channels.  in_views[i] and out_views[i] belong together (same channel, same n_frames; a channel
@@ -1463,46 +1452,12 @@ class Lc3Resampler:
         ie = (0 if d_pcm_in is None else _numel(d_pcm_in, "in_elems")) if in_elems is None else int(in_elems)
         oe = (0 if d_pcm_out is None else _numel(d_pcm_out, "out_elems")) if out_elems is None else int(out_elems)
         n = int(vi.shape[0])
-        rc = self._L.lc3gpu_resample_mixed_views(self._h, _ptr(vi) if n else None, _ptr(d_pcm_in), ie, _ptr(vo) if n else None, _ptr(d_pcm_out),
-                                                 oe, n, _ptr(stream))
-        if rc:
-            raise Lc3GpuError(rc, "resample_mixed_views")
-
-    def reset(self):
-        """every channel reads a zero history in its next call; waits for nothing, launches nothing (lc3gpu_resampler_reset)"""
-        rc = self._L.lc3gpu_resampler_reset(self._h)
-        if rc:
-            raise Lc3GpuError(rc, "resampler_reset")
-
-    def reset_channels(self, channels):
-        """the named channels read a zero history in their next call (lc3gpu_resampler_reset_channels)"""
-        ch = np.ascontiguousarray(np.asarray(channels, np.int32).reshape(-1))
-        rc = self._L.lc3gpu_resampler_reset_channels(self._h, _ptr(ch) if ch.size else None, int(ch.size))
-        if rc:
-            raise Lc3GpuError(rc, "resampler_reset_channels")
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.lc3gpu_resampler_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._call("resample_mixed_views", _ptr(vi) if n else None, _ptr(d_pcm_in), ie, _ptr(vo) if n else None, _ptr(d_pcm_out), oe, n, _ptr(stream))
 
 
 def resampler_plan_info():
-    """-> (output samples of a view per workgroup, lanes per workgroup, upload ring slots, samples of a history buffer) of a resampler
-    call: the plan's own figures, from the companion library (tests and tools)"""
-    load_library()  # (the main library first: it brings the companion in, and the one HIP runtime of the process)
-    C = ctypes.CDLL(_RESAMPLER_LIB)
-    spw, lanes, slots, hist = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    rc = C.lc3rs_plan_info(ctypes.byref(spw), ctypes.byref(lanes), ctypes.byref(slots), ctypes.byref(hist))
-    if rc:
-        raise Lc3GpuError(rc, "resampler_plan_info")
-    return spw.value, lanes.value, slots.value, hist.value
+    """-> (output samples of a view per workgroup, lanes per workgroup, upload ring slots, samples of a history buffer) of a resampler call"""
+    return _companion_plan_info("resampler", "lc3rs_plan_info", (ctypes.c_int,) * 4)
 
 
 # PCM levels (lc3gpu_measure_mixed_views): lc3gpu_meter_desc, 24 bytes, and the record of one frame, lc3gpu_level, 32 bytes
@@ -1513,25 +1468,20 @@ LEVEL_DTYPE = np.dtype([("sum_sq", "<i8"), ("env", "<u4"), ("sum", "<i4"), ("min
 assert METER_DESC_DTYPE.itemsize == 24 and LEVEL_DTYPE.itemsize == 32
 
 
-class Lc3Meter:
+class Lc3Meter(_ChannelStates):
     """lc3gpu_meter: the PCM levels and the speech gate of a tick, the PCM read where one view array says it lies, in one launch, with a
     small state per channel (last sample, envelope, hang-over) carried from call to call.  descs = [(fs_hz, frame_us, attack_q15,
     release_q15, threshold, hang_frames), ...]; max_views = the most views one call may name.  Independent of every other object; bound to
     the device current at creation."""
 
+    _NAME, _DESC_DTYPE = "meter", METER_DESC_DTYPE
+
+    @staticmethod
+    def _desc(d):
+        return tuple(int(x) for x in d)
+
     def __init__(self, descs, max_views):
-        self._L = load_library()
-        self.descs = [tuple(int(x) for x in d) for d in descs]
-        self.num_channels = len(self.descs)
-        self.max_views = int(max_views)
-        arr = np.zeros(max(1, self.num_channels), METER_DESC_DTYPE)
-        for k, d in enumerate(self.descs):
-            arr[k] = d
-        h = ctypes.c_void_p()
-        rc = self._L.lc3gpu_meter_create(ctypes.byref(h), self.num_channels, _ptr(arr), self.max_views)
-        if rc:
-            raise Lc3GpuError(rc, "Lc3Meter::new")
-        self._h = h
+        self._create(descs, max_views)
 
     def measure_mixed_views(self, views, d_pcm, d_active=None, d_levels=None, stream=None, pcm_elems=None, n_active=None, n_levels=None):
         """one launch over all listed channels (a channel once per call).  Frame t of a view gets, at index flag_off + t * flag_pitch, its
@@ -1541,54 +1491,14 @@ class Lc3Meter:
         v = _view_list(views)
         pe = (0 if d_pcm is None else _numel(d_pcm, "pcm_elems")) if pcm_elems is None else int(pcm_elems)
         na = (0 if d_active is None else _numel(d_active, "n_active")) if n_active is None else int(n_active)
-        if n_levels is None:
-            nl = 0
-            if d_levels is not None:
-                item = d_levels.element_size() if hasattr(d_levels, "element_size") else (d_levels.itemsize if isinstance(d_levels, np.ndarray) else 0)
-                nl = _numel(d_levels, "n_levels") * int(item) // LEVEL_DTYPE.itemsize
-        else:
-            nl = int(n_levels)
+        nl = _records(d_levels, n_levels, LEVEL_DTYPE.itemsize, "n_levels")
         n = int(v.shape[0])
-        rc = self._L.lc3gpu_measure_mixed_views(self._h, _ptr(v) if n else None, n, _ptr(d_pcm), pe, _ptr(d_active), na, _ptr(d_levels), nl,
-                                                _ptr(stream))
-        if rc:
-            raise Lc3GpuError(rc, "measure_mixed_views")
-
-    def reset(self):
-        """every channel starts from last = 0, env = 0, hang = 0 in its next call; waits for nothing, launches nothing (lc3gpu_meter_reset)"""
-        rc = self._L.lc3gpu_meter_reset(self._h)
-        if rc:
-            raise Lc3GpuError(rc, "meter_reset")
-
-    def reset_channels(self, channels):
-        """the named channels start fresh in their next call (lc3gpu_meter_reset_channels)"""
-        ch = np.ascontiguousarray(np.asarray(channels, np.int32).reshape(-1))
-        rc = self._L.lc3gpu_meter_reset_channels(self._h, _ptr(ch) if ch.size else None, int(ch.size))
-        if rc:
-            raise Lc3GpuError(rc, "meter_reset_channels")
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.lc3gpu_meter_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._call("measure_mixed_views", _ptr(v) if n else None, n, _ptr(d_pcm), pe, _ptr(d_active), na, _ptr(d_levels), nl, _ptr(stream))
 
 
 def meter_plan_info():
-    """-> (waves = views of a workgroup, lanes per workgroup, upload ring slots, bytes of a channel's state on the device) of a meter call:
-    the plan's own figures, from the companion library (tests and tools)"""
-    load_library()  # (the main library first: it brings the companion in, and the one HIP runtime of the process)
-    C = ctypes.CDLL(_METER_LIB)
-    wpw, lanes, slots, sb = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    rc = C.lc3mtr_plan_info(ctypes.byref(wpw), ctypes.byref(lanes), ctypes.byref(slots), ctypes.byref(sb))
-    if rc:
-        raise Lc3GpuError(rc, "meter_plan_info")
-    return wpw.value, lanes.value, slots.value, sb.value
+    """-> (waves = views of a workgroup, lanes per workgroup, upload ring slots, bytes of a channel's state on the device) of a meter call"""
+    return _companion_plan_info("meter", "lc3mtr_plan_info", (ctypes.c_int,) * 4)
 
 
 class PinnedBuffer:

@@ -154,62 +154,25 @@ __global__ __launch_bounds__(256) void lc3_analyze_views_kernel(const lc3_iv_row
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------
-namespace {
-#define ANA_TRY(expr)                      \
-    do {                                   \
-        if ((expr) != hipSuccess) {        \
-            (void)hipGetLastError();       \
-            return LC3GPU_EHIP;            \
-        }                                  \
-    } while (0)
-
-// calls in flight before a call waits for the oldest of its own uploads
-constexpr int kRingSlots = 8;
-
-// makes the analyzer's device current for the scope of a call
-struct OnDevice {
-    int prev = -1, dev;
-    bool switched = false;
-    explicit OnDevice(int d) : dev(d) {
-        if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = hipSetDevice(dev) == hipSuccess;
-    }
-    ~OnDevice() {
-        if (switched) (void)hipSetDevice(prev);
-    }
-};
-}  // namespace
+#include "lc3_host_ring.h"
 
 struct lc3gpu_analyzer {
-    int device = 0, max_views = 0, max_frames = 0;
+    int max_views = 0, max_frames = 0;
     std::vector<lc3_iv_stream> streams;
     lc3_iv_plan plan;
     // the scratch columns: max_frames of LC3_PLANE_WORDS words, shared by every call of this analyzer
     int32_t *d_columns = nullptr;
-    // the ring: slot k is slot_bytes of pinned host memory and as many of device memory (a call's view rows, then its bucket rows), and an
-    // event behind the kernel that read it last
-    size_t slot_bytes = 0;
-    uint8_t *h_ring = nullptr, *d_ring = nullptr;
-    hipEvent_t done[kRingSlots] = {};
-    bool recorded[kRingSlots] = {};
-    int next = 0;
-    // the stream of the previous call and the ring slot whose event lies behind its kernel: a call on another stream waits for it on the
-    // device, since both kernels write the same columns
-    hipStream_t last_stream = nullptr;
-    int last_slot = -1;
+    // a call's view rows, then its bucket rows, uploaded through the ring (lc3_host_ring.h); ordered: on another stream than the previous
+    // call's, a call waits for it on the device, since both kernels write the same columns
+    lc3_host_ring ring;
 };
 
 extern "C" {
 int lc3ana_destroy(lc3gpu_analyzer *p) {
     if (!p) return LC3GPU_EINVAL;
-    OnDevice on(p->device);
-    for (int k = 0; k < kRingSlots; k++)
-        if (p->done[k]) {
-            if (p->recorded[k]) (void)hipEventSynchronize(p->done[k]);
-            (void)hipEventDestroy(p->done[k]);
-        }
+    OnDevice on(p->ring.device);
+    lc3_ring_destroy(p->ring);
     if (p->d_columns) (void)hipFree(p->d_columns);
-    if (p->d_ring) (void)hipFree(p->d_ring);
-    if (p->h_ring) (void)hipHostFree(p->h_ring);
     delete p;
     return LC3GPU_OK;
 }
@@ -235,12 +198,8 @@ int lc3ana_create(lc3gpu_analyzer **out, int n_streams, const lc3gpu_stream_desc
     p->max_views = max_views;
     p->max_frames = max_frames;
     const size_t max_buckets = (size_t)(max_views < LC3_IV_CONFIGS * LC3_IV_MAX_NBYTES ? max_views : LC3_IV_CONFIGS * LC3_IV_MAX_NBYTES);
-    p->slot_bytes = (size_t)max_views * sizeof(lc3_iv_row) + max_buckets * sizeof(lc3_iv_bucket);
-    hipError_t e = hipGetDevice(&p->device);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&p->h_ring, p->slot_bytes * kRingSlots, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_ring, p->slot_bytes * kRingSlots);
+    hipError_t e = lc3_ring_create(p->ring, (size_t)max_views * sizeof(lc3_iv_row) + max_buckets * sizeof(lc3_iv_bucket));
     if (e == hipSuccess) e = hipMalloc((void **)&p->d_columns, (size_t)max_frames * LC3_PLANE_WORDS * sizeof(int32_t));
-    for (int k = 0; k < kRingSlots && e == hipSuccess; k++) e = hipEventCreateWithFlags(&p->done[k], hipEventDisableTiming);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         (void)lc3ana_destroy(p);
@@ -275,30 +234,23 @@ int lc3ana_mixed_views(lc3gpu_analyzer *p, const lc3gpu_view *views, int n_views
     const int rc = lc3_aviews_check(p->streams.data(), (int)p->streams.size(), p->max_views, p->max_frames, v, n_views, B, &frames, &max_nbytes);
     if (rc) return rc;
     if (n_views == 0) return LC3GPU_OK;
-    OnDevice on(p->device);
+    OnDevice on(p->ring.device);
     const hipStream_t stream = (hipStream_t)hip_stream;
-    const int k = p->next;
-    if (p->recorded[k]) ANA_TRY(hipEventSynchronize(p->done[k]));  // (returns at once unless kRingSlots calls are still in flight)
-    // the columns are this analyzer's, not the call's: on another stream than the previous call's, behind that call's kernel
-    if (p->last_slot >= 0 && p->last_stream != stream) ANA_TRY(hipStreamWaitEvent(stream, p->done[p->last_slot], 0));
-    lc3_iv_row *rows = (lc3_iv_row *)(p->h_ring + (size_t)k * p->slot_bytes);
+    uint8_t *h_slot, *d_slot;
+    LC3_HIP_TRY(lc3_ring_acquire(p->ring, stream, true, h_slot, d_slot));
+    lc3_iv_row *rows = (lc3_iv_row *)h_slot;
     const size_t rows_bytes = (size_t)n_views * sizeof(lc3_iv_row);
-    lc3_iv_bucket *buckets = (lc3_iv_bucket *)(p->h_ring + (size_t)k * p->slot_bytes + rows_bytes);  // (at most one bucket per view)
+    lc3_iv_bucket *buckets = (lc3_iv_bucket *)(h_slot + rows_bytes);  // (at most one bucket per view)
     const unsigned fpb = lc3_av_fpb(max_nbytes);
     const size_t lds = lc3_av_lds_bytes(max_nbytes);
     lc3_iviews_build(p->streams.data(), v, n_views, (int)fpb, rows, buckets, p->plan);
     // one upload: the rows and, right behind them, the bucket rows
     const size_t buckets_bytes = (size_t)p->plan.n_buckets * sizeof(lc3_iv_bucket);
-    uint8_t *d_slot = p->d_ring + (size_t)k * p->slot_bytes;
-    ANA_TRY(hipMemcpyAsync(d_slot, rows, rows_bytes + buckets_bytes, hipMemcpyHostToDevice, stream));
+    LC3_HIP_TRY(hipMemcpyAsync(d_slot, rows, rows_bytes + buckets_bytes, hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(lc3_analyze_views_kernel, dim3((unsigned)p->plan.n_wg), dim3(fpb), lds, stream, (const lc3_iv_row *)d_slot,
                        (const lc3_iv_bucket *)(d_slot + rows_bytes), p->plan.n_buckets, d_in, d_bad_frame, p->d_columns, d_energy, d_bands, d_spec);
-    ANA_TRY(hipGetLastError());
-    ANA_TRY(hipEventRecord(p->done[k], stream));
-    p->recorded[k] = true;
-    p->last_stream = stream;
-    p->last_slot = k;
-    p->next = (k + 1) % kRingSlots;
+    LC3_HIP_TRY(hipGetLastError());
+    LC3_HIP_TRY(lc3_ring_commit(p->ring, stream));
     return LC3GPU_OK;
 }
 
@@ -308,7 +260,7 @@ int lc3ana_plan_info(int max_nbytes, int *fpb, size_t *lds_bytes, int *ring_slot
     if (max_nbytes < 1 || max_nbytes > LC3_IV_MAX_NBYTES) return LC3GPU_ELENGTH;
     if (fpb) *fpb = (int)lc3_av_fpb(max_nbytes);
     if (lds_bytes) *lds_bytes = lc3_av_lds_bytes(max_nbytes);
-    if (ring_slots) *ring_slots = kRingSlots;
+    if (ring_slots) *ring_slots = lc3_host_ring::slots;
     if (column_words) *column_words = LC3_PLANE_WORDS;
     return LC3GPU_OK;
 }

@@ -110,55 +110,21 @@ __global__ __launch_bounds__(256) void lc3_inspect_views_kernel(const lc3_iv_row
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------
-namespace {
-#define INSP_TRY(expr)                     \
-    do {                                   \
-        if ((expr) != hipSuccess) {        \
-            (void)hipGetLastError();       \
-            return LC3GPU_EHIP;            \
-        }                                  \
-    } while (0)
-
-// calls in flight before a call waits for the oldest of its own uploads
-constexpr int kRingSlots = 8;
-
-// makes the inspector's device current for the scope of a call
-struct OnDevice {
-    int prev = -1, dev;
-    bool switched = false;
-    explicit OnDevice(int d) : dev(d) {
-        if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = hipSetDevice(dev) == hipSuccess;
-    }
-    ~OnDevice() {
-        if (switched) (void)hipSetDevice(prev);
-    }
-};
-}  // namespace
+#include "lc3_host_ring.h"
 
 struct lc3gpu_inspector {
-    int device = 0, max_views = 0;
+    int max_views = 0;
     std::vector<lc3_iv_stream> streams;
     lc3_iv_plan plan;
-    // the ring: slot k is slot_bytes of pinned host memory and as many of device memory (a call's view rows, then its bucket rows), and an
-    // event behind the kernel that read it last
-    size_t slot_bytes = 0;
-    uint8_t *h_ring = nullptr, *d_ring = nullptr;
-    hipEvent_t done[kRingSlots] = {};
-    bool recorded[kRingSlots] = {};
-    int next = 0;
+    // a call's view rows, then its bucket rows, uploaded through the ring (lc3_host_ring.h); not ordered: the inspector keeps nothing on
+    // the device between calls
+    lc3_host_ring ring;
 };
 
 extern "C" {
 int lc3insp_destroy(lc3gpu_inspector *p) {
     if (!p) return LC3GPU_EINVAL;
-    OnDevice on(p->device);
-    for (int k = 0; k < kRingSlots; k++)
-        if (p->done[k]) {
-            if (p->recorded[k]) (void)hipEventSynchronize(p->done[k]);
-            (void)hipEventDestroy(p->done[k]);
-        }
-    if (p->d_ring) (void)hipFree(p->d_ring);
-    if (p->h_ring) (void)hipHostFree(p->h_ring);
+    lc3_ring_destroy(p->ring);
     delete p;
     return LC3GPU_OK;
 }
@@ -183,12 +149,7 @@ int lc3insp_create(lc3gpu_inspector **out, int n_streams, const lc3gpu_stream_de
     p->streams.swap(streams);
     p->max_views = max_views;
     const size_t max_buckets = (size_t)(max_views < LC3_IV_CONFIGS * LC3_IV_MAX_NBYTES ? max_views : LC3_IV_CONFIGS * LC3_IV_MAX_NBYTES);
-    p->slot_bytes = (size_t)max_views * sizeof(lc3_iv_row) + max_buckets * sizeof(lc3_iv_bucket);
-    hipError_t e = hipGetDevice(&p->device);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&p->h_ring, p->slot_bytes * kRingSlots, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_ring, p->slot_bytes * kRingSlots);
-    for (int k = 0; k < kRingSlots && e == hipSuccess; k++) e = hipEventCreateWithFlags(&p->done[k], hipEventDisableTiming);
-    if (e != hipSuccess) {
+    if (lc3_ring_create(p->ring, (size_t)max_views * sizeof(lc3_iv_row) + max_buckets * sizeof(lc3_iv_bucket)) != hipSuccess) {
         (void)hipGetLastError();
         (void)lc3insp_destroy(p);
         return LC3GPU_EHIP;
@@ -219,26 +180,23 @@ int lc3insp_mixed_views(lc3gpu_inspector *p, const lc3gpu_view *views, int n_vie
     const int rc = lc3_iviews_check(p->streams.data(), (int)p->streams.size(), p->max_views, v, n_views, B, &frames, &max_nbytes);
     if (rc) return rc;
     if (n_views == 0) return LC3GPU_OK;
-    OnDevice on(p->device);
+    OnDevice on(p->ring.device);
     const hipStream_t stream = (hipStream_t)hip_stream;
-    const int k = p->next;
-    if (p->recorded[k]) INSP_TRY(hipEventSynchronize(p->done[k]));  // (returns at once unless kRingSlots calls are still in flight)
-    lc3_iv_row *rows = (lc3_iv_row *)(p->h_ring + (size_t)k * p->slot_bytes);
+    uint8_t *h_slot, *d_slot;
+    LC3_HIP_TRY(lc3_ring_acquire(p->ring, stream, false, h_slot, d_slot));
+    lc3_iv_row *rows = (lc3_iv_row *)h_slot;
     const size_t rows_bytes = (size_t)n_views * sizeof(lc3_iv_row);
-    lc3_iv_bucket *buckets = (lc3_iv_bucket *)(p->h_ring + (size_t)k * p->slot_bytes + rows_bytes);  // (at most one bucket per view)
+    lc3_iv_bucket *buckets = (lc3_iv_bucket *)(h_slot + rows_bytes);  // (at most one bucket per view)
     const unsigned fpb = lc3_iv_fpb(max_nbytes);
     const size_t lds = lc3_iv_lds_bytes(max_nbytes);
     lc3_iviews_build(p->streams.data(), v, n_views, (int)fpb, rows, buckets, p->plan);
     // one upload: the rows and, right behind them, the bucket rows
     const size_t buckets_bytes = (size_t)p->plan.n_buckets * sizeof(lc3_iv_bucket);
-    uint8_t *d_slot = p->d_ring + (size_t)k * p->slot_bytes;
-    INSP_TRY(hipMemcpyAsync(d_slot, rows, rows_bytes + buckets_bytes, hipMemcpyHostToDevice, stream));
+    LC3_HIP_TRY(hipMemcpyAsync(d_slot, rows, rows_bytes + buckets_bytes, hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(lc3_inspect_views_kernel, dim3((unsigned)p->plan.n_wg), dim3(fpb), lds, stream, (const lc3_iv_row *)d_slot,
                        (const lc3_iv_bucket *)(d_slot + rows_bytes), p->plan.n_buckets, d_in, d_bad_frame, d_status, (int32_t *)d_info);
-    INSP_TRY(hipGetLastError());
-    INSP_TRY(hipEventRecord(p->done[k], stream));
-    p->recorded[k] = true;
-    p->next = (k + 1) % kRingSlots;
+    LC3_HIP_TRY(hipGetLastError());
+    LC3_HIP_TRY(lc3_ring_commit(p->ring, stream));
     return LC3GPU_OK;
 }
 
@@ -247,7 +205,7 @@ int lc3insp_plan_info(int max_nbytes, int *fpb, size_t *lds_bytes, int *ring_slo
     if (max_nbytes < 1 || max_nbytes > LC3_IV_MAX_NBYTES) return LC3GPU_ELENGTH;
     if (fpb) *fpb = (int)lc3_iv_fpb(max_nbytes);
     if (lds_bytes) *lds_bytes = lc3_iv_lds_bytes(max_nbytes);
-    if (ring_slots) *ring_slots = kRingSlots;
+    if (ring_slots) *ring_slots = lc3_host_ring::slots;
     return LC3GPU_OK;
 }
 }

@@ -42,56 +42,22 @@ __global__ __launch_bounds__(LC3_MX_LANES) void lc3_mix_views_kernel(const lc3_m
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------
-namespace {
-#define MIX_TRY(expr)                      \
-    do {                                   \
-        if ((expr) != hipSuccess) {        \
-            (void)hipGetLastError();       \
-            return LC3GPU_EHIP;            \
-        }                                  \
-    } while (0)
-
-// calls in flight before a call waits for the oldest of its own uploads
-constexpr int kRingSlots = 8;
-
-// makes the mixer's device current for the scope of a call
-struct OnDevice {
-    int prev = -1, dev;
-    bool switched = false;
-    explicit OnDevice(int d) : dev(d) {
-        if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = hipSetDevice(dev) == hipSuccess;
-    }
-    ~OnDevice() {
-        if (switched) (void)hipSetDevice(prev);
-    }
-};
-}  // namespace
+#include "lc3_host_ring.h"
 
 struct lc3gpu_mixer {
-    int device = 0, max_views = 0;
+    int max_views = 0;
     std::vector<lc3_mx_stream> streams;
     lc3_mx_plan plan;
-    // the ring: slot k is slot_bytes of pinned host memory and as many of device memory (a call's input rows, its output rows, then its bus
-    // rows: at most max_views rows and max_views buses), and an event behind the kernel that read it last
-    size_t slot_bytes = 0;
-    uint8_t *h_ring = nullptr, *d_ring = nullptr;
-    hipEvent_t done[kRingSlots] = {};
-    bool recorded[kRingSlots] = {};
-    int next = 0;
+    // a call's input rows, its output rows, then its bus rows (at most max_views rows and max_views buses), uploaded through the ring
+    // (lc3_host_ring.h); not ordered: the mixer keeps nothing on the device between calls
+    lc3_host_ring ring;
     explicit lc3gpu_mixer(int mv) : max_views(mv), plan(mv) {}
 };
 
 extern "C" {
 int lc3mix_destroy(lc3gpu_mixer *p) {
     if (!p) return LC3GPU_EINVAL;
-    OnDevice on(p->device);
-    for (int k = 0; k < kRingSlots; k++)
-        if (p->done[k]) {
-            if (p->recorded[k]) (void)hipEventSynchronize(p->done[k]);
-            (void)hipEventDestroy(p->done[k]);
-        }
-    if (p->d_ring) (void)hipFree(p->d_ring);
-    if (p->h_ring) (void)hipHostFree(p->h_ring);
+    lc3_ring_destroy(p->ring);
     delete p;
     return LC3GPU_OK;
 }
@@ -115,12 +81,7 @@ int lc3mix_create(lc3gpu_mixer **out, int n_streams, const lc3gpu_stream_desc *d
     lc3gpu_mixer *p = new (std::nothrow) lc3gpu_mixer(max_views);
     if (!p) return LC3GPU_EHIP;
     p->streams.swap(streams);
-    p->slot_bytes = (size_t)max_views * (sizeof(lc3_mx_row) + sizeof(lc3_mx_bus));
-    hipError_t e = hipGetDevice(&p->device);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&p->h_ring, p->slot_bytes * kRingSlots, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_ring, p->slot_bytes * kRingSlots);
-    for (int k = 0; k < kRingSlots && e == hipSuccess; k++) e = hipEventCreateWithFlags(&p->done[k], hipEventDisableTiming);
-    if (e != hipSuccess) {
+    if (lc3_ring_create(p->ring, (size_t)max_views * (sizeof(lc3_mx_row) + sizeof(lc3_mx_bus))) != hipSuccess) {
         (void)hipGetLastError();
         (void)lc3mix_destroy(p);
         return LC3GPU_EHIP;
@@ -147,28 +108,25 @@ int lc3mix_mixed_views(lc3gpu_mixer *p, const lc3gpu_view *in_views, const lc3gp
         p->plan.clear();
         return LC3GPU_OK;
     }
-    OnDevice on(p->device);
+    OnDevice on(p->ring.device);
     const hipStream_t stream = (hipStream_t)hip_stream;
-    const int k = p->next;
-    if (p->recorded[k] && hipEventSynchronize(p->done[k]) != hipSuccess) {  // (returns at once unless kRingSlots calls are still in flight)
+    uint8_t *h_slot, *d_slot;
+    if (lc3_ring_acquire(p->ring, stream, false, h_slot, d_slot) != hipSuccess) {
         (void)hipGetLastError();
         p->plan.clear();  // (the check's counts: the plan that would have consumed them is not built)
         return LC3GPU_EHIP;
     }
-    uint8_t *h_slot = p->h_ring + (size_t)k * p->slot_bytes, *d_slot = p->d_ring + (size_t)k * p->slot_bytes;
     const size_t in_bytes = (size_t)n_in * sizeof(lc3_mx_row), out_bytes = (size_t)n_out * sizeof(lc3_mx_row);
     lc3_mviews_build(p->streams.data(), vi, ti, n_in, vo, to, n_out, (lc3_mx_row *)h_slot, (lc3_mx_row *)(h_slot + in_bytes),
                      (lc3_mx_bus *)(h_slot + in_bytes + out_bytes), p->plan);
     // one upload: the input rows, the output rows and, right behind them, the bus rows
     const size_t bus_bytes = (size_t)p->plan.n_buses * sizeof(lc3_mx_bus);
-    MIX_TRY(hipMemcpyAsync(d_slot, h_slot, in_bytes + out_bytes + bus_bytes, hipMemcpyHostToDevice, stream));
+    LC3_HIP_TRY(hipMemcpyAsync(d_slot, h_slot, in_bytes + out_bytes + bus_bytes, hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(lc3_mix_views_kernel, dim3((unsigned)p->plan.n_wg), dim3(LC3_MX_LANES), 0, stream, (const lc3_mx_row *)d_slot,
                        (const lc3_mx_row *)(d_slot + in_bytes), (const lc3_mx_bus *)(d_slot + in_bytes + out_bytes), p->plan.n_buses, d_pcm_in,
                        d_pcm_out);
-    MIX_TRY(hipGetLastError());
-    MIX_TRY(hipEventRecord(p->done[k], stream));
-    p->recorded[k] = true;
-    p->next = (k + 1) % kRingSlots;
+    LC3_HIP_TRY(hipGetLastError());
+    LC3_HIP_TRY(lc3_ring_commit(p->ring, stream));
     return LC3GPU_OK;
 }
 
@@ -176,7 +134,7 @@ int lc3mix_mixed_views(lc3gpu_mixer *p, const lc3gpu_view *in_views, const lc3gp
 int lc3mix_plan_info(int *samples_per_wg, int *lanes, int *ring_slots) {
     if (samples_per_wg) *samples_per_wg = LC3_MX_SPW;
     if (lanes) *lanes = LC3_MX_LANES;
-    if (ring_slots) *ring_slots = kRingSlots;
+    if (ring_slots) *ring_slots = lc3_host_ring::slots;
     return LC3GPU_OK;
 }
 }

@@ -49,60 +49,23 @@ __global__ __launch_bounds__(LC3_RS_LANES) void lc3_rate_views_kernel(const lc3_
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------
-namespace {
-#define RS_TRY(expr)                       \
-    do {                                   \
-        if ((expr) != hipSuccess) {        \
-            (void)hipGetLastError();       \
-            return LC3GPU_EHIP;            \
-        }                                  \
-    } while (0)
-
-// calls in flight before a call waits for the oldest of its own uploads
-constexpr int kRingSlots = 8;
-
-// makes the resampler's device current for the scope of a call
-struct OnDevice {
-    int prev = -1, dev;
-    bool switched = false;
-    explicit OnDevice(int d) : dev(d) {
-        if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = hipSetDevice(dev) == hipSuccess;
-    }
-    ~OnDevice() {
-        if (switched) (void)hipSetDevice(prev);
-    }
-};
-}  // namespace
+#include "lc3_host_ring.h"
 
 struct lc3gpu_resampler {
-    int device = 0, max_views = 0;
+    int max_views = 0;
     lc3_rs_state state;
     int16_t *d_hist = nullptr;  // [n_channels][2][LC3_RS_HIST]
-    // the ring: slot k is slot_bytes of pinned host memory and as many of device memory (a call's rows: at most max_views), and an event
-    // behind the kernel that read it last
-    size_t slot_bytes = 0;
-    uint8_t *h_ring = nullptr, *d_ring = nullptr;
-    hipEvent_t done[kRingSlots] = {};
-    bool recorded[kRingSlots] = {};
-    int next = 0;
-    // the stream of the previous call and the ring slot whose event lies behind its kernel: a call on another stream waits for it on the
-    // device, since both kernels read and write the same histories
-    hipStream_t last_stream = nullptr;
-    int last_slot = -1;
+    // a call's rows (at most max_views), uploaded through the ring (lc3_host_ring.h); ordered: on another stream than the previous call's,
+    // a call waits for it on the device, since both kernels read and write the same histories
+    lc3_host_ring ring;
 };
 
 extern "C" {
 int lc3rs_destroy(lc3gpu_resampler *p) {
     if (!p) return LC3GPU_EINVAL;
-    OnDevice on(p->device);
-    for (int k = 0; k < kRingSlots; k++)
-        if (p->done[k]) {
-            if (p->recorded[k]) (void)hipEventSynchronize(p->done[k]);
-            (void)hipEventDestroy(p->done[k]);
-        }
+    OnDevice on(p->ring.device);
+    lc3_ring_destroy(p->ring);
     if (p->d_hist) (void)hipFree(p->d_hist);
-    if (p->d_ring) (void)hipFree(p->d_ring);
-    if (p->h_ring) (void)hipHostFree(p->h_ring);
     delete p;
     return LC3GPU_OK;
 }
@@ -126,14 +89,10 @@ int lc3rs_create(lc3gpu_resampler **out, int n_channels, const lc3gpu_rate_desc 
     if (!p) return LC3GPU_EHIP;
     p->max_views = max_views;
     p->state.channels.swap(channels);
-    p->slot_bytes = (size_t)max_views * sizeof(lc3_rs_row);
     const size_t hist_bytes = (size_t)n_channels * 2 * LC3_RS_HIST * sizeof(int16_t);
-    hipError_t e = hipGetDevice(&p->device);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&p->h_ring, p->slot_bytes * kRingSlots, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_ring, p->slot_bytes * kRingSlots);
+    hipError_t e = lc3_ring_create(p->ring, (size_t)max_views * sizeof(lc3_rs_row));
     if (e == hipSuccess) e = hipMalloc((void **)&p->d_hist, hist_bytes);
     if (e == hipSuccess) e = hipMemset(p->d_hist, 0, hist_bytes);  // (never read before it is written: every channel starts fresh)
-    for (int k = 0; k < kRingSlots && e == hipSuccess; k++) e = hipEventCreateWithFlags(&p->done[k], hipEventDisableTiming);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         (void)lc3rs_destroy(p);
@@ -171,14 +130,11 @@ int lc3rs_mixed_views(lc3gpu_resampler *p, const lc3gpu_view *in_views, const in
     const int rc = lc3_rviews_check(p->state, p->max_views, vi, vo, n_views, B);
     if (rc) return rc;
     if (n_views == 0) return LC3GPU_OK;
-    OnDevice on(p->device);
+    OnDevice on(p->ring.device);
     const hipStream_t stream = (hipStream_t)hip_stream;
-    const int k = p->next;
-    if (p->recorded[k]) RS_TRY(hipEventSynchronize(p->done[k]));  // (returns at once unless kRingSlots calls are still in flight)
-    // the histories are this resampler's, not the call's: on another stream than the previous call's, behind that call's kernel
-    if (p->last_slot >= 0 && p->last_stream != stream) RS_TRY(hipStreamWaitEvent(stream, p->done[p->last_slot], 0));
-    lc3_rs_row *rows = (lc3_rs_row *)(p->h_ring + (size_t)k * p->slot_bytes);
-    uint8_t *d_slot = p->d_ring + (size_t)k * p->slot_bytes;
+    uint8_t *h_slot, *d_slot;
+    LC3_HIP_TRY(lc3_ring_acquire(p->ring, stream, true, h_slot, d_slot));
+    lc3_rs_row *rows = (lc3_rs_row *)h_slot;
     lc3_rviews_build(p->state, vi, vo, n_views, rows);
     hipError_t e = hipMemcpyAsync(d_slot, rows, (size_t)n_views * sizeof(lc3_rs_row), hipMemcpyHostToDevice, stream);
     if (e == hipSuccess) {
@@ -191,11 +147,7 @@ int lc3rs_mixed_views(lc3gpu_resampler *p, const lc3gpu_view *in_views, const in
         lc3_rviews_unbuild(p->state, vi, n_views, rows);
         return LC3GPU_EHIP;
     }
-    RS_TRY(hipEventRecord(p->done[k], stream));
-    p->recorded[k] = true;
-    p->last_stream = stream;
-    p->last_slot = k;
-    p->next = (k + 1) % kRingSlots;
+    LC3_HIP_TRY(lc3_ring_commit(p->ring, stream));
     return LC3GPU_OK;
 }
 
@@ -203,7 +155,7 @@ int lc3rs_mixed_views(lc3gpu_resampler *p, const lc3gpu_view *in_views, const in
 int lc3rs_plan_info(int *samples_per_wg, int *lanes, int *ring_slots, int *hist_samples) {
     if (samples_per_wg) *samples_per_wg = LC3_RS_CHUNK;
     if (lanes) *lanes = LC3_RS_LANES;
-    if (ring_slots) *ring_slots = kRingSlots;
+    if (ring_slots) *ring_slots = lc3_host_ring::slots;
     if (hist_samples) *hist_samples = LC3_RS_HIST;
     return LC3GPU_OK;
 }

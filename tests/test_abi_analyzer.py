@@ -82,6 +82,14 @@ def test_the_second_companion_library_is_built_and_the_main_library_links_it():
     assert hip.count("__syncthreads()") == 1 and hip.count("__global__") == 1
     assert '#include "lc3_host_inspect_views.h"' in _read("lc3-codec_amd", "csrc", "lc3_host_analyze_views.h")
     assert '#include "../../lc3-codec_amd/csrc/lc3_host_analyze_views.h"' in _read("tests", "emu", "lc3_emu_analyze_views.cpp")
+    # the analyzer's own sources are no part of what the other units are stamped with
+    own = set(api.companion_own("analyzer"))
+    assert own == {"lc3gpu_analyzer.hip", "lc3_host_analyze_views.h", "lc3_dev_dec_analyze.h"}
+    names = lambda paths: {os.path.basename(p) for p in paths}
+    assert own <= names(api.companion_sources("analyzer"))
+    for other in api._COMPANIONS:
+        assert other == "analyzer" or not own & names(api.companion_sources(other)), other
+    assert not own & names(api.main_sources())
     # the plan's figures, from the companion itself
     assert api.analyzer_plan_info(40) == (256, 10672 + 256 * (72 + 40) + 8, 8, 648)
     assert api.analyzer_plan_info(400)[:2] == (64, 10672 + 64 * (72 + 400) + 8)

@@ -75,6 +75,17 @@ def test_the_companion_library_is_built_and_the_main_library_links_it():
     hip = _read("lc3-codec_amd", "csrc", "lc3gpu_inspector.hip")
     assert '#include "lc3_dev_dec_inspect.h"' in hip and '#include "lc3_host_inspect_views.h"' in hip and "lc3_inspect_record(" in hip
     assert '#include "../../lc3-codec_amd/csrc/lc3_host_inspect_views.h"' in _read("tests", "emu", "lc3_emu_inspect_views.cpp")
+    # the inspector's own unit is no part of what the other units are stamped with; the check and plan, and the upload ring, are shared by
+    # the companions and hidden from the main units
+    own = set(api.companion_own("inspector"))
+    assert own == {"lc3gpu_inspector.hip"} and set(api._COMPANION_SHARED) == {"lc3_host_inspect_views.h", "lc3_host_ring.h"}
+    names = lambda paths: {os.path.basename(p) for p in paths}
+    assert own <= names(api.companion_sources("inspector"))
+    for other in api._COMPANIONS:
+        assert other == "inspector" or not own & names(api.companion_sources(other)), other
+        assert set(api._COMPANION_SHARED) <= names(api.companion_sources(other)), other
+    assert not (own | set(api._COMPANION_SHARED)) & names(api.main_sources())
+    assert {"lc3gpu.hip", "lc3_dev_common.h", "lc3gpu.h", "lc3_tables.h"} <= names(api.main_sources())
 
 
 def test_the_header_states_the_refusal_table_and_the_two_equivalences():

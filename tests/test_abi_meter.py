@@ -113,7 +113,7 @@ def test_the_fifth_companion_library_is_built_and_the_main_library_links_it():
     assert "__global__" not in _read("lc3-codec_amd", "csrc", "lc3gpu_meter_api.cpp")
     csrc = os.path.join(ROOT, "lc3-codec_amd", "csrc")
     for other in sorted(os.listdir(csrc)):  # the companion's sources are seen by its own unit only
-        if other in api._METER_ONLY or other == "lc3gpu_meter_api.cpp" or not other.endswith((".h", ".hip", ".cpp")):
+        if other in api.companion_own("meter") or other == "lc3gpu_meter_api.cpp" or not other.endswith((".h", ".hip", ".cpp")):
             continue
         src = _read("lc3-codec_amd", "csrc", other)
         assert "measure_mixed_views" not in src and "lc3mtr_" not in src and "lc3_dev_level" not in src and "lc3_host_measure_views" not in src, other
@@ -129,9 +129,15 @@ def test_the_fifth_companion_library_is_built_and_the_main_library_links_it():
     for user in ("lc3_emu_meter_views.cpp", "lc3_meter_views_check_main.cpp"):
         assert '#include "../../lc3-codec_amd/csrc/lc3_dev_level.h"' in _read("tests", "emu", user), user
     # the meter's own sources are no part of what the other units are stamped with
-    assert set(api._METER_ONLY) == {"lc3gpu_meter.hip", "lc3_host_measure_views.h", "lc3_dev_level.h"}
-    build = _read("lc3-codec_amd", "api.py")
-    assert build.count("+ _METER_ONLY") == 5  # hidden from the main units and from the four other companions
+    own = set(api.companion_own("meter"))
+    assert own == {"lc3gpu_meter.hip", "lc3_host_measure_views.h", "lc3_dev_level.h"}
+    names = lambda paths: {os.path.basename(p) for p in paths}
+    assert own <= names(api.companion_sources("meter"))
+    others = [c for c in api._COMPANIONS if c != "meter"]
+    assert sorted(others) == ["analyzer", "inspector", "mixer", "resampler"]
+    for other in others:  # hidden from the four other companions and from the main units
+        assert not own & names(api.companion_sources(other)), other
+    assert not own & names(api.main_sources())
     # the plan's figures, from the companion itself
     assert api.meter_plan_info() == (4, 256, 8, 16)
 

@@ -88,7 +88,13 @@ def test_the_third_companion_library_is_built_and_the_main_library_links_it():
     for user in ("lc3_emu_mix_views.cpp", "lc3_mix_views_check_main.cpp"):
         assert '#include "../../lc3-codec_amd/csrc/lc3_dev_mix.h"' in _read("tests", "emu", user), user
     # the mixer's own sources are no part of what the other units are stamped with
-    assert set(api._MIXER_ONLY) == {"lc3gpu_mixer.hip", "lc3_host_mix_views.h", "lc3_dev_mix.h"}
+    own = set(api.companion_own("mixer"))
+    assert own == {"lc3gpu_mixer.hip", "lc3_host_mix_views.h", "lc3_dev_mix.h"}
+    names = lambda paths: {os.path.basename(p) for p in paths}
+    assert own <= names(api.companion_sources("mixer"))
+    for other in api._COMPANIONS:
+        assert other == "mixer" or not own & names(api.companion_sources(other)), other
+    assert not own & names(api.main_sources())
     # the plan's figures, from the companion itself
     assert api.mixer_plan_info() == (512, 256, 8)
 

@@ -92,7 +92,13 @@ def test_the_fourth_companion_library_is_built_and_the_main_library_links_it():
     for user in ("lc3_emu_resample_views.cpp", "lc3_resample_views_check_main.cpp"):
         assert '#include "../../lc3-codec_amd/csrc/lc3_dev_resample.h"' in _read("tests", "emu", user), user
     # the resampler's own sources are no part of what the other units are stamped with
-    assert set(api._RESAMPLER_ONLY) == {"lc3gpu_resampler.hip", "lc3_host_resample_views.h", "lc3_dev_resample.h", "lc3_resample_tables.h"}
+    own = set(api.companion_own("resampler"))
+    assert own == {"lc3gpu_resampler.hip", "lc3_host_resample_views.h", "lc3_dev_resample.h", "lc3_resample_tables.h"}
+    names = lambda paths: {os.path.basename(p) for p in paths}
+    assert own <= names(api.companion_sources("resampler"))
+    for other in api._COMPANIONS:
+        assert other == "resampler" or not own & names(api.companion_sources(other)), other
+    assert not own & names(api.main_sources())
     # the plan's figures, from the companion itself
     assert api.resampler_plan_info() == (768, 256, 8, 96)
 
