@@ -222,8 +222,9 @@ void *lc3o_encoder_new_spec(int fs_hz, int frame_us, int spec_flags) {
     if (e && lc3o_encoder_init_spec(e, fs_hz, frame_us, spec_flags)) { free(e); return 0; }
     return e;
 }
-/* dbg float[1600]: MDCT [0,nf), after SNS [480,..), after TNS [960,..); scalars at 1440: +0 bandwidth index, +1 attack flag,
- * +6 / +7 TNS orders, +21 near-Nyquist flag; band energies at 1472.  scf[16]: the unquantised scale factors; rc_q[16] */
+/* dbg float[1600]: MDCT [0,nf), after SNS [480,..), after TNS [960,..); scalars at 1440, +0 .. +24 as LC3GPU_ENC_DBG_SCALARS lays them
+ * out (include/lc3gpu.h); band energies at 1472; the attack detector's five state values at 1536.  scf[16]: the unquantised scale
+ * factors; rc_q[16] */
 void lc3o_kat_encode_stages(void *enc, const int16_t *x_s, uint8_t *out, int nbytes, float *dbg, float *scf, float *rc_q) {
     lc3o_encoder *e = (lc3o_encoder *)enc;
     const lc3o_config *c = &e->cfg;
@@ -253,6 +254,22 @@ void lc3o_kat_encode_stages(void *enc, const int16_t *x_s, uint8_t *out, int nby
     n_res = lc3o_enc_residual(spec.nbits_spec, spec.nbits_trunc, c->ne, spec.gg, e->mdct_out, e->x_q, e->res_bits);
     noise_factor = lc3o_enc_noise_factor(c, e->mdct_out, e->x_q, bw.bandwidth_ind, spec.gg);
     lc3o_enc_bitstream(c, bw, &sns, &tns, pf, &spec, e->res_bits, n_res, noise_factor, e->x_q, out, nbytes);
+    dbg[1442] = (float)sns.ind_lf; dbg[1443] = (float)sns.ind_hf; dbg[1444] = (float)sns.shape_j; dbg[1445] = (float)sns.gind;
+    dbg[1448] = (float)tns.nbits_tns;
+    dbg[1449] = (float)pf.pitch_index; dbg[1450] = (float)pf.pitch_present; dbg[1451] = (float)pf.ltpf_active;
+    dbg[1452] = (float)spec.gg_ind; dbg[1453] = (float)spec.lastnz_trunc; dbg[1454] = (float)spec.nbits_lsb;
+    dbg[1455] = (float)spec.lsb_mode; dbg[1456] = (float)n_res; dbg[1457] = (float)noise_factor; dbg[1458] = spec.gg;
+    dbg[1459] = (float)spec.nbits_spec; dbg[1460] = (float)spec.nbits_trunc;
+    dbg[1462] = (float)sns.ls_inda; dbg[1463] = (float)(sns.index_joint_j & 0xffffu); dbg[1464] = (float)(sns.index_joint_j >> 16);
+    /* the attack detector's state after the frame (attack_detector.rs:17-21) */
+    dbg[1536] = e->att.energy_last; dbg[1537] = e->att.max_energy_last; dbg[1538] = (float)e->att.attack_pos_last;
+    dbg[1539] = (float)e->att.ds_tm1; dbg[1540] = (float)e->att.ds_tm2;
+}
+/* the LTPF analysis' 12.8 kHz signal after the frame (resampled, high-passed; 128 + 44 + 232 floats as the reference lays them out,
+ * encoder/long_term_post_filter.rs:114,152): the one value of that stage that none of its decisions shows, its scale */
+void lc3o_kat_ltpf_x12(void *enc, float *out) {
+    lc3o_encoder *e = (lc3o_encoder *)enc;
+    memcpy(out, e->ltpf.x12, sizeof(e->ltpf.x12));
 }
 /* dbg float[2560] in the LC3GPU_DBG_* layout (INT 0, SPEC 400, IMDCT 800, LTPF 1280, GAIN 1760, TNS 2160); si[20] as
  * lc3o_kat_side_info, iad[22] as lc3o_kat_arith, res_bits[480].  Returns 1 when the frame was concealed (nothing but IMDCT / LTPF

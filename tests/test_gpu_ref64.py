@@ -2,7 +2,9 @@
 
 The same material and bounds as tests/test_ref64_oracle.py, on the device's own stage dumps: lc3gpu_encode_frame_debug (MDCT,
 band energies, SNS, TNS, decisions), lc3gpu_decode_frame_debug in all three reconstruction forms, lc3gpu_decoder_synth_debug (IMDCT
-and post-filter with chosen filter parameters), and one batch decode through the production kernels against a float64 decode."""
+and post-filter with chosen filter parameters), and one batch decode through the production kernels against a float64 decode.
+The encoder's decisions (attack, TNS and LTPF analysis, rate loop, residual bits, noise level) are held to their float64 models
+under the margins measured on the oracle (ref64_check.MARGIN), by default and with the sequential sums forced."""
 import importlib
 
 import numpy as np
@@ -56,6 +58,53 @@ def test_device_encoder_stages_against_float64(fs, us):
         assert rec.paths["attack"] > 0
     if fs <= 32000:
         assert rec.paths["near_nyquist"] > 0
+
+
+def device_decisions(fs, us):
+    """the encoder's decisions of the device over decision_jobs (one stream per handle) under the oracle's margins: the checker,
+    the path assertions and the cap of tests/test_ref64_oracle.py::test_oracle_decisions_against_float64"""
+    cfg = R.config(fs, us)
+    rec = C.Decisions()
+    parser = C.Parser(fs, us)
+    for x, nb in C.decision_jobs(cfg):
+        enc = pkg.Lc3Encoder(1, us, fs, spec_flags=_enc_flags(cfg))
+        chk = C.EncoderCheck(cfg, rec, parser)
+        for t in range(x.shape[0]):
+            out, dbg = enc.encode_frame_debug(x[t], nb)
+            chk.frame(x[t], dbg, out)
+    print(rec.table("device %d Hz %d us" % (fs, us)))
+    assert not rec.unexcused, rec.unexcused[:8]
+    assert not rec.failures(), rec.failures()
+    assert not rec.over_cap(cfg), rec.over_cap(cfg)
+    missing = [k for k in C.decision_paths(cfg) if not rec.paths[k] > 0]
+    assert not missing, (missing, dict(rec.paths))
+
+
+@pytest.mark.parametrize("fs,us", R.CONFIGS)
+def test_device_decisions_against_float64(fs, us):
+    device_decisions(fs, us)
+
+
+def test_device_decisions_with_sequential_sums():
+    """the gain bisection and the noise level are the decisions that the kernels take from a tree sum when it is safely off the
+    threshold (tests/test_gpu_parity.py::test_sequential_sum_path_of_guarded_decisions); with LC3GPU_SEQ_SUMS=1, read when a handle
+    is created, every one of them takes the sequential sum instead: the same check in a fresh process with it set"""
+    import os
+    import subprocess
+    import sys
+
+    code = (
+        "import sys; sys.path.insert(0, 'tests')\n"
+        "import test_gpu_ref64 as t\n"
+        "t.device_decisions(48000, 10000)\n"
+        "t.device_decisions(16000, 7500)\n"
+        "print('seq decisions ok')\n"
+    )
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, LC3GPU_SEQ_SUMS="1")
+    r = subprocess.run([sys.executable, "-c", code], cwd=root, env=env, capture_output=True, text=True, timeout=600)
+    print(r.stdout[-3000:])
+    assert r.returncode == 0 and "seq decisions ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
 
 
 @pytest.mark.parametrize("fs,us,flag", [(8000, 10000, R.SPEC_8KHZ_ENCODE), (24000, 10000, R.SPEC_TNS_SSWB_STOP),
