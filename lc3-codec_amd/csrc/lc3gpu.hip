@@ -3013,7 +3013,7 @@ struct HandleCommon {
         HIP_TRY(hipMemcpy(d_pc_timeouts, init, sizeof init, hipMemcpyHostToDevice));
         return LC3GPU_OK;
     }
-    bool pc_optin_done = false;            // the pair kernels' dynamic-LDS opt-in has been made for this handle's device (no lock per call)
+    unsigned lds_optins = 0;               // bit LdsOptin::id: that list's dynamic-LDS opt-in has been made for this handle's device (no lock per call)
     hipStream_t last_stream = nullptr;
     hipEvent_t done = nullptr;
     bool has_work = false;
@@ -3692,46 +3692,36 @@ static bool lc3_pack_pc_enabled() {
     }();
     return on;
 }
-static int lc3_pack_pc_optin() {
-    static bool done[LC3_MAX_DEVICES] = {};
-    static std::mutex mu;
+// An opt-in list: kernels launched with more than the default 64 KB of dynamic LDS and the size they are allowed
+// (hipFuncAttributeMaxDynamicSharedMemorySize).  lc3_lds_optin takes a list once per device, under the one process-wide lock, and notes it
+// in the handle (HandleCommon::lds_optins), so that no call takes the lock after a handle's first.  A handle stays on one device
+struct LdsOptin {
+    int id;  // 0..31, one per list
+    int bytes;
+    const void *kernels[LC3_N_VIEWS + 2];  // (the rest null)
+};
+static int lc3_lds_optin(HandleCommon &hc, const LdsOptin &list) {
+    if (hc.lds_optins >> list.id & 1u) return LC3GPU_OK;
+    static unsigned done[LC3_MAX_DEVICES] = {};  // bit LdsOptin::id
+    static std::mutex mu;                         // handles of different host threads may reach this at the same time
     std::lock_guard<std::mutex> lock(mu);
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
     if (dev < 0 || dev >= LC3_MAX_DEVICES) return LC3GPU_EINVAL;
-    if (done[dev]) return LC3GPU_OK;
-    HIP_TRY(hipFuncSetAttribute((const void *)lc3_pack_pc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIP_TRY(hipFuncSetAttribute((const void *)lc3_pack_pc_mixed_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    done[dev] = true;
+    if (!(done[dev] >> list.id & 1u)) {
+        for (const void *k : list.kernels)
+            if (k) HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, list.bytes));
+        done[dev] |= 1u << list.id;
+    }
+    hc.lds_optins |= 1u << list.id;
     return LC3GPU_OK;
 }
+static const LdsOptin lc3_pack_pc_optin = {0, 160 * 1024, {(const void *)lc3_pack_pc_kernel, (const void *)lc3_pack_pc_mixed_kernel}};
 // ... and the pair packer of the mc-items call (lc3gpu_encode_mixed_mc_items): at 128 frames per workgroup it passes the default 64 KB
 // from frame sizes of about 360 bytes on.  A list of its own, so that what the other calls opt in to is what it was
-static int lc3_pack_pc_mc_optin() {
-    static bool done[LC3_MAX_DEVICES] = {};
-    static std::mutex mu;
-    std::lock_guard<std::mutex> lock(mu);
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev < 0 || dev >= LC3_MAX_DEVICES) return LC3GPU_EINVAL;
-    if (done[dev]) return LC3GPU_OK;
-    HIP_TRY(hipFuncSetAttribute((const void *)LC3_MIXED_LAUNCH(lc3_pack_pc_mc_items_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    done[dev] = true;
-    return LC3GPU_OK;
-}
+static const LdsOptin lc3_pack_pc_mc_optin = {1, 160 * 1024, {(const void *)LC3_MIXED_LAUNCH(lc3_pack_pc_mc_items_kernel)}};
 // ... and the pair packer of the views call (lc3gpu_encode_mixed_views), as lc3_pack_pc_mc_optin
-static int lc3_pack_pc_views_optin() {
-    static bool done[LC3_MAX_DEVICES] = {};
-    static std::mutex mu;
-    std::lock_guard<std::mutex> lock(mu);
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev < 0 || dev >= LC3_MAX_DEVICES) return LC3GPU_EINVAL;
-    if (done[dev]) return LC3GPU_OK;
-    HIP_TRY(hipFuncSetAttribute((const void *)LC3_MIXED_LAUNCH(lc3_pack_pc_view_items_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    done[dev] = true;
-    return LC3GPU_OK;
-}
+static const LdsOptin lc3_pack_pc_views_optin = {2, 160 * 1024, {(const void *)LC3_MIXED_LAUNCH(lc3_pack_pc_view_items_kernel)}};
 // Frames per workgroup of the pair kernels: 128 (four waves, one per SIMD; ~40 KB of LDS at 150-byte frames).  Such a workgroup takes
 // the place of exactly ONE workgroup of a wave-per-stream kernel (40 KB, a wave per SIMD) when another handle's call runs beside it on
 // another HIP stream; with 256 frames (70 KB, two waves per SIMD) it displaced two for as long as it ran.  Measured: two-stream
@@ -3753,70 +3743,29 @@ static bool lc3_parse_pc_enabled() {
     }();
     return on;
 }
-static int lc3_parse_pc_optin() {
-    static bool done[LC3_MAX_DEVICES] = {};
-    static std::mutex mu;
-    std::lock_guard<std::mutex> lock(mu);
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev < 0 || dev >= LC3_MAX_DEVICES) return LC3GPU_EINVAL;
-    if (done[dev]) return LC3GPU_OK;
-    HIP_TRY(hipFuncSetAttribute((const void *)LC3_MIXED_LAUNCH(lc3_parse_pc_mixed_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LC3_PC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)lc3_parse_pc_kernel<lc3_cfg_any>, hipFuncAttributeMaxDynamicSharedMemorySize, LC3_PC_LDS_MAX));
-#define LC3_X(i, V) HIP_TRY(hipFuncSetAttribute((const void *)lc3_parse_pc_kernel<V>, hipFuncAttributeMaxDynamicSharedMemorySize, LC3_PC_LDS_MAX));
-    LC3_FOR_EACH_VIEW(LC3_X)
+#define LC3_X(i, V) (const void *)lc3_parse_pc_kernel<V>,
+static const LdsOptin lc3_parse_pc_optin = {3, LC3_PC_LDS_MAX, {(const void *)LC3_MIXED_LAUNCH(lc3_parse_pc_mixed_kernel),
+                                                                (const void *)lc3_parse_pc_kernel<lc3_cfg_any>, LC3_FOR_EACH_VIEW(LC3_X)}};
 #undef LC3_X
-    done[dev] = true;
-    return LC3GPU_OK;
-}
 // ... and the pair parser of the mc-items call (see lc3_pack_pc_mc_optin)
-static int lc3_parse_pc_mc_optin() {
-    static bool done[LC3_MAX_DEVICES] = {};
-    static std::mutex mu;
-    std::lock_guard<std::mutex> lock(mu);
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev < 0 || dev >= LC3_MAX_DEVICES) return LC3GPU_EINVAL;
-    if (done[dev]) return LC3GPU_OK;
-    HIP_TRY(hipFuncSetAttribute((const void *)LC3_MIXED_LAUNCH(lc3_parse_pc_mc_items_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LC3_PC_LDS_MAX));
-    done[dev] = true;
-    return LC3GPU_OK;
-}
+static const LdsOptin lc3_parse_pc_mc_optin = {4, LC3_PC_LDS_MAX, {(const void *)LC3_MIXED_LAUNCH(lc3_parse_pc_mc_items_kernel)}};
 // ... and the pair parser of the views call (see lc3_pack_pc_views_optin)
-static int lc3_parse_pc_views_optin() {
-    static bool done[LC3_MAX_DEVICES] = {};
-    static std::mutex mu;
-    std::lock_guard<std::mutex> lock(mu);
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev < 0 || dev >= LC3_MAX_DEVICES) return LC3GPU_EINVAL;
-    if (done[dev]) return LC3GPU_OK;
-    HIP_TRY(hipFuncSetAttribute((const void *)LC3_MIXED_LAUNCH(lc3_parse_pc_view_items_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LC3_PC_LDS_MAX));
-    done[dev] = true;
-    return LC3GPU_OK;
-}
+static const LdsOptin lc3_parse_pc_views_optin = {5, LC3_PC_LDS_MAX, {(const void *)LC3_MIXED_LAUNCH(lc3_parse_pc_view_items_kernel)}};
+// ... and the two pair kernels of the items calls (lc3gpu_encode_mixed_items / lc3gpu_decode_mixed_items), which were on no list: with
+// lc3_pack_pc_fpb / lc3_parse_pc_fpb frames per workgroup (128) lc3_pack_pc_lds passes 65 536 bytes from 373-byte frames on (65 584; 69 040
+// at LC3_MAX_NE) and lc3_parse_pc_lds from 349-byte frames on (65 648; 72 176 at LC3_MAX_NE).  A list of its own, by the same rule
+static const LdsOptin lc3_pc_items_optin = {6, LC3_PC_LDS_MAX, {(const void *)LC3_MIXED_LAUNCH(lc3_pack_pc_items_kernel),
+                                                                (const void *)LC3_MIXED_LAUNCH(lc3_parse_pc_items_kernel)}};
 static unsigned lc3_parse_pc_fpb(int nbytes) {
     unsigned fpb = lc3_frame_block(128u);  // (see lc3_pack_pc_fpb)
     while (fpb > 64u && lc3_parse_pc_lds(fpb, nbytes) > (size_t)LC3_PC_LDS_MAX) fpb >>= 1;
     return fpb;
 }
-// the TNS kernels use more than the default 64 KB of dynamic LDS: opt in once per device (every instantiation)
-static int lc3_tns_lds_optin() {
-    static bool done[LC3_MAX_DEVICES] = {};
-    static std::mutex mu;  // handles of different host threads may reach this at the same time
-    std::lock_guard<std::mutex> lock(mu);
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev < 0 || dev >= LC3_MAX_DEVICES) return LC3GPU_EINVAL;
-    if (done[dev]) return LC3GPU_OK;
-    HIP_TRY(hipFuncSetAttribute((const void *)lc3_tns_kernel<lc3_cfg_any>, hipFuncAttributeMaxDynamicSharedMemorySize, LC3_TNS_LDS));
-#define LC3_X(i, V) HIP_TRY(hipFuncSetAttribute((const void *)lc3_tns_kernel<V>, hipFuncAttributeMaxDynamicSharedMemorySize, LC3_TNS_LDS));
-    LC3_FOR_EACH_VIEW(LC3_X)
+// the TNS kernels use more than the default 64 KB of dynamic LDS (every instantiation)
+#define LC3_X(i, V) (const void *)lc3_tns_kernel<V>,
+static const LdsOptin lc3_tns_lds_optin = {
+    7, LC3_TNS_LDS, {(const void *)lc3_tns_kernel<lc3_cfg_any>, LC3_FOR_EACH_VIEW(LC3_X)(const void *) LC3_MIXED_LAUNCH(lc3_tns_mixed_kernel)}};
 #undef LC3_X
-    HIP_TRY(hipFuncSetAttribute((const void *)LC3_MIXED_LAUNCH(lc3_tns_mixed_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LC3_TNS_LDS));
-    done[dev] = true;
-    return LC3GPU_OK;
-}
 // workgroups of the reconstruction kernel: eight per CU (LC3GPU_RECON_GRID overrides: tuning aid)
 static size_t lc3_recon_grid() {
     static const size_t n = [] {
@@ -3832,6 +3781,29 @@ static unsigned lc3_frame_block_fit(size_t lds_fixed, size_t lds_per_frame) {
     unsigned fpb = lc3_frame_block(256u);
     while (fpb > 64u && lds_fixed + (size_t)fpb * lds_per_frame + 8 > 65536u) fpb >>= 1;
     return fpb;
+}
+// The launch geometry of the packer and of the parser for frames of at most max_nbytes, as producer / consumer pairs or one lane per frame:
+// frames per workgroup (what a mixed call builds its group table with), threads per workgroup, dynamic LDS
+struct FrameLaunch {
+    unsigned fpb, threads;
+    size_t lds;
+};
+static FrameLaunch lc3_pack_geometry(bool pairs, int max_nbytes) {
+    if (pairs) {
+        const unsigned fpb = lc3_pack_pc_fpb(max_nbytes);
+        return {fpb, 2 * fpb, lc3_pack_pc_lds(fpb, max_nbytes)};
+    }
+    const unsigned fpb = lc3_frame_block_fit(LC3_PACK_LDS_FIXED, (size_t)max_nbytes);
+    return {fpb, fpb, LC3_PACK_LDS_FIXED + (((size_t)fpb * (size_t)max_nbytes + 3) & ~(size_t)3) + 4};  // + the packer's sink byte
+}
+static FrameLaunch lc3_parse_geometry(bool pairs, int max_nbytes) {
+    if (pairs) {
+        const unsigned fpb = lc3_parse_pc_fpb(max_nbytes);
+        return {fpb, 2 * fpb, lc3_parse_pc_lds(fpb, max_nbytes)};
+    }
+    // as many frames as fit the default 64 KB of dynamic LDS (tables + 64 B of scale factors and nbytes of frame data per frame)
+    const unsigned fpb = lc3_frame_block_fit(LC3_PARSE_LDS_FIXED, (size_t)(64 + max_nbytes));
+    return {fpb, fpb, LC3_PARSE_LDS_FIXED + (size_t)fpb * (size_t)(64 + max_nbytes)};
 }
 
 static int encoder_reserve_planes(lc3gpu_encoder *e, size_t frames, hipStream_t stream) {
@@ -4222,27 +4194,20 @@ static int symbols_launch(const HostCfg &h, int32_t *planes, size_t frames, size
                    planes, (int)frames);
     return launch_result(LC3GPU_OK);
 }
-// the pair kernels' LDS opt-in, once per handle: the opt-in itself takes a process-wide lock
-static int pc_optin_once(HandleCommon &hc, int (*optin)()) {
-    if (hc.pc_optin_done) return LC3GPU_OK;
-    const int rc = optin();
-    if (rc == LC3GPU_OK) hc.pc_optin_done = true;
-    return rc;
-}
 // the packer: the producer / consumer pairs where the packer derives its symbols itself (full batches), else one lane per frame
+static bool lc3_pack_pairs(size_t frames_of_call) { return lc3_prep_symbols_mode(frames_of_call) == 0 && lc3_pack_pc_enabled(); }
 static int pack_launch(lc3gpu_encoder *e, const HostCfg &h, const int32_t *planes, uint8_t *d_out, int nbytes, size_t frames, int n_frames,
                        lc3_io io, size_t frames_of_call, hipStream_t stream) {
-    if (lc3_prep_symbols_mode(frames_of_call) == 0 && lc3_pack_pc_enabled()) {
-        const int rc = pc_optin_once(*e, lc3_pack_pc_optin);
+    const bool pairs = lc3_pack_pairs(frames_of_call);
+    const FrameLaunch g = lc3_pack_geometry(pairs, nbytes);
+    const dim3 grid((unsigned)((frames + g.fpb - 1) / g.fpb));
+    if (pairs) {
+        const int rc = lc3_lds_optin(*e, lc3_pack_pc_optin);
         if (rc) return rc;
-        const unsigned pfpb = lc3_pack_pc_fpb(nbytes);
-        hipLaunchKernelGGL(lc3_pack_pc_kernel, dim3((unsigned)((frames + pfpb - 1) / pfpb)), dim3(2 * pfpb), lc3_pack_pc_lds(pfpb, nbytes), stream,
-                           h.c.ne, planes, d_out, nbytes, (int)frames, n_frames, io, e->d_pc_timeouts);
+        hipLaunchKernelGGL(lc3_pack_pc_kernel, grid, dim3(g.threads), g.lds, stream, h.c.ne, planes, d_out, nbytes, (int)frames, n_frames, io,
+                           e->d_pc_timeouts);
     } else {
-        const unsigned fpb = lc3_frame_block_fit(LC3_PACK_LDS_FIXED, (size_t)nbytes);
-        const size_t lds = LC3_PACK_LDS_FIXED + (((size_t)fpb * (size_t)nbytes + 3) & ~(size_t)3) + 4;  // + the packer's sink byte
-        hipLaunchKernelGGL(lc3_pack_kernel, dim3((unsigned)((frames + fpb - 1) / fpb)), dim3(fpb), lds, stream, h.c.ne, planes, d_out, nbytes,
-                           (int)frames, n_frames, io);
+        hipLaunchKernelGGL(lc3_pack_kernel, grid, dim3(g.threads), g.lds, stream, h.c.ne, planes, d_out, nbytes, (int)frames, n_frames, io);
     }
     return LC3GPU_OK;
 }
@@ -4258,19 +4223,18 @@ static int vq_mixed_launch(lc3gpu_encoder *e, Groups groups, int n_frames, hipSt
 template <class Groups>
 static int pack_mixed_launch(lc3gpu_encoder *e, Groups groups, int max_nbytes, uint8_t *d_out, int n_frames, lc3_io io, size_t frames_of_call,
                              hipStream_t stream) {
+    const bool pairs = lc3_pack_pairs(frames_of_call);
+    const FrameLaunch g = lc3_pack_geometry(pairs, max_nbytes);
     GroupTable t;  // (a group table of the packer's own number of frames per workgroup)
-    if (lc3_prep_symbols_mode(frames_of_call) == 0 && lc3_pack_pc_enabled()) {
-        const int rc = pc_optin_once(*e, lc3_pack_pc_optin);
+    groups(g.fpb, t);
+    if (pairs) {
+        const int rc = lc3_lds_optin(*e, lc3_pack_pc_optin);
         if (rc) return rc;
-        const unsigned pfpb = lc3_pack_pc_fpb(max_nbytes);
-        groups(pfpb, t);
-        hipLaunchKernelGGL(lc3_pack_pc_mixed_kernel, dim3(t.wg_frame), dim3(2 * pfpb), lc3_pack_pc_lds(pfpb, max_nbytes), stream, t.G,
-                           (const int32_t *)e->d_planes, d_out, n_frames, io, e->d_pc_timeouts);
+        hipLaunchKernelGGL(lc3_pack_pc_mixed_kernel, dim3(t.wg_frame), dim3(g.threads), g.lds, stream, t.G, (const int32_t *)e->d_planes, d_out,
+                           n_frames, io, e->d_pc_timeouts);
     } else {
-        const unsigned fpb = lc3_frame_block_fit(LC3_PACK_LDS_FIXED, (size_t)max_nbytes);
-        const size_t lds = LC3_PACK_LDS_FIXED + (((size_t)fpb * (size_t)max_nbytes + 3) & ~(size_t)3) + 4;
-        groups(fpb, t);
-        hipLaunchKernelGGL(lc3_pack_mixed_kernel, dim3(t.wg_frame), dim3(fpb), lds, stream, t.G, (const int32_t *)e->d_planes, d_out, n_frames, io);
+        hipLaunchKernelGGL(lc3_pack_mixed_kernel, dim3(t.wg_frame), dim3(g.threads), g.lds, stream, t.G, (const int32_t *)e->d_planes, d_out, n_frames,
+                           io);
     }
     return LC3GPU_OK;
 }
@@ -4578,41 +4542,38 @@ int lc3gpu_encode_mixed_list(lc3gpu_encoder *e, const int32_t *channels, int n_l
     return call.end(rc);
 }
 
-// A list of items of a mixed handle: a frame count and a frame size per listed stream.  As lc3gpu_encode_mixed_list -- host check, plan into
-// a pinned slot, one upload -- with the items bucketed by (configuration, frame size, frame count) and the items twins of every kernel,
-// which read the frame count from their group row: one launch per kernel per LC3_MAX_GROUPS buckets.  The kernel forms are chosen once
-// per call, by its total number of frames.
-int lc3gpu_encode_mixed_items(lc3gpu_encoder *e, const lc3gpu_item *items, int n_items, const int16_t *d_pcm, uint8_t *d_out, void *stream_) {
-    if (!e || !e->mixed || n_items < 0) return LC3GPU_EINVAL;
-    if (n_items == 0) return LC3GPU_OK;
-    if (!items || !d_pcm || !d_out || ((uintptr_t)d_pcm & 3u) != 0) return LC3GPU_EINVAL;
-    if (!e->mixed_list_views_ok()) return LC3GPU_EUNSUPPORTED;
-    size_t frames = 0;
-    int max_frames = 0;
-    int rc = e->items_check(items, n_items, 20, &frames, &max_frames);
-    if (rc) return rc;
-    LC3_ON_DEVICE(e);
-    hipStream_t stream = (hipStream_t)stream_;
-    BatchCall call(*e, stream);
-    rc = call.begin();
-    if (rc == LC3GPU_OK) rc = encoder_reserve_planes(e, frames, stream);
-    if (rc == LC3GPU_OK) rc = e->mitems_send(items, n_items, e->fresh_mask.data(), stream);
-    if (rc) return rc;
+// ---- the items family: lc3gpu_encode_mixed_items, _mc_items and _views are one launch path over three placements of PCM and frames.  A
+// placement is the kernels that touch PCM or frame bytes -- front half, lane packer, pair packer; the three of a role have one signature --
+// and the pair packer's opt-in list.  The vector quantiser and the back half see plane columns only: the items call's kernels for all three
+struct EncPlacement {
+    decltype(&LC3_MIXED_LAUNCH(lc3_enc_front_items_kernel)) front;
+    decltype(&LC3_MIXED_LAUNCH(lc3_pack_items_kernel)) pack;
+    decltype(&LC3_MIXED_LAUNCH(lc3_pack_pc_items_kernel)) pack_pc;
+    const LdsOptin &pack_pc_optin;
+};
+static const EncPlacement lc3_enc_items = {LC3_MIXED_LAUNCH(lc3_enc_front_items_kernel), LC3_MIXED_LAUNCH(lc3_pack_items_kernel),
+                                           LC3_MIXED_LAUNCH(lc3_pack_pc_items_kernel), lc3_pc_items_optin};
+static const EncPlacement lc3_enc_mc_items = {LC3_MIXED_LAUNCH(lc3_enc_front_mc_items_kernel), LC3_MIXED_LAUNCH(lc3_pack_mc_items_kernel),
+                                              LC3_MIXED_LAUNCH(lc3_pack_pc_mc_items_kernel), lc3_pack_pc_mc_optin};
+static const EncPlacement lc3_enc_views = {LC3_MIXED_LAUNCH(lc3_enc_front_view_items_kernel), LC3_MIXED_LAUNCH(lc3_pack_view_items_kernel),
+                                           LC3_MIXED_LAUNCH(lc3_pack_pc_view_items_kernel), lc3_pack_pc_views_optin};
+// the four encoder kernels over the handle's items plan (built and sent by the caller's *_send; tab: its table on the device), one launch
+// per kernel per launch set.  pairs: the packer's form, chosen once per call by its total number of frames (lc3_pack_pairs), the opt-in
+// already taken
+static int encode_items_kernels(lc3gpu_encoder *e, const EncPlacement &pl, const lc3_stream_io *tab, size_t frames, bool pairs, const int16_t *d_pcm,
+                                uint8_t *d_out, hipStream_t stream) {
     const lc3_mitems_plan &P = e->mitems_plan;
     const int32_t *d_entries = e->d_mlist_entries();
-    const lc3_io io = {0, e->d_mlist_tab(n_items)};
+    const lc3_io io = {0, tab};
     const dim3 wg_block(64 * LC3_WG_WAVES);
-    const bool pairs = lc3_prep_symbols_mode(frames) == 0 && lc3_pack_pc_enabled();
-    if (pairs && (rc = pc_optin_once(*e, lc3_pack_pc_optin)) != LC3GPU_OK) return rc;
-    call.arm();
-    rc = encode_stages(
+    return encode_stages(
         e, stream, 0, nullptr,
         [&] {
             return items_stage(*e, P, [&](ItemsGroups groups, int) {
                 GroupTable t;
                 groups(256u, t);
-                hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_enc_front_items_kernel), dim3(t.wg_stream), wg_block, 0, stream, t.G, e->d_states, d_entries, d_pcm,
-                                   e->d_mid, e->d_planes, io, e->spec_flags);
+                hipLaunchKernelGGL(pl.front, dim3(t.wg_stream), wg_block, 0, stream, t.G, e->d_states, d_entries, d_pcm, e->d_mid, e->d_planes, io,
+                                   e->spec_flags);
                 return LC3GPU_OK;
             });
         },
@@ -4637,22 +4598,44 @@ int lc3gpu_encode_mixed_items(lc3gpu_encoder *e, const lc3gpu_item *items, int n
         [] { return LC3GPU_OK; },
         [&] {
             return items_stage(*e, P, [&](ItemsGroups groups, int max_nbytes) {
-                GroupTable t;  // (the LDS of a launch set is sized by ITS largest frame)
-                if (pairs) {
-                    const unsigned pfpb = lc3_pack_pc_fpb(max_nbytes);
-                    groups(pfpb, t);
-                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_pack_pc_items_kernel), dim3(t.wg_frame), dim3(2 * pfpb), lc3_pack_pc_lds(pfpb, max_nbytes),
-                                       stream, t.G, (const int32_t *)e->d_planes, d_out, io, e->d_pc_timeouts);
-                } else {
-                    const unsigned fpb = lc3_frame_block_fit(LC3_PACK_LDS_FIXED, (size_t)max_nbytes);
-                    const size_t lds = LC3_PACK_LDS_FIXED + (((size_t)fpb * (size_t)max_nbytes + 3) & ~(size_t)3) + 4;
-                    groups(fpb, t);
-                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_pack_items_kernel), dim3(t.wg_frame), dim3(fpb), lds, stream, t.G, (const int32_t *)e->d_planes,
-                                       d_out, io);
-                }
+                const FrameLaunch g = lc3_pack_geometry(pairs, max_nbytes);  // (the LDS of a launch set is sized by ITS largest frame)
+                GroupTable t;
+                groups(g.fpb, t);
+                if (pairs)
+                    hipLaunchKernelGGL(pl.pack_pc, dim3(t.wg_frame), dim3(g.threads), g.lds, stream, t.G, (const int32_t *)e->d_planes, d_out, io,
+                                       e->d_pc_timeouts);
+                else
+                    hipLaunchKernelGGL(pl.pack, dim3(t.wg_frame), dim3(g.threads), g.lds, stream, t.G, (const int32_t *)e->d_planes, d_out, io);
                 return LC3GPU_OK;
             });
         });
+}
+
+// A list of items of a mixed handle: a frame count and a frame size per listed stream.  As lc3gpu_encode_mixed_list -- host check, plan into
+// a pinned slot, one upload -- with the items bucketed by (configuration, frame size, frame count) and the items twins of every kernel,
+// which read the frame count from their group row: one launch per kernel per LC3_MAX_GROUPS buckets.  The kernel forms are chosen once
+// per call, by its total number of frames.
+int lc3gpu_encode_mixed_items(lc3gpu_encoder *e, const lc3gpu_item *items, int n_items, const int16_t *d_pcm, uint8_t *d_out, void *stream_) {
+    if (!e || !e->mixed || n_items < 0) return LC3GPU_EINVAL;
+    if (n_items == 0) return LC3GPU_OK;
+    if (!items || !d_pcm || !d_out || ((uintptr_t)d_pcm & 3u) != 0) return LC3GPU_EINVAL;
+    if (!e->mixed_list_views_ok()) return LC3GPU_EUNSUPPORTED;
+    size_t frames = 0;
+    int max_frames = 0;
+    int rc = e->items_check(items, n_items, 20, &frames, &max_frames);
+    if (rc) return rc;
+    LC3_ON_DEVICE(e);
+    hipStream_t stream = (hipStream_t)stream_;
+    const bool pairs = lc3_pack_pairs(frames);
+    BatchCall call(*e, stream);
+    rc = call.begin();
+    if (rc == LC3GPU_OK) rc = encoder_reserve_planes(e, frames, stream);
+    if (rc == LC3GPU_OK && pairs) rc = lc3_lds_optin(*e, lc3_pack_pc_optin);  // (the list this call has always taken; its own kernel's follows)
+    if (rc == LC3GPU_OK && pairs) rc = lc3_lds_optin(*e, lc3_enc_items.pack_pc_optin);
+    if (rc == LC3GPU_OK) rc = e->mitems_send(items, n_items, e->fresh_mask.data(), stream);
+    if (rc) return rc;
+    call.arm();
+    rc = encode_items_kernels(e, lc3_enc_items, e->d_mlist_tab(n_items), frames, pairs, d_pcm, d_out, stream);
     if (rc == LC3GPU_OK)
         for (int i = 0; i < n_items; i++) e->fresh_mask[(size_t)e->streams[(size_t)items[i].channel].internal] = 0;
     return call.end(rc);
@@ -4673,66 +4656,15 @@ int lc3gpu_encode_mixed_mc_items(lc3gpu_encoder *e, const lc3gpu_mc_item *items,
     if (rc) return rc;
     LC3_ON_DEVICE(e);
     hipStream_t stream = (hipStream_t)stream_;
+    const bool pairs = lc3_pack_pairs(frames);
     BatchCall call(*e, stream);
     rc = call.begin();
     if (rc == LC3GPU_OK) rc = encoder_reserve_planes(e, frames, stream);
+    if (rc == LC3GPU_OK && pairs) rc = lc3_lds_optin(*e, lc3_enc_mc_items.pack_pc_optin);
     if (rc == LC3GPU_OK) rc = e->mcitems_send(items, n_items, n_list, e->fresh_mask.data(), stream);
     if (rc) return rc;
-    const lc3_mitems_plan &P = e->mitems_plan;
-    const int32_t *d_entries = e->d_mlist_entries();
-    const lc3_io io = {0, e->d_mlist_tab(n_list)};
-    const dim3 wg_block(64 * LC3_WG_WAVES);
-    const bool pairs = lc3_prep_symbols_mode(frames) == 0 && lc3_pack_pc_enabled();
-    if (pairs && (rc = lc3_pack_pc_mc_optin()) != LC3GPU_OK) return rc;  // (before anything is launched)
     call.arm();
-    rc = encode_stages(
-        e, stream, 0, nullptr,
-        [&] {
-            return items_stage(*e, P, [&](ItemsGroups groups, int) {
-                GroupTable t;
-                groups(256u, t);
-                hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_enc_front_mc_items_kernel), dim3(t.wg_stream), wg_block, 0, stream, t.G, e->d_states, d_entries,
-                                   d_pcm, e->d_mid, e->d_planes, io, e->spec_flags);
-                return LC3GPU_OK;
-            });
-        },
-        [&] {
-            return items_stage(*e, P, [&](ItemsGroups groups, int) {
-                GroupTable t;
-                groups(256u, t);
-                hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_sns_vq_items_kernel), dim3(t.wg_frame), dim3(256), 0, stream, t.G, e->d_mid, e->d_planes,
-                                   e->spec_flags);
-                return LC3GPU_OK;
-            });
-        },
-        [&] {
-            return items_stage(*e, P, [&](ItemsGroups groups, int) {
-                GroupTable t;
-                groups(256u, t);
-                hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_enc_back_items_kernel), dim3(t.wg_stream), wg_block, 0, stream, t.G, e->d_states, d_entries,
-                                   (const float *)e->d_mid, e->d_planes, e->spec_flags | lc3_prep_symbols_flag(frames, true));
-                return LC3GPU_OK;
-            });
-        },
-        [] { return LC3GPU_OK; },
-        [&] {
-            return items_stage(*e, P, [&](ItemsGroups groups, int max_nbytes) {
-                GroupTable t;  // (the LDS of a launch set is sized by ITS largest frame)
-                if (pairs) {
-                    const unsigned pfpb = lc3_pack_pc_fpb(max_nbytes);
-                    groups(pfpb, t);
-                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_pack_pc_mc_items_kernel), dim3(t.wg_frame), dim3(2 * pfpb),
-                                       lc3_pack_pc_lds(pfpb, max_nbytes), stream, t.G, (const int32_t *)e->d_planes, d_out, io, e->d_pc_timeouts);
-                } else {
-                    const unsigned fpb = lc3_frame_block_fit(LC3_PACK_LDS_FIXED, (size_t)max_nbytes);
-                    const size_t lds = LC3_PACK_LDS_FIXED + (((size_t)fpb * (size_t)max_nbytes + 3) & ~(size_t)3) + 4;
-                    groups(fpb, t);
-                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_pack_mc_items_kernel), dim3(t.wg_frame), dim3(fpb), lds, stream, t.G,
-                                       (const int32_t *)e->d_planes, d_out, io);
-                }
-                return LC3GPU_OK;
-            });
-        });
+    rc = encode_items_kernels(e, lc3_enc_mc_items, e->d_mlist_tab(n_list), frames, pairs, d_pcm, d_out, stream);
     if (rc == LC3GPU_OK)
         for (int i = 0; i < n_items; i++)
             for (int c = 0; c < items[i].n_channels; c++) e->fresh_mask[(size_t)e->streams[(size_t)(items[i].first_channel + c)].internal] = 0;
@@ -4755,66 +4687,15 @@ int lc3gpu_encode_mixed_views(lc3gpu_encoder *e, const lc3gpu_view *views, int n
     if (rc) return rc;
     LC3_ON_DEVICE(e);
     hipStream_t stream = (hipStream_t)stream_;
+    const bool pairs = lc3_pack_pairs(frames);
     BatchCall call(*e, stream);
     rc = call.begin();
     if (rc == LC3GPU_OK) rc = encoder_reserve_planes(e, frames, stream);
+    if (rc == LC3GPU_OK && pairs) rc = lc3_lds_optin(*e, lc3_enc_views.pack_pc_optin);
     if (rc == LC3GPU_OK) rc = e->mviews_send(views, n_views, 0, e->fresh_mask.data(), stream);
     if (rc) return rc;
-    const lc3_mitems_plan &P = e->mitems_plan;
-    const int32_t *d_entries = e->d_mlist_entries();
-    const lc3_io io = {0, e->d_mviews_rows(n_views)};
-    const dim3 wg_block(64 * LC3_WG_WAVES);
-    const bool pairs = lc3_prep_symbols_mode(frames) == 0 && lc3_pack_pc_enabled();
-    if (pairs && (rc = lc3_pack_pc_views_optin()) != LC3GPU_OK) return rc;  // (before anything is launched)
     call.arm();
-    rc = encode_stages(
-        e, stream, 0, nullptr,
-        [&] {
-            return items_stage(*e, P, [&](ItemsGroups groups, int) {
-                GroupTable t;
-                groups(256u, t);
-                hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_enc_front_view_items_kernel), dim3(t.wg_stream), wg_block, 0, stream, t.G, e->d_states, d_entries,
-                                   d_pcm, e->d_mid, e->d_planes, io, e->spec_flags);
-                return LC3GPU_OK;
-            });
-        },
-        [&] {
-            return items_stage(*e, P, [&](ItemsGroups groups, int) {
-                GroupTable t;
-                groups(256u, t);
-                hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_sns_vq_items_kernel), dim3(t.wg_frame), dim3(256), 0, stream, t.G, e->d_mid, e->d_planes,
-                                   e->spec_flags);
-                return LC3GPU_OK;
-            });
-        },
-        [&] {
-            return items_stage(*e, P, [&](ItemsGroups groups, int) {
-                GroupTable t;
-                groups(256u, t);
-                hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_enc_back_items_kernel), dim3(t.wg_stream), wg_block, 0, stream, t.G, e->d_states, d_entries,
-                                   (const float *)e->d_mid, e->d_planes, e->spec_flags | lc3_prep_symbols_flag(frames, true));
-                return LC3GPU_OK;
-            });
-        },
-        [] { return LC3GPU_OK; },
-        [&] {
-            return items_stage(*e, P, [&](ItemsGroups groups, int max_nbytes) {
-                GroupTable t;  // (the LDS of a launch set is sized by ITS largest frame)
-                if (pairs) {
-                    const unsigned pfpb = lc3_pack_pc_fpb(max_nbytes);
-                    groups(pfpb, t);
-                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_pack_pc_view_items_kernel), dim3(t.wg_frame), dim3(2 * pfpb),
-                                       lc3_pack_pc_lds(pfpb, max_nbytes), stream, t.G, (const int32_t *)e->d_planes, d_out, io, e->d_pc_timeouts);
-                } else {
-                    const unsigned fpb = lc3_frame_block_fit(LC3_PACK_LDS_FIXED, (size_t)max_nbytes);
-                    const size_t lds = LC3_PACK_LDS_FIXED + (((size_t)fpb * (size_t)max_nbytes + 3) & ~(size_t)3) + 4;
-                    groups(fpb, t);
-                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_pack_view_items_kernel), dim3(t.wg_frame), dim3(fpb), lds, stream, t.G,
-                                       (const int32_t *)e->d_planes, d_out, io);
-                }
-                return LC3GPU_OK;
-            });
-        });
+    rc = encode_items_kernels(e, lc3_enc_views, e->d_mviews_rows(n_views), frames, pairs, d_pcm, d_out, stream);
     if (rc == LC3GPU_OK)
         for (int i = 0; i < n_views; i++) e->fresh_mask[(size_t)e->streams[(size_t)views[i].channel].internal] = 0;
     return call.end(rc);
@@ -5050,21 +4931,19 @@ static int decode_stages(lc3gpu_decoder *d, hipStream_t stream, int chain, int m
 
 // ---- the launches the decoder's call variants share (uniform handles: `frames` frames in `planes`)
 // the parser: the producer / consumer pairs where the parsing lane reconstructs the spectrum (full batches), else one lane per frame
+static bool lc3_parse_pairs(int mode) { return mode == LC3_RECON_LANE && lc3_parse_pc_enabled(); }
 static int parse_launch(lc3gpu_decoder *d, const HostCfg &h, const uint8_t *d_in, const uint8_t *d_bad, int32_t *planes, int nbytes, size_t frames,
                         int n_frames, lc3_io io, int mode, hipStream_t stream) {
-    if (mode == LC3_RECON_LANE && lc3_parse_pc_enabled()) {
-        const int rc = pc_optin_once(*d, lc3_parse_pc_optin);
+    const bool pairs = lc3_parse_pairs(mode);
+    const FrameLaunch g = lc3_parse_geometry(pairs, nbytes);
+    const dim3 grid((unsigned)((frames + g.fpb - 1) / g.fpb));
+    if (pairs) {
+        const int rc = lc3_lds_optin(*d, lc3_parse_pc_optin);
         if (rc) return rc;
-        const unsigned pfpb = lc3_parse_pc_fpb(nbytes);
-        LC3_LAUNCH_CFG(lc3_parse_pc_kernel, h, dim3((unsigned)((frames + pfpb - 1) / pfpb)), dim3(2 * pfpb), lc3_parse_pc_lds(pfpb, nbytes), stream,
-                       d_in, d_bad, planes, nbytes, (int)frames, n_frames, io, d->d_pc_timeouts);
+        LC3_LAUNCH_CFG(lc3_parse_pc_kernel, h, grid, dim3(g.threads), g.lds, stream, d_in, d_bad, planes, nbytes, (int)frames, n_frames, io,
+                       d->d_pc_timeouts);
     } else {
-        // frames per workgroup: as many as fit the default 64 KB of dynamic LDS (tables + 64 B of scale factors and nbytes of
-        // frame data per frame)
-        const unsigned fpb = lc3_frame_block_fit(LC3_PARSE_LDS_FIXED, (size_t)(64 + nbytes));
-        const size_t lds = LC3_PARSE_LDS_FIXED + (size_t)fpb * (size_t)(64 + nbytes);
-        LC3_LAUNCH_CFG(lc3_parse_kernel, h, dim3((unsigned)((frames + fpb - 1) / fpb)), dim3(fpb), lds, stream, d_in, d_bad, planes, nbytes,
-                       (int)frames, n_frames, io, mode);
+        LC3_LAUNCH_CFG(lc3_parse_kernel, h, grid, dim3(g.threads), g.lds, stream, d_in, d_bad, planes, nbytes, (int)frames, n_frames, io, mode);
     }
     return LC3GPU_OK;
 }
@@ -5088,20 +4967,18 @@ extern "C++" {
 template <class Groups>
 static int parse_mixed_launch(lc3gpu_decoder *d, Groups groups, int max_nbytes, const uint8_t *d_in, const uint8_t *d_bad, int n_frames, lc3_io io,
                               int mode, hipStream_t stream) {
+    const bool pairs = lc3_parse_pairs(mode);
+    const FrameLaunch g = lc3_parse_geometry(pairs, max_nbytes);
     GroupTable t;  // (a group table of the parser's own number of frames per workgroup)
-    if (mode == LC3_RECON_LANE && lc3_parse_pc_enabled()) {
-        const int rc = pc_optin_once(*d, lc3_parse_pc_optin);
+    groups(g.fpb, t);
+    if (pairs) {
+        const int rc = lc3_lds_optin(*d, lc3_parse_pc_optin);
         if (rc) return rc;
-        const unsigned pfpb = lc3_parse_pc_fpb(max_nbytes);
-        groups(pfpb, t);
-        hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_parse_pc_mixed_kernel), dim3(t.wg_frame), dim3(2 * pfpb), lc3_parse_pc_lds(pfpb, max_nbytes), stream, t.G,
-                           d_in, d_bad, d->d_planes, n_frames, io, d->d_pc_timeouts);
+        hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_parse_pc_mixed_kernel), dim3(t.wg_frame), dim3(g.threads), g.lds, stream, t.G, d_in, d_bad,
+                           d->d_planes, n_frames, io, d->d_pc_timeouts);
     } else {
-        const unsigned fpb = lc3_frame_block_fit(LC3_PARSE_LDS_FIXED, (size_t)(64 + max_nbytes));
-        const size_t lds = LC3_PARSE_LDS_FIXED + (size_t)fpb * (size_t)(64 + max_nbytes);
-        groups(fpb, t);
-        hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_parse_mixed_kernel), dim3(t.wg_frame), dim3(fpb), lds, stream, t.G, d_in, d_bad, d->d_planes, n_frames,
-                           io, mode);
+        hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_parse_mixed_kernel), dim3(t.wg_frame), dim3(g.threads), g.lds, stream, t.G, d_in, d_bad, d->d_planes,
+                           n_frames, io, mode);
     }
     return LC3GPU_OK;
 }
@@ -5169,7 +5046,7 @@ static int decode_launch(lc3gpu_decoder *d, const HostCfg &h, int first, int n, 
     if (rc) return rc;
     lc3_io io = {layout == LC3GPU_LAYOUT_INTERLEAVED ? n : 0, nullptr};
     const int mode = lc3_recon_mode(frames, n_frames);
-    if (mode == LC3_RECON_WAVE && (rc = lc3_tns_lds_optin()) != LC3GPU_OK) return rc;
+    if (mode == LC3_RECON_WAVE && (rc = lc3_lds_optin(*d, lc3_tns_lds_optin)) != LC3GPU_OK) return rc;
     call.arm();
     if (parts == 1) {
         rc = decode_kernels(d, h, first, n, d_in, d_bad, d_pcm, d->d_planes, nbytes, n_frames, io, mode, stream, 0, fresh);
@@ -5224,7 +5101,7 @@ int lc3gpu_decode_list(lc3gpu_decoder *d, const int32_t *channels, int n_list, c
     BatchCall call(*d, stream);
     rc = call.begin();
     if (rc == LC3GPU_OK) rc = decoder_reserve_planes(d, frames, stream);
-    if (rc == LC3GPU_OK && mode == LC3_RECON_WAVE) rc = lc3_tns_lds_optin();
+    if (rc == LC3GPU_OK && mode == LC3_RECON_WAVE) rc = lc3_lds_optin(*d, lc3_tns_lds_optin);
     if (rc == LC3GPU_OK) rc = d->list_upload(channels, n_list, d->fresh_mask, stream);
     if (rc) return rc;
     const lc3_io io = {0, nullptr};
@@ -5265,15 +5142,14 @@ int lc3gpu_decode_vbr(lc3gpu_decoder *d, const uint8_t *d_in, const uint16_t *d_
     if (rc == LC3GPU_OK) rc = decoder_reserve_planes(d, frames, stream);
     if (rc) return rc;
     const int mode = lc3_recon_mode(frames, n_frames);
-    if (mode == LC3_RECON_WAVE && (rc = lc3_tns_lds_optin()) != LC3GPU_OK) return rc;
+    if (mode == LC3_RECON_WAVE && (rc = lc3_lds_optin(*d, lc3_tns_lds_optin)) != LC3GPU_OK) return rc;
     call.arm();
     rc = decode_stages(
         d, stream, 0, mode,
         [&] {
-            const unsigned fpb = lc3_frame_block_fit(LC3_PARSE_LDS_FIXED, (size_t)(64 + slot_bytes));
-            const size_t lds = LC3_PARSE_LDS_FIXED + (size_t)fpb * (size_t)(64 + slot_bytes);
-            LC3_LAUNCH_HEADLINE(lc3_parse_vbr_kernel, h, dim3((unsigned)((frames + fpb - 1) / fpb)), dim3(fpb), lds, stream, d_in, d_bad, d_nbytes,
-                                slot_bytes, d->d_planes, (int)frames, mode);
+            const FrameLaunch g = lc3_parse_geometry(false, slot_bytes);
+            LC3_LAUNCH_HEADLINE(lc3_parse_vbr_kernel, h, dim3((unsigned)((frames + g.fpb - 1) / g.fpb)), dim3(g.threads), g.lds, stream, d_in, d_bad,
+                                d_nbytes, slot_bytes, d->d_planes, (int)frames, mode);
             return LC3GPU_OK;
         },
         [&] {
@@ -5336,7 +5212,7 @@ int lc3gpu_decode_mixed(lc3gpu_decoder *d, const uint8_t *d_in, const uint8_t *d
     if (rc) return rc;
     lc3_io io = {0, d->d_tab};
     const int mode = lc3_recon_mode(frames, n_frames);
-    if (mode == LC3_RECON_WAVE && (rc = lc3_tns_lds_optin()) != LC3GPU_OK) return rc;
+    if (mode == LC3_RECON_WAVE && (rc = lc3_lds_optin(*d, lc3_tns_lds_optin)) != LC3GPU_OK) return rc;
     const HandleGroups groups{*d, n_frames};
     GroupTable t;  // (the synthesis kernel's workgroups do not depend on the frames per workgroup of the others)
     groups(256u, t);
@@ -5376,7 +5252,7 @@ int lc3gpu_decode_mixed_list(lc3gpu_decoder *d, const int32_t *channels, int n_l
     BatchCall call(*d, stream);
     rc = call.begin();
     if (rc == LC3GPU_OK) rc = decoder_reserve_planes(d, frames, stream);
-    if (rc == LC3GPU_OK && mode == LC3_RECON_WAVE) rc = lc3_tns_lds_optin();
+    if (rc == LC3GPU_OK && mode == LC3_RECON_WAVE) rc = lc3_lds_optin(*d, lc3_tns_lds_optin);
     if (rc == LC3GPU_OK) rc = d->mlist_send(channels, n_list, d->fresh_mask.data(), stream, P);
     if (rc) return rc;
     const int32_t *d_entries = d->d_mlist_entries();
@@ -5403,50 +5279,43 @@ int lc3gpu_decode_mixed_list(lc3gpu_decoder *d, const int32_t *channels, int n_l
     return call.end(rc);
 }
 
-// A list of items of a mixed handle, as lc3gpu_encode_mixed_items: the parser and reconstruction form are chosen once per call, by its
-// total number of frames and its largest per-item count
-int lc3gpu_decode_mixed_items(lc3gpu_decoder *d, const lc3gpu_item *items, int n_items, const uint8_t *d_in, const uint8_t *d_bad, int16_t *d_pcm,
-                              void *stream_) {
-    if (!d || !d->mixed || n_items < 0) return LC3GPU_EINVAL;
-    if (n_items == 0) return LC3GPU_OK;
-    if (!items || !d_in || !d_pcm || ((uintptr_t)d_pcm & 3u) != 0) return LC3GPU_EINVAL;
-    if (!d->mixed_list_views_ok()) return LC3GPU_EUNSUPPORTED;
-    size_t frames = 0;
-    int max_frames = 0;
-    int rc = d->items_check(items, n_items, 1, &frames, &max_frames);
-    if (rc) return rc;
-    LC3_ON_DEVICE(d);
-    hipStream_t stream = (hipStream_t)stream_;
-    const int mode = lc3_recon_mode(frames, max_frames);
-    const bool pairs = mode == LC3_RECON_LANE && lc3_parse_pc_enabled();
-    BatchCall call(*d, stream);
-    rc = call.begin();
-    if (rc == LC3GPU_OK) rc = decoder_reserve_planes(d, frames, stream);
-    if (rc == LC3GPU_OK && mode == LC3_RECON_WAVE) rc = lc3_tns_lds_optin();
-    if (rc == LC3GPU_OK && pairs) rc = pc_optin_once(*d, lc3_parse_pc_optin);
-    if (rc == LC3GPU_OK) rc = d->mitems_send(items, n_items, d->fresh_mask.data(), stream);
-    if (rc) return rc;
+// ---- the items family of the decoder (as EncPlacement): a placement is the kernels that touch frame bytes, flags or PCM -- lane parser,
+// pair parser, both synthesis forms -- and the pair parser's opt-in list; the wave-per-frame reconstruction and the TNS kernel see plane
+// columns only and are the items call's for all three
+struct DecPlacement {
+    decltype(&LC3_MIXED_LAUNCH(lc3_parse_items_kernel)) parse;
+    decltype(&LC3_MIXED_LAUNCH(lc3_parse_pc_items_kernel)) parse_pc;
+    decltype(&LC3_MIXED_LAUNCH(lc3_decode_items_kernel)) synth, synth_late;
+    const LdsOptin &parse_pc_optin;
+};
+static const DecPlacement lc3_dec_items = {LC3_MIXED_LAUNCH(lc3_parse_items_kernel), LC3_MIXED_LAUNCH(lc3_parse_pc_items_kernel),
+                                           LC3_MIXED_LAUNCH(lc3_decode_items_kernel), LC3_MIXED_LAUNCH(lc3_decode_items_late_kernel),
+                                           lc3_pc_items_optin};
+static const DecPlacement lc3_dec_mc_items = {LC3_MIXED_LAUNCH(lc3_parse_mc_items_kernel), LC3_MIXED_LAUNCH(lc3_parse_pc_mc_items_kernel),
+                                              LC3_MIXED_LAUNCH(lc3_decode_mc_items_kernel), LC3_MIXED_LAUNCH(lc3_decode_mc_items_late_kernel),
+                                              lc3_parse_pc_mc_optin};
+static const DecPlacement lc3_dec_views = {LC3_MIXED_LAUNCH(lc3_parse_view_items_kernel), LC3_MIXED_LAUNCH(lc3_parse_pc_view_items_kernel),
+                                           LC3_MIXED_LAUNCH(lc3_decode_view_items_kernel), LC3_MIXED_LAUNCH(lc3_decode_view_items_late_kernel),
+                                           lc3_parse_pc_views_optin};
+// the decoder kernels over the handle's items plan (as encode_items_kernels).  mode: the reconstruction form, chosen once per call
+// (lc3_recon_mode over its total number of frames and its largest per-item count); the opt-ins already taken
+static int decode_items_kernels(lc3gpu_decoder *d, const DecPlacement &pl, const lc3_stream_io *tab, int mode, const uint8_t *d_in, const uint8_t *d_bad,
+                                int16_t *d_pcm, hipStream_t stream) {
     const lc3_mitems_plan &P = d->mitems_plan;
     const int32_t *d_entries = d->d_mlist_entries();
-    const lc3_io io = {0, d->d_mlist_tab(n_items)};
-    call.arm();
-    rc = decode_stages(
+    const lc3_io io = {0, tab};
+    const bool pairs = lc3_parse_pairs(mode);
+    return decode_stages(
         d, stream, 0, mode,
         [&] {
             return items_stage(*d, P, [&](ItemsGroups groups, int max_nbytes) {
+                const FrameLaunch g = lc3_parse_geometry(pairs, max_nbytes);
                 GroupTable t;
-                if (pairs) {
-                    const unsigned pfpb = lc3_parse_pc_fpb(max_nbytes);
-                    groups(pfpb, t);
-                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_parse_pc_items_kernel), dim3(t.wg_frame), dim3(2 * pfpb), lc3_parse_pc_lds(pfpb, max_nbytes),
-                                       stream, t.G, d_in, d_bad, d->d_planes, io, d->d_pc_timeouts);
-                } else {
-                    const unsigned fpb = lc3_frame_block_fit(LC3_PARSE_LDS_FIXED, (size_t)(64 + max_nbytes));
-                    const size_t lds = LC3_PARSE_LDS_FIXED + (size_t)fpb * (size_t)(64 + max_nbytes);
-                    groups(fpb, t);
-                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_parse_items_kernel), dim3(t.wg_frame), dim3(fpb), lds, stream, t.G, d_in, d_bad, d->d_planes, io,
-                                       mode);
-                }
+                groups(g.fpb, t);
+                if (pairs)
+                    hipLaunchKernelGGL(pl.parse_pc, dim3(t.wg_frame), dim3(g.threads), g.lds, stream, t.G, d_in, d_bad, d->d_planes, io, d->d_pc_timeouts);
+                else
+                    hipLaunchKernelGGL(pl.parse, dim3(t.wg_frame), dim3(g.threads), g.lds, stream, t.G, d_in, d_bad, d->d_planes, io, mode);
                 return LC3GPU_OK;
             });
         },
@@ -5470,15 +5339,39 @@ int lc3gpu_decode_mixed_items(lc3gpu_decoder *d, const lc3gpu_item *items, int n
             return items_stage(*d, P, [&](ItemsGroups groups, int) {
                 GroupTable t;
                 groups(256u, t);
-                if (mode == LC3_RECON_LATE)
-                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_decode_items_late_kernel), dim3(t.wg_stream), dim3(64 * LC3_WG_WAVES), 0, stream, t.G, d->d_states,
-                                       d_entries, (const int32_t *)d->d_planes, d_pcm, io);
-                else
-                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_decode_items_kernel), dim3(t.wg_stream), dim3(64 * LC3_WG_WAVES), 0, stream, t.G, d->d_states,
-                                       d_entries, (const int32_t *)d->d_planes, d_pcm, io);
+                hipLaunchKernelGGL(mode == LC3_RECON_LATE ? pl.synth_late : pl.synth, dim3(t.wg_stream), dim3(64 * LC3_WG_WAVES), 0, stream, t.G,
+                                   d->d_states, d_entries, (const int32_t *)d->d_planes, d_pcm, io);
                 return LC3GPU_OK;
             });
         });
+}
+
+// A list of items of a mixed handle, as lc3gpu_encode_mixed_items: the parser and reconstruction form are chosen once per call, by its
+// total number of frames and its largest per-item count
+int lc3gpu_decode_mixed_items(lc3gpu_decoder *d, const lc3gpu_item *items, int n_items, const uint8_t *d_in, const uint8_t *d_bad, int16_t *d_pcm,
+                              void *stream_) {
+    if (!d || !d->mixed || n_items < 0) return LC3GPU_EINVAL;
+    if (n_items == 0) return LC3GPU_OK;
+    if (!items || !d_in || !d_pcm || ((uintptr_t)d_pcm & 3u) != 0) return LC3GPU_EINVAL;
+    if (!d->mixed_list_views_ok()) return LC3GPU_EUNSUPPORTED;
+    size_t frames = 0;
+    int max_frames = 0;
+    int rc = d->items_check(items, n_items, 1, &frames, &max_frames);
+    if (rc) return rc;
+    LC3_ON_DEVICE(d);
+    hipStream_t stream = (hipStream_t)stream_;
+    const int mode = lc3_recon_mode(frames, max_frames);
+    const bool pairs = lc3_parse_pairs(mode);
+    BatchCall call(*d, stream);
+    rc = call.begin();
+    if (rc == LC3GPU_OK) rc = decoder_reserve_planes(d, frames, stream);
+    if (rc == LC3GPU_OK && mode == LC3_RECON_WAVE) rc = lc3_lds_optin(*d, lc3_tns_lds_optin);
+    if (rc == LC3GPU_OK && pairs) rc = lc3_lds_optin(*d, lc3_parse_pc_optin);  // (as lc3gpu_encode_mixed_items)
+    if (rc == LC3GPU_OK && pairs) rc = lc3_lds_optin(*d, lc3_dec_items.parse_pc_optin);
+    if (rc == LC3GPU_OK) rc = d->mitems_send(items, n_items, d->fresh_mask.data(), stream);
+    if (rc) return rc;
+    call.arm();
+    rc = decode_items_kernels(d, lc3_dec_items, d->d_mlist_tab(n_items), mode, d_in, d_bad, d_pcm, stream);
     if (rc == LC3GPU_OK)
         for (int i = 0; i < n_items; i++) d->fresh_clear(d->streams[(size_t)items[i].channel].internal);
     return call.end(rc);
@@ -5499,67 +5392,16 @@ int lc3gpu_decode_mixed_mc_items(lc3gpu_decoder *d, const lc3gpu_mc_item *items,
     LC3_ON_DEVICE(d);
     hipStream_t stream = (hipStream_t)stream_;
     const int mode = lc3_recon_mode(frames, max_frames);
-    const bool pairs = mode == LC3_RECON_LANE && lc3_parse_pc_enabled();
+    const bool pairs = lc3_parse_pairs(mode);
     BatchCall call(*d, stream);
     rc = call.begin();
     if (rc == LC3GPU_OK) rc = decoder_reserve_planes(d, frames, stream);
-    if (rc == LC3GPU_OK && mode == LC3_RECON_WAVE) rc = lc3_tns_lds_optin();
-    if (rc == LC3GPU_OK && pairs) rc = lc3_parse_pc_mc_optin();
+    if (rc == LC3GPU_OK && mode == LC3_RECON_WAVE) rc = lc3_lds_optin(*d, lc3_tns_lds_optin);
+    if (rc == LC3GPU_OK && pairs) rc = lc3_lds_optin(*d, lc3_dec_mc_items.parse_pc_optin);
     if (rc == LC3GPU_OK) rc = d->mcitems_send(items, n_items, n_list, d->fresh_mask.data(), stream);
     if (rc) return rc;
-    const lc3_mitems_plan &P = d->mitems_plan;
-    const int32_t *d_entries = d->d_mlist_entries();
-    const lc3_io io = {0, d->d_mlist_tab(n_list)};
     call.arm();
-    rc = decode_stages(
-        d, stream, 0, mode,
-        [&] {
-            return items_stage(*d, P, [&](ItemsGroups groups, int max_nbytes) {
-                GroupTable t;
-                if (pairs) {
-                    const unsigned pfpb = lc3_parse_pc_fpb(max_nbytes);
-                    groups(pfpb, t);
-                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_parse_pc_mc_items_kernel), dim3(t.wg_frame), dim3(2 * pfpb),
-                                       lc3_parse_pc_lds(pfpb, max_nbytes), stream, t.G, d_in, d_bad, d->d_planes, io, d->d_pc_timeouts);
-                } else {
-                    const unsigned fpb = lc3_frame_block_fit(LC3_PARSE_LDS_FIXED, (size_t)(64 + max_nbytes));
-                    const size_t lds = LC3_PARSE_LDS_FIXED + (size_t)fpb * (size_t)(64 + max_nbytes);
-                    groups(fpb, t);
-                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_parse_mc_items_kernel), dim3(t.wg_frame), dim3(fpb), lds, stream, t.G, d_in, d_bad, d->d_planes,
-                                       io, mode);
-                }
-                return LC3GPU_OK;
-            });
-        },
-        [&] {
-            return items_stage(*d, P, [&](ItemsGroups groups, int) {
-                GroupTable t;
-                groups((unsigned)LC3_WG_WAVES, t);
-                hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_recon_items_kernel), dim3(t.wg_frame), dim3(64 * LC3_WG_WAVES), 0, stream, t.G, d->d_planes);
-                return LC3GPU_OK;
-            });
-        },
-        [&] {
-            return items_stage(*d, P, [&](ItemsGroups groups, int) {
-                GroupTable t;
-                groups((unsigned)LC3_TNS_FPB, t);
-                hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_tns_items_kernel), dim3(t.wg_frame), dim3(LC3_TNS_FPB), LC3_TNS_LDS, stream, t.G, d->d_planes);
-                return LC3GPU_OK;
-            });
-        },
-        [&] {
-            return items_stage(*d, P, [&](ItemsGroups groups, int) {
-                GroupTable t;
-                groups(256u, t);
-                if (mode == LC3_RECON_LATE)
-                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_decode_mc_items_late_kernel), dim3(t.wg_stream), dim3(64 * LC3_WG_WAVES), 0, stream, t.G,
-                                       d->d_states, d_entries, (const int32_t *)d->d_planes, d_pcm, io);
-                else
-                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_decode_mc_items_kernel), dim3(t.wg_stream), dim3(64 * LC3_WG_WAVES), 0, stream, t.G,
-                                       d->d_states, d_entries, (const int32_t *)d->d_planes, d_pcm, io);
-                return LC3GPU_OK;
-            });
-        });
+    rc = decode_items_kernels(d, lc3_dec_mc_items, d->d_mlist_tab(n_list), mode, d_in, d_bad, d_pcm, stream);
     if (rc == LC3GPU_OK)
         for (int i = 0; i < n_items; i++)
             for (int c = 0; c < items[i].n_channels; c++) d->fresh_clear(d->streams[(size_t)(items[i].first_channel + c)].internal);
@@ -5583,67 +5425,16 @@ int lc3gpu_decode_mixed_views(lc3gpu_decoder *d, const lc3gpu_view *views, int n
     LC3_ON_DEVICE(d);
     hipStream_t stream = (hipStream_t)stream_;
     const int mode = lc3_recon_mode(frames, max_frames);
-    const bool pairs = mode == LC3_RECON_LANE && lc3_parse_pc_enabled();
+    const bool pairs = lc3_parse_pairs(mode);
     BatchCall call(*d, stream);
     rc = call.begin();
     if (rc == LC3GPU_OK) rc = decoder_reserve_planes(d, frames, stream);
-    if (rc == LC3GPU_OK && mode == LC3_RECON_WAVE) rc = lc3_tns_lds_optin();
-    if (rc == LC3GPU_OK && pairs) rc = lc3_parse_pc_views_optin();
+    if (rc == LC3GPU_OK && mode == LC3_RECON_WAVE) rc = lc3_lds_optin(*d, lc3_tns_lds_optin);
+    if (rc == LC3GPU_OK && pairs) rc = lc3_lds_optin(*d, lc3_dec_views.parse_pc_optin);
     if (rc == LC3GPU_OK) rc = d->mviews_send(views, n_views, use_flags, d->fresh_mask.data(), stream);
     if (rc) return rc;
-    const lc3_mitems_plan &P = d->mitems_plan;
-    const int32_t *d_entries = d->d_mlist_entries();
-    const lc3_io io = {0, d->d_mviews_rows(n_views)};
     call.arm();
-    rc = decode_stages(
-        d, stream, 0, mode,
-        [&] {
-            return items_stage(*d, P, [&](ItemsGroups groups, int max_nbytes) {
-                GroupTable t;
-                if (pairs) {
-                    const unsigned pfpb = lc3_parse_pc_fpb(max_nbytes);
-                    groups(pfpb, t);
-                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_parse_pc_view_items_kernel), dim3(t.wg_frame), dim3(2 * pfpb),
-                                       lc3_parse_pc_lds(pfpb, max_nbytes), stream, t.G, d_in, d_bad, d->d_planes, io, d->d_pc_timeouts);
-                } else {
-                    const unsigned fpb = lc3_frame_block_fit(LC3_PARSE_LDS_FIXED, (size_t)(64 + max_nbytes));
-                    const size_t lds = LC3_PARSE_LDS_FIXED + (size_t)fpb * (size_t)(64 + max_nbytes);
-                    groups(fpb, t);
-                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_parse_view_items_kernel), dim3(t.wg_frame), dim3(fpb), lds, stream, t.G, d_in, d_bad, d->d_planes,
-                                       io, mode);
-                }
-                return LC3GPU_OK;
-            });
-        },
-        [&] {
-            return items_stage(*d, P, [&](ItemsGroups groups, int) {
-                GroupTable t;
-                groups((unsigned)LC3_WG_WAVES, t);
-                hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_recon_items_kernel), dim3(t.wg_frame), dim3(64 * LC3_WG_WAVES), 0, stream, t.G, d->d_planes);
-                return LC3GPU_OK;
-            });
-        },
-        [&] {
-            return items_stage(*d, P, [&](ItemsGroups groups, int) {
-                GroupTable t;
-                groups((unsigned)LC3_TNS_FPB, t);
-                hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_tns_items_kernel), dim3(t.wg_frame), dim3(LC3_TNS_FPB), LC3_TNS_LDS, stream, t.G, d->d_planes);
-                return LC3GPU_OK;
-            });
-        },
-        [&] {
-            return items_stage(*d, P, [&](ItemsGroups groups, int) {
-                GroupTable t;
-                groups(256u, t);
-                if (mode == LC3_RECON_LATE)
-                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_decode_view_items_late_kernel), dim3(t.wg_stream), dim3(64 * LC3_WG_WAVES), 0, stream, t.G,
-                                       d->d_states, d_entries, (const int32_t *)d->d_planes, d_pcm, io);
-                else
-                    hipLaunchKernelGGL(LC3_MIXED_LAUNCH(lc3_decode_view_items_kernel), dim3(t.wg_stream), dim3(64 * LC3_WG_WAVES), 0, stream, t.G,
-                                       d->d_states, d_entries, (const int32_t *)d->d_planes, d_pcm, io);
-                return LC3GPU_OK;
-            });
-        });
+    rc = decode_items_kernels(d, lc3_dec_views, d->d_mviews_rows(n_views), mode, d_in, d_bad, d_pcm, stream);
     if (rc == LC3GPU_OK)
         for (int i = 0; i < n_views; i++) d->fresh_clear(d->streams[(size_t)views[i].channel].internal);
     return call.end(rc);
@@ -5690,19 +5481,18 @@ int lc3gpu_decode_frame_debug(lc3gpu_decoder *d, int recon_form, const uint8_t *
     if (rc == LC3GPU_OK) rc = decoder_materialise(d);
     if (rc == LC3GPU_OK) rc = decoder_reserve_planes(d, 1, nullptr);
     if (rc == LC3GPU_OK) rc = decoder_debug_begin(d, nullptr);
-    if (rc == LC3GPU_OK && recon_form == LC3_RECON_WAVE) rc = lc3_tns_lds_optin();
+    if (rc == LC3GPU_OK && recon_form == LC3_RECON_WAVE) rc = lc3_lds_optin(*d, lc3_tns_lds_optin);
     if (rc) return rc;
     std::memcpy(d->d_in1, buf_in, (size_t)nbytes);
-    const unsigned fpb = lc3_frame_block_fit(LC3_PARSE_LDS_FIXED, (size_t)(64 + nbytes));
-    const size_t lds = LC3_PARSE_LDS_FIXED + (size_t)fpb * (size_t)(64 + nbytes);
+    const FrameLaunch g = lc3_parse_geometry(false, nbytes);
     std::vector<int32_t> col((size_t)LC3_PLANE_WORDS);
     // the integers: parsing is stateless, so the frame is first parsed in the form that leaves them in the plane
-    LC3_LAUNCH_CFG(lc3_parse_debug_kernel, h, dim3(1), dim3(fpb), lds, nullptr, (const uint8_t *)d->d_in1, d->d_planes, nbytes, 1, (float *)nullptr);
+    LC3_LAUNCH_CFG(lc3_parse_debug_kernel, h, dim3(1), dim3(g.threads), g.lds, nullptr, (const uint8_t *)d->d_in1, d->d_planes, nbytes, 1, (float *)nullptr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(col.data(), d->d_planes, sizeof(int32_t) * LC3_PLANE_WORDS, hipMemcpyDeviceToHost));
     const int parsed = col[AD_OK] != 0, lastnz = col[SI_LASTNZ];
     if (recon_form != LC3_RECON_LATE) {  // the form under test rebuilds the plane column
-        LC3_LAUNCH_CFG(lc3_parse_debug_kernel, h, dim3(1), dim3(fpb), lds, nullptr, (const uint8_t *)d->d_in1, d->d_planes, nbytes, recon_form,
+        LC3_LAUNCH_CFG(lc3_parse_debug_kernel, h, dim3(1), dim3(g.threads), g.lds, nullptr, (const uint8_t *)d->d_in1, d->d_planes, nbytes, recon_form,
                        recon_form == LC3_RECON_LANE ? d->d_dbg : (float *)nullptr);
         HIP_TRY(hipGetLastError());
         if (recon_form == LC3_RECON_WAVE) {

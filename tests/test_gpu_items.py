@@ -376,3 +376,49 @@ def test_items_every_kernel_form_in_a_fresh_process():
         e.update(env)
         r = subprocess.run([sys.executable, "-c", _FORMS_CHILD, ROOT, str(threshold)], env=e, capture_output=True, text=True, timeout=900)
         assert r.returncode == 0 and "forms ok" in r.stdout, (env, r.returncode, r.stdout[-1000:], r.stderr[-3000:])
+
+
+_PAIR_400_CHILD = r"""
+import sys
+import numpy as np
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
+import test_gpu_items as m
+torch = m.torch_mod()
+n = 128 + 1  # one workgroup of the pair kernels full, a second partial
+descs = [(48000, 10000, 400)] * n
+pcm = m.dev(m.synth.make_pcm(n, 1, 480, 48000, seed=29).reshape(-1))
+flags = m.dev((np.random.default_rng(29).random(n) < 0.05).astype(np.uint8))
+st = m.cur_stream()
+calls = {"mixed_items": [(c, 1) for c in range(n)], "mixed_mc_items": [(c, 1, 1) for c in range(n)],
+         "mixed_views": [dict(channel=c, n_frames=1, pcm_off=c * 480, byte_off=c * 400, flag_off=c) for c in range(n)]}  # (compact)
+enc_l, dec_l = m.pkg.Lc3Encoder.mixed(descs), m.pkg.Lc3Decoder.mixed(descs)
+out_l = torch.zeros(n * 400, dtype=torch.uint8, device="cuda")
+enc_l.encode_mixed_list(np.arange(n), pcm, out_l, 1, stream=st)
+pcm_l = torch.zeros(n * 480, dtype=torch.int16, device="cuda")
+dec_l.decode_mixed_list(np.arange(n), out_l, pcm_l, 1, stream=st, d_bad_frame=flags)
+torch.cuda.synchronize()
+assert enc_l.pair_timeouts() == 0 and dec_l.pair_timeouts() == 0
+assert bool(out_l.any()) and bool(pcm_l.any())
+for name, arg in calls.items():
+    enc, dec = m.pkg.Lc3Encoder.mixed(descs), m.pkg.Lc3Decoder.mixed(descs)
+    out = torch.zeros(n * 400, dtype=torch.uint8, device="cuda")
+    getattr(enc, "encode_" + name)(arg, pcm, out, stream=st)
+    got = torch.zeros(n * 480, dtype=torch.int16, device="cuda")
+    getattr(dec, "decode_" + name)(arg, out_l, got, stream=st, d_bad_frame=flags)
+    torch.cuda.synchronize()
+    assert torch.equal(out, out_l), "encode_%s at 400 bytes differs from encode_mixed_list" % name
+    assert torch.equal(got, pcm_l), "decode_%s at 400 bytes differs from decode_mixed_list" % name
+    assert enc.pair_timeouts() == 0 and dec.pair_timeouts() == 0, name
+print("pairs at 400 bytes ok")
+"""
+
+
+def test_pair_kernels_at_400_bytes_in_a_fresh_process():
+    """the pair packer and the pair parser of the items, mc-items and views calls with more than the default 64 KB of dynamic LDS (400-byte
+    frames, 128 per workgroup: lc3_pc_items_optin and its siblings): 129 streams at 48 kHz / 10 ms, one frame each, every launch forced
+    onto the pair kernels; bytes and samples equal to lc3gpu_*_mixed_list on twin handles"""
+    env = dict(os.environ, LC3GPU_PREP_SYMBOLS="0", LC3GPU_RECON="lane", LC3GPU_PACK_PC="1", LC3GPU_PARSE_PC="1")
+    env.pop("LC3GPU_LATE_RECON", None)
+    env.pop("LC3GPU_FPB", None)
+    r = subprocess.run([sys.executable, "-c", _PAIR_400_CHILD, ROOT], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "pairs at 400 bytes ok" in r.stdout, (r.returncode, r.stdout[-1000:], r.stderr[-3000:])
